@@ -11,6 +11,11 @@ from bzx_ctypes import LIB_PATH, ROOT
 
 
 def _lib():
+    # torch bundles its own HIP runtime under the same soname: initialise it before libbzx.so is loaded (as the bzx
+    # fixture does), or on a GPU machine the process gets two runtimes and the GPU tests after these find no device
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.init()
     if not os.path.exists(LIB_PATH):
         import sys
         sys.path.insert(0, ROOT)

@@ -437,35 +437,30 @@ def test_deep_repeats(bzx, oracle):
         assert bzx.compress_buffer(data, 9) == bz2.compress(data, 9)
 
 
-def test_real_files_from_the_image(bzx):
-    """Real data (python sources: 7-bit text with deep repeats; shared objects: 8-bit, highly redundant fat binaries)
-    read from the system image -- the kind of input that synthetic generators miss."""
+def test_real_files_from_the_repository(bzx, oracle):
+    """Real data, the kind of input that synthetic generators miss, taken from the repository itself: its sources,
+    documents and tables (7-bit text with deep repeats), and the shared objects and program that build() makes
+    (8-bit, highly redundant: a fat binary with its gfx950 code object, and host code)."""
     import glob
+    from bzx_ctypes import ROOT
 
-    def collect(patterns, limit):
-        out, seen = bytearray(), set()
+    def collect(patterns):
+        out = bytearray()
         for pat in patterns:
-            for f in sorted(glob.glob(pat, recursive=True)):
-                rp = os.path.realpath(f)
-                if rp in seen or not os.path.isfile(rp):
-                    continue
-                seen.add(rp)
-                try:
-                    with open(rp, "rb") as fh:
-                        out += fh.read(limit - len(out))       # some of these libraries are gigabytes long
-                except OSError:
-                    continue
-                if len(out) >= limit:
-                    return bytes(out[:limit])
+            for f in sorted(glob.glob(os.path.join(ROOT, pat))):
+                with open(f, "rb") as fh:
+                    out += fh.read()
         return bytes(out)
 
-    sets = [collect(["/usr/lib/python3*/**/*.py"], 6 << 20),
-            collect(["/opt/rocm/lib/*.so*", "/usr/lib/x86_64-linux-gnu/*.so*"], 16 << 20)]
-    if not any(len(d) > (1 << 20) for d in sets):
-        pytest.skip("no system files to read")
+    text = ("py", "hip", "h", "c", "cpp", "sh", "md", "csv", "json")
+    sets = [collect([f"{d}*.{ext}" for ext in text for d in ("", "include/", "bzip2-rust_amd/csrc/", "oracle/",
+                                                             "tests/", "tests/emu/", "tools/", "tools/ubench/",
+                                                             "profiles/")]),
+            collect(["bzip2-rust_amd/libbzx.so", "bzip2-rust_amd/bzx", "oracle/libbzx_oracle.so"])]
+    assert all(len(d) > 500_000 for d in sets), [len(d) for d in sets]
     for data in sets:
-        if len(data) > (1 << 20):
-            assert bzx.compress_buffer(data, 9) == bz2.compress(data, 9)
+        for level in (9, 1):                                   # one block or more at -9, five or more at -1
+            assert bzx.compress_buffer(data, level) == bz2.compress(data, level), (len(data), level)
 
 
 def test_structured_fuzz_slice(bzx):
