@@ -1406,6 +1406,10 @@ static int decompress_one(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_o
                 i++;
                 continue;
             }
+            if (ctx->h_blk[i].status & BZX_ST_DC_RANDOMISED) {
+                ctx->err = "randomised block (written by bzip2 0.9.0 or older): not supported";
+                return BZX_E_DATA;
+            }
             if (ctx->h_blk[i].status) {
                 ctx->err = "damaged block in the bzip2 stream";
                 return BZX_E_DATA;

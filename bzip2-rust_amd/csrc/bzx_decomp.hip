@@ -153,7 +153,8 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
     const uint32_t crc = br.get(32);
     const uint32_t randomised = br.get(1);
     const uint32_t orig = br.get(24);
-    if (randomised) err |= DC_ERR_HEADER;          // never written by bzip2 >= 0.9.5 nor by the reference (compress_block.rs:41)
+    // never written by bzip2 >= 0.9.5 nor by the reference (compress_block.rs:41); de-randomising is not implemented
+    if (randomised) err |= BZX_ST_DC_RANDOMISED;
     // symbol map (symbol_map.rs:20-42)
     const uint32_t l1 = br.get(16);
     uint32_t n_in_use = 0;
@@ -170,7 +171,10 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
     const uint32_t alpha = n_in_use + 2;
     const uint32_t n_groups = br.get(3);
     const uint32_t n_sel = br.get(15);
-    if (n_in_use == 0 || n_groups < 2 || n_groups > 6 || n_sel < 1 || n_sel > BZX_MAX_SEL) err |= DC_ERR_HEADER;
+    // any count the 15-bit field holds; only the first BZX_MAX_SEL are kept (libbz2 >= 1.0.8 and decompress.rs ignore
+    // the rest: no block has more than ceil(900001 / 50) groups)
+    if (n_in_use == 0 || n_groups < 2 || n_groups > 6 || n_sel < 1) err |= DC_ERR_HEADER;
+    const uint32_t n_sel_kept = n_sel < BZX_MAX_SEL ? n_sel : BZX_MAX_SEL;
     if (!err) {
         // selectors: unary MTF indices (decompress.rs:159-203)
         uint32_t pos[6] = {0, 1, 2, 3, 4, 5};
@@ -187,7 +191,7 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
             const uint32_t v = pos[j];
             for (uint32_t k = j; k > 0; k--) pos[k] = pos[k - 1];
             pos[0] = v;
-            if (lane == 0) SEL[i] = (uint8_t)v;
+            if (lane == 0 && i < BZX_MAX_SEL) SEL[i] = (uint8_t)v;
         }
         // code lengths, delta coded (decompress.rs:216-260)
         for (uint32_t t = 0; t < n_groups && !err; t++) {
@@ -241,7 +245,7 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
     };
     while (!err) {
         if (g_left == 0) {
-            if (g >= n_sel) {
+            if (g >= n_sel_kept) {
                 err |= DC_ERR_DATA;
                 break;
             }
@@ -415,6 +419,8 @@ __global__ __launch_bounds__(64) void bzx_dc_walk_kernel(BzxBatch B, uint8_t *__
             out++;
         }
     }
+    // four equal bytes end the block: libbz2 reads their count byte past the block's end and refuses the stream
+    if (cnt == 4) B.blk[b].status = DC_ERR_DATA;
     B.blk[b].pack_word = out;                  // expanded length
 }
 

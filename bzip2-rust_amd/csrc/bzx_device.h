@@ -21,6 +21,7 @@
 #define BZX_ST_PERIODIC 1u         // block is u^k, k>1: identical rotations exist
 #define BZX_ST_REDO 2u             // the split kernel handed the block to the general sorter, to be sorted from scratch
 #define BZX_ST_RESUME 4u           // a bucket gave up (deep repeats): the general sorter finishes the leftover groups
+#define BZX_ST_DC_RANDOMISED 0x400u   // decompression: the block has its randomised bit set (not decoded, bzx.h)
 // Rank rounds of the bucket sorter (bzx_bsort.hip): round r compares the ranks h and 2h symbols ahead, h = (give-up
 // depth of the block) * 3^r, and leaves the depth at 3h.
 #ifndef RK_ROUNDS

@@ -197,7 +197,16 @@ void bzx_host_free(void *p);
  * raw bytes; every block CRC and the combined CRC are verified (a mismatch is BZX_E_DATA, unlike the reference, which
  * logs it and continues, decompress.rs:379-386).  The blocks of the stream are decoded side by side.
  * _device: d_bz2 / d_out are DEVICE pointers (d_out 16-byte aligned); _buffer: host pointers.
- * BZX_E_OUTBUF: *out_len = bytes needed.  Bytes after the end-of-stream marker are ignored.
+ * _device decodes ONE stream: bytes after its end-of-stream marker are ignored unless they begin another stream
+ * ("BZh1".."BZh9"), which is refused with BZX_E_DATA (a concatenated .bz2 is not decoded in part).  _buffer decodes
+ * every stream of a concatenated .bz2, one after the other; bytes after the last one that do not begin a stream are
+ * ignored.
+ * BZX_E_OUTBUF: *out_len = bytes needed by _device; by _buffer, bytes needed by the streams up to and including the
+ * one that did not fit -- a lower bound while more streams follow it.
+ * Accepted streams are those libbz2 1.0.8 accepts -- 2..6 tables, 1..32767 selectors (the first 18002 are used),
+ * code lengths 1..20, incomplete prefix codes, RLE1 count bytes 0..255, blocks of up to 100000 * level bytes --
+ * with ONE exception: a block whose randomised bit is set (written by bzip2 0.9.0 and older; never by bzip2 >= 0.9.5
+ * nor by the reference) is refused with BZX_E_DATA and the error text "randomised block ...", where libbz2 decodes it.
  */
 int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len);
 int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len);

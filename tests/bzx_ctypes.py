@@ -33,7 +33,9 @@ class BzxBlockInfo(C.Structure):
 
 
 class BzxError(RuntimeError):
-    pass
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code            # the BZX_E_* return code
 
 
 class BzxLib:
@@ -77,7 +79,7 @@ class BzxLib:
             msg = self.lib.bzx_strerror(rc).decode()
             if self.ctx:
                 msg += ": " + self.lib.bzx_last_error(self.ctx).decode()
-            raise BzxError(f"bzx error {rc}: {msg}")
+            raise BzxError(f"bzx error {rc}: {msg}", rc)
 
     def close(self):
         if self.ctx:
