@@ -1,0 +1,336 @@
+// bzx_batch.hip -- batched compression on gfx950: many independent inputs, one .bz2 stream each.
+//
+// The stage kernels (BWT, MTF, Huffman, emit) already work over any set of blocks; what a batch needs around them is
+// the split, the layout and the framing of MANY inputs at once:
+//   split analysis, once per call over all inputs (kernels A, B, C of bzx_rle1.hip, segmented):
+//     every input starts on a fresh 8 KiB tile and a tile knows its input (tile_seg); A and B load a tile through its
+//     input's pointer at local positions, so the byte before an input's first byte is "none" and is never read.
+//     Run starts are kept as tile0 * 8192 + local position + 1: each input's first byte starts a run, so the global
+//     max-scan carries nothing across inputs; the RLE1 offsets are a global sum-scan minus the input's base.
+//     C: one workgroup per input walks its chain of boundaries (bzx_split_chain) into slots of its own.
+//   per device round (whole inputs, at most R blocks; bzx_api.hip):
+//     describe  block descriptors and block -> input map of the round (one wave per input)
+//     scatter   the RLE1'd bytes of every block into its slab (plain tiles are copied; no block is read in place,
+//               there is no single raw base)
+//     crc       CRC-32/BZIP2 of every block's raw range, through its input's pointer
+//     (run_stages: BWT .. Huffman, unchanged)
+//     layout    per stream: out_bit = 8 * off + 32 + exclusive scan of the block sizes inside the stream; stream
+//               length (32 + bits + 80 + 7) / 8; off = running offset + exclusive scan of the lengths rounded up to 4
+//     (emit, unchanged: streams start on 32-bit words, so no word is shared by two streams)
+//     frame     one wave per stream: "BZh<level>", footer magic, combined CRC over the stream's blocks (0 without blocks)
+#include <hip/hip_runtime.h>
+#include "bzx_device.h"
+#include "bzx_rle1.h"
+
+#define BT_NT 1024        // layout kernel (one workgroup)
+
+__device__ __forceinline__ uint64_t bt_carry(const BzxBatchWs &ws, const BzxSeg &s, uint64_t tile)
+{
+    const uint64_t v = ws.tile_rs[tile], base = s.tile0 * RL_TILE;
+    return v > base ? v - base : 0;
+}
+
+// ---- A: last run start per tile, in the call's position numbering
+__global__ __launch_bounds__(RL_NT) void bzx_bt_runstart_kernel(BzxBatchWs ws)
+{
+    __shared__ uint64_t scratch[RL_NT / 64];
+    for (uint64_t tile = blockIdx.x; tile < ws.ntiles; tile += gridDim.x) {
+        const BzxSeg s = ws.seg[ws.tile_seg[tile]];
+        bool any4;
+        const uint64_t tot = bzx_tile_runstart(s.raw, s.len, tile - s.tile0, scratch, any4);
+        if (threadIdx.x == 0) {
+            ws.tile_rs[tile] = tot ? tot + s.tile0 * RL_TILE : 0;
+            ws.tile_np[tile] = any4 ? 1 : 0;     // provisional: 0 = plain for sure, B skips the tile
+            ws.tile_off[tile] = RL_TILE;
+        }
+    }
+}
+
+// ---- B: emitted bytes of the tiles that may hold a run position k >= 3 (256 tiles per step, flags read coalesced)
+__global__ __launch_bounds__(RL_NT) void bzx_bt_count_kernel(BzxBatchWs ws)
+{
+    __shared__ uint64_t s64[RL_NT / 64];
+    __shared__ uint32_t s32[RL_NT / 64];
+    __shared__ uint32_t s_list[RL_NT];
+    __shared__ uint32_t s_cnt;
+    for (uint64_t base = (uint64_t)blockIdx.x * RL_NT; base < ws.ntiles; base += (uint64_t)gridDim.x * RL_NT) {
+        if (threadIdx.x == 0) s_cnt = 0;
+        __syncthreads();
+        {
+            const uint64_t tile = base + threadIdx.x;
+            if (tile < ws.ntiles && ws.tile_np[tile]) s_list[atomicAdd(&s_cnt, 1u)] = threadIdx.x;
+        }
+        __syncthreads();
+        const uint32_t nlist = s_cnt;
+        for (uint32_t k = 0; k < nlist; k++) {
+            const uint64_t tile = base + s_list[k];
+            const BzxSeg s = ws.seg[ws.tile_seg[tile]];
+            TileInfo ti;
+            tile_analyse(s.raw, s.len, tile - s.tile0, bt_carry(ws, s, tile), s64, s32, ti);
+            const bool np = __syncthreads_or(ti.any_long);
+            if (threadIdx.x == 0) {
+                ws.tile_off[tile] = ti.f_total;
+                ws.tile_np[tile] = np ? 1 : 0;
+            }
+            __syncthreads();
+        }
+        __syncthreads();
+    }
+}
+
+// ---- C: block boundaries, one workgroup per input
+__global__ __launch_bounds__(RL_NT) void bzx_bt_boundaries_kernel(BzxBatchWs ws, uint32_t nmax)
+{
+    __shared__ BzxChainLds lds;
+    for (uint32_t i = blockIdx.x; i < ws.count; i += gridDim.x) {
+        const BzxSeg s = ws.seg[i];
+        BzxChainIO io;
+        io.tile_rs = ws.tile_rs + s.tile0;
+        io.tile_off = ws.tile_off + s.tile0;
+        io.tile_np = ws.tile_np + s.tile0;
+        io.rs_base = s.tile0 * RL_TILE;
+        io.f_base = ws.tile_off[s.tile0];
+        io.blk_raw = ws.blk_raw + s.slot0;
+        io.blk_f = ws.blk_f + s.slot0;
+        io.blk_plain = ws.blk_plain + s.slot0;
+        io.max_blocks = s.nslot - 1;
+        const uint32_t nb = bzx_split_chain(s.raw, s.len, (s.len + RL_TILE - 1) / RL_TILE, nmax, io, lds);
+        if (threadIdx.x == 0) ws.seg_nblk[i] = nb;     // 0xffffffff: more blocks than slots (the host refuses the call)
+        __syncthreads();
+    }
+}
+
+// ---- describe: descriptors of the round's blocks [0, nb) (inputs [i0, i1), whose first block is rb0), one wave per input
+__global__ __launch_bounds__(256) void bzx_bt_describe_kernel(BzxBatchWs ws, uint32_t i0, uint32_t i1, uint32_t rb0,
+                                                              BzxBlock *__restrict__ blk)
+{
+    const uint32_t i = i0 + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (i >= i1) return;
+    const uint32_t n = ws.seg_nblk[i], b0 = ws.seg_blk[i] - rb0, slot0 = ws.seg[i].slot0;
+    for (uint32_t j = lane; j < n; j += 64) {
+        const uint32_t b = b0 + j;
+        ws.blk_seg[b] = i;
+        blk[b].in_off = (uint64_t)b * BZX_BLK_STRIDE;
+        blk[b].n = (uint32_t)(ws.blk_f[slot0 + j + 1] - ws.blk_f[slot0 + j]);
+        blk[b].status = 0;
+    }
+}
+
+// ---- D: scatter the emitted bytes of tiles [t0, t1) (the tiles of the round's inputs) into the block slabs
+__global__ __launch_bounds__(RL_NT) void bzx_bt_scatter_kernel(BzxBatchWs ws, uint64_t t0, uint64_t t1, uint32_t rb0,
+                                                               uint8_t *__restrict__ slabs)
+{
+    __shared__ uint64_t s64[RL_NT / 64];
+    __shared__ uint32_t s32[RL_NT / 64];
+    for (uint64_t tile = t0 + blockIdx.x; tile < t1; tile += gridDim.x) {
+        const uint32_t si = ws.tile_seg[tile];
+        const BzxSeg s = ws.seg[si];
+        const uint64_t lt = tile - s.tile0;
+        TileInfo ti;
+        if (ws.tile_np[tile + 1] == ws.tile_np[tile]) {
+            // no run position k >= 3 in the tile: every byte is emitted once
+            tile_load(s.raw, s.len, lt, ti.t);
+            ti.e_bits = 0x5555555555555555ull;
+            ti.f_excl = threadIdx.x * RL_BYTES;
+        } else {
+            tile_analyse(s.raw, s.len, lt, bt_carry(ws, s, tile), s64, s32, ti);
+        }
+        if (ti.t.nvalid) {
+            const uint64_t *braw = ws.blk_raw + s.slot0, *bf = ws.blk_f + s.slot0;
+            const uint32_t nb = ws.seg_nblk[si], b0 = ws.seg_blk[si] - rb0;
+            // block of my first byte: last block of the input with braw <= p0
+            uint32_t lo = 0, hi = nb;
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (braw[mid] <= ti.t.p0) lo = mid; else hi = mid;
+            }
+            uint32_t kb = lo;
+            uint64_t next_raw = braw[kb + 1];
+            uint64_t f0 = bf[kb];
+            uint8_t *dst = slabs + (size_t)(b0 + kb) * BZX_BLK_STRIDE;
+            uint64_t f = ws.tile_off[tile] - ws.tile_off[s.tile0] + ti.f_excl;
+            for (int i = 0; i < RL_BYTES; i++) {
+                if ((uint32_t)i < ti.t.nvalid) {
+                    const uint64_t p = ti.t.p0 + i;
+                    if (p >= next_raw) {
+                        kb++;
+                        next_raw = braw[kb + 1];
+                        f0 = bf[kb];
+                        dst = slabs + (size_t)(b0 + kb) * BZX_BLK_STRIDE;
+                    }
+                    const uint32_t e = (uint32_t)(ti.e_bits >> (2 * i)) & 3u;
+                    if (e) {
+                        const uint32_t c = tile_byte(ti.t, i);
+                        dst[f - f0] = (uint8_t)c;
+                        if (e == 2) {
+                            // 4th byte of a piece: count the rest of the piece (<= 251 more equal bytes)
+                            uint64_t q = p + 1;
+                            uint32_t extra = 0;
+                            while (q < s.len && extra < 251 && s.raw[q] == c) {
+                                q++;
+                                extra++;
+                            }
+                            dst[f - f0 + 1] = (uint8_t)extra;
+                        }
+                        f += e;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- E: CRC of every block of the round, through its input's pointer
+__global__ __launch_bounds__(CRC_NT) void bzx_bt_crc_kernel(BzxBatchWs ws, uint32_t nb, uint32_t rb0,
+                                                            BzxBlock *__restrict__ blk)
+{
+    __shared__ BzxCrcLds lds;
+    const uint32_t my_weight = bzx_crc_setup(lds);
+    for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
+        const uint32_t si = ws.blk_seg[b];
+        const BzxSeg s = ws.seg[si];
+        const uint32_t j = s.slot0 + (b + rb0 - ws.seg_blk[si]);
+        const uint32_t crc = bzx_crc_range(s.raw, ws.blk_raw[j], ws.blk_raw[j + 1], lds, my_weight);
+        if (threadIdx.x == 0) blk[b].crc = crc;
+    }
+}
+
+// Exclusive sum over the BT_NT lanes of the workgroup; total of all lanes in `total`.
+__device__ __forceinline__ uint64_t bt_excl_sum64(uint64_t v, uint64_t *wsum, uint64_t &total)
+{
+    const uint32_t lane = bzx_lane(), wave = bzx_wave();
+    uint64_t x = v;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint64_t y = __shfl_up(x, d);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    uint64_t pre = 0, tot = 0;
+    for (uint32_t w = 0; w < BT_NT / 64; w++) {
+        if (w < wave) pre += wsum[w];
+        tot += wsum[w];
+    }
+    __syncthreads();
+    total = tot;
+    return pre + x - v;
+}
+
+// ---- layout of the round's streams (inputs [i0, i1), blocks [0, nb)), the first at byte `base` of the output
+__global__ __launch_bounds__(BT_NT) void bzx_bt_layout_kernel(BzxBatchWs ws, uint32_t i0, uint32_t i1, uint32_t rb0,
+                                                              uint32_t nb, BzxBlock *__restrict__ blk, uint64_t base)
+{
+    __shared__ uint64_t wsum[BT_NT / 64];
+    const uint32_t tid = threadIdx.x;
+    uint64_t carry = 0, tot;
+    for (uint32_t b0 = 0; b0 < nb; b0 += BT_NT) {
+        const uint32_t b = b0 + tid;
+        const uint64_t ex = bt_excl_sum64(b < nb ? blk[b].bits : 0, wsum, tot);
+        if (b < nb) ws.pre[b] = carry + ex;
+        carry += tot;
+    }
+    if (tid == 0) ws.pre[nb] = carry;
+    __syncthreads();
+    carry = base;
+    for (uint32_t k0 = i0; k0 < i1; k0 += BT_NT) {
+        const uint32_t i = k0 + tid;
+        uint64_t len = 0;
+        if (i < i1) {
+            const uint32_t first = ws.seg_blk[i] - rb0;
+            len = (32 + (ws.pre[first + ws.seg_nblk[i]] - ws.pre[first]) + 80 + 7) >> 3;
+        }
+        const uint64_t ex = bt_excl_sum64((len + 3) & ~3ull, wsum, tot);
+        if (i < i1) {
+            ws.s_off[i] = carry + ex;
+            ws.s_len[i] = len;
+        }
+        carry += tot;
+    }
+    if (tid == 0) ws.round_end[0] = carry;
+    __syncthreads();
+    for (uint32_t b = tid; b < nb; b += BT_NT) {
+        const uint32_t si = ws.blk_seg[b];
+        blk[b].out_bit = 8 * ws.s_off[si] + 32 + ws.pre[b] - ws.pre[ws.seg_blk[si] - rb0];
+    }
+}
+
+// OR the low nbits (1..32) of val into the big-endian bit buffer at bit pos (nothing else writes these words now)
+__device__ __forceinline__ void bt_or_bits(uint32_t *out, uint64_t pos, uint32_t nbits, uint32_t val)
+{
+    const uint32_t sh = (uint32_t)(pos & 31u);
+    const uint64_t v = (uint64_t)val << (64 - nbits - sh);
+    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
+    if (hi) out[pos >> 5] |= __builtin_bswap32(hi);
+    if (lo) out[(pos >> 5) + 1] |= __builtin_bswap32(lo);
+}
+
+// ---- framing of the round's streams, one wave per stream; after the emit kernel
+__global__ __launch_bounds__(256) void bzx_bt_frame_kernel(BzxBatchWs ws, uint32_t i0, uint32_t i1, uint32_t rb0,
+                                                           const BzxBlock *__restrict__ blk, uint32_t *out, int level)
+{
+    const uint32_t i = i0 + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (i >= i1) return;
+    // combined CRC (crc.rs:25-27): c = rotl(c, 1) ^ crc_b over the stream's blocks, i.e. XOR_j rotl(crc_j, (n-1-j) mod 32)
+    const uint32_t n = ws.seg_nblk[i], b0 = ws.seg_blk[i] - rb0;
+    uint32_t x = 0;
+    for (uint32_t j = lane; j < n; j += 64) {
+        const uint32_t c = blk[b0 + j].crc, r = (n - 1u - j) & 31u;
+        x ^= r ? ((c << r) | (c >> (32u - r))) : c;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) x ^= __shfl_xor(x, d);
+    if (lane == 0) {
+        const uint64_t off = ws.s_off[i];
+        const uint64_t end = 8 * off + 32 + (ws.pre[b0 + n] - ws.pre[b0]);
+        out[off >> 2] = __builtin_bswap32(0x425A6830u + (uint32_t)level);        // "BZh<level>"
+        bt_or_bits(out, end, 24, 0x177245u);
+        bt_or_bits(out, end + 24, 24, 0x385090u);
+        bt_or_bits(out, end + 48, 32, x);
+    }
+}
+
+// ---- host side (called from bzx_api.hip on the context's stream)
+void bzx_split_scan(hipStream_t st, uint64_t *v, uint64_t n, int is_max, uint64_t *segtot);
+
+static uint32_t bt_grid(uint64_t items, uint32_t ncu, uint32_t per_cu)
+{
+    const uint64_t g = (uint64_t)ncu * per_cu;
+    return (uint32_t)(items < g ? (items ? items : 1) : g);
+}
+
+// Kernels A, B, C over every input of the call; writes ws.seg_nblk.
+void bzx_batch_launch_split(const BzxBatchWs &ws, int level, uint32_t ncu, hipStream_t st)
+{
+    const uint32_t grid = bt_grid(ws.ntiles, ncu, 8);
+    hipLaunchKernelGGL(bzx_bt_runstart_kernel, dim3(grid), dim3(RL_NT), 0, st, ws);
+    bzx_split_scan(st, ws.tile_rs, ws.ntiles, 1, ws.segtot);
+    hipLaunchKernelGGL(bzx_bt_count_kernel, dim3(bt_grid((ws.ntiles + RL_NT - 1) / RL_NT, ncu, 8)), dim3(RL_NT), 0, st, ws);
+    bzx_split_scan(st, ws.tile_off, ws.ntiles, 0, ws.segtot);
+    bzx_split_scan(st, ws.tile_np, ws.ntiles, 0, ws.segtot);
+    hipLaunchKernelGGL(bzx_bt_boundaries_kernel, dim3(bt_grid(ws.count, ncu, 4)), dim3(RL_NT), 0, st, ws,
+                       100000u * (uint32_t)level - 19u);
+}
+
+// One round, before the stage kernels: descriptors, slabs and CRCs of blocks [0, nb) (inputs [i0, i1), tiles [t0, t1)).
+void bzx_batch_launch_round(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint64_t t0, uint64_t t1, uint32_t rb0,
+                            uint32_t nb, uint8_t *slabs, BzxBlock *blk, uint32_t ncu, hipStream_t st)
+{
+    if (nb == 0) return;
+    hipLaunchKernelGGL(bzx_bt_describe_kernel, dim3((i1 - i0 + 3) / 4), dim3(256), 0, st, ws, i0, i1, rb0, blk);
+    hipLaunchKernelGGL(bzx_bt_scatter_kernel, dim3(bt_grid(t1 - t0, ncu, 8)), dim3(RL_NT), 0, st, ws, t0, t1, rb0, slabs);
+    hipLaunchKernelGGL(bzx_bt_crc_kernel, dim3(bt_grid(nb, ncu, 1)), dim3(CRC_NT), 0, st, ws, nb, rb0, blk);
+}
+
+void bzx_batch_launch_layout(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint32_t rb0, uint32_t nb, BzxBlock *blk,
+                             uint64_t base, hipStream_t st)
+{
+    hipLaunchKernelGGL(bzx_bt_layout_kernel, dim3(1), dim3(BT_NT), 0, st, ws, i0, i1, rb0, nb, blk, base);
+}
+
+void bzx_batch_launch_frame(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint32_t rb0, const BzxBlock *blk, void *d_out,
+                            int level, hipStream_t st)
+{
+    hipLaunchKernelGGL(bzx_bt_frame_kernel, dim3((i1 - i0 + 3) / 4), dim3(256), 0, st, ws, i0, i1, rb0, blk,
+                       (uint32_t *)d_out, level);
+}

@@ -175,6 +175,37 @@ struct BzxSplitWs {
 };
 
 
+// Batched compression (bzx_batch.hip): many independent inputs, one .bz2 stream each.  Every input starts on a fresh
+// 8 KiB tile of the call's tile numbering, and its block boundaries live in slots of its own.
+struct BzxSeg {
+    const uint8_t *raw;     // device pointer, 16-byte aligned (not read when len == 0)
+    uint64_t len;
+    uint64_t tile0;         // first tile of the input (the tiles of input i + 1 follow those of input i)
+    uint32_t slot0;         // first slot of the input in BzxBatchWs.blk_raw / blk_f / blk_plain
+    uint32_t nslot;         // slots of the input: its block bound (len + len/4)/nmax + 2, and one for the end entry
+};
+
+struct BzxBatchWs {
+    BzxSeg *seg;            // [count]
+    uint32_t *tile_seg;     // [ntiles] input of every tile
+    uint64_t *tile_rs;      // [ntiles+1] as BzxSplitWs, over all tiles of the call.  Run starts are tile0 * 8192 + local
+    uint64_t *tile_off;     //            position + 1: the first byte of every input starts a run, so the max-scan
+    uint64_t *tile_np;      //            carries nothing from one input into the next
+    uint64_t *blk_raw;      // [nslots] per input: local raw start of each block; entry nblk = len
+    uint64_t *blk_f;        // [nslots] ... RLE1 offset (F) of each block start; entry nblk = F(len)
+    uint32_t *blk_plain;    // [nslots] (written by the chain; a batch scatters every block into the slabs)
+    uint32_t *seg_nblk;     // [count] blocks of each input
+    uint32_t *seg_blk;      // [count] first block of each input in the call's block numbering (set by the host)
+    uint32_t *blk_seg;      // [round blocks] input of every block of the round
+    uint64_t *pre;          // [round blocks + 1] exclusive scan of the round's block sizes (bits)
+    uint64_t *s_off;        // [count] byte offset of each stream in the output
+    uint64_t *s_len;        // [count] byte length of each stream
+    uint64_t *round_end;    // [1] end of the round's last stream, rounded up to 4 bytes
+    uint64_t *segtot;       // scratch of the tile scans
+    uint64_t ntiles;
+    uint32_t count;
+};
+
 // Slab of block b.  Block DESCRIPTORS (B.blk, plist, redo_list) are indexed by the global block number; the per-block
 // slabs (bwt, rank, mtfv, tables, packed block, records, RLE1 bytes) exist only for the blocks a launch owns
 // (round-robin sharding over GPUs: b = blk_first + j * blk_step owns slab j), so a rank of an 8-GPU job holds 1/8

@@ -117,6 +117,38 @@ int bzx_compress_buffer(bzx_ctx *ctx, const uint8_t *raw, size_t len, int level,
                         size_t *out_len);
 
 /*
+ * Batched compression: count independent inputs -> count independent .bz2 streams, all on the device.  The form for
+ * many small objects (files, records, pages): their blocks share device batches, so a batch of thousands of inputs
+ * costs a few launches and host synchronisations per round instead of some twenty launches and three
+ * synchronisations per input.
+ * Stream i is byte-identical to bzx_compress_device on input i alone (and to libbz2's output at that level); an empty
+ * input gives the 14-byte empty stream.  Stream i starts at d_out + out_offs[i] (offsets ascend with i and are
+ * multiples of 4; the bytes between two streams are zero) and is out_lens[i] bytes long.  out_offs / out_lens are HOST
+ * arrays of count entries.
+ * d_raws: HOST array of count DEVICE pointers, each 16-byte aligned (NULL allowed where lens[i] == 0); d_out: DEVICE
+ * buffer of cap bytes, 4-byte aligned.
+ * Returns BZX_OK at once for count == 0 (nothing written); BZX_E_PARAM for a bad level, NULL arrays or a misaligned
+ * pointer (bzx_last_error names the input); BZX_E_OUTBUF when the streams do not fit cap
+ * (bzx_compress_batch_bound(count, lens) always fits).  After any error the context stays usable.
+ * Rounds: the inputs run in device rounds of whole inputs with at most R blocks each, R = the larger of the block
+ * slabs the context holds (at least the max_blocks of bzx_ctx_create, 16 for 0; more after a larger call) and the
+ * blocks of the largest single input.  A small input is one block, so R is also the number of small inputs per round;
+ * a slab costs about 28 MB of device memory: a larger max_blocks means fewer rounds and more memory.  A call costs one
+ * host synchronisation for the block counts of all inputs, one per round and one at the end.
+ * bzx_get_stats after a batch call: nblk, n_periodic, raw_bytes, rle1_bytes, mtf_symbols and out_bits are sums over
+ * all streams, the stage times and sorter counters are summed over the rounds, ms_total is the device time of the
+ * call.  bzx_get_block_info after a batch call returns BZX_E_STATE (no per-block figures are kept).
+ */
+/* Upper bound of the output of a batch: sum over i of round_up4(lens[i] + lens[i]/50 + 4096). */
+size_t bzx_compress_batch_bound(uint32_t count, const size_t *lens);
+int bzx_compress_batch_device(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, const size_t *lens, int level,
+                              void *d_out, size_t cap, size_t *out_offs, size_t *out_lens);
+/* The same with host buffers: the inputs are staged to the device (H2D) and the streams come back (D2H).  The staged
+ * inputs and the outputs of one call are all on the device at once (about twice the input), for that call only. */
+int bzx_compress_batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws, const size_t *lens, int level,
+                              uint8_t *out, size_t cap, size_t *out_offs, size_t *out_lens);
+
+/*
  * Multi-GPU sharding (replaces the rayon fan-out over blocks, compress.rs:125-132, across
  * devices): bzip2 block i belongs to rank i mod world.  No collective happens inside the library; the
  * caller (one process per GPU) exchanges 8 bytes per block between the two calls:
@@ -211,7 +243,7 @@ void bzx_host_free(void *p);
 int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len);
 int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len);
 
-/* Per-call telemetry of the last bzx_compress_device/_buffer/_blocks call. */
+/* Per-call telemetry of the last bzx_compress_device/_buffer/_blocks/_batch_* call. */
 typedef struct {
     uint32_t nblk;
     uint32_t n_periodic;        /* blocks flagged periodic */
@@ -239,7 +271,8 @@ int bzx_get_stats(const bzx_ctx *ctx, bzx_stats *out);
  * Per-block figures of the last bzx_compress_device / bzx_compress_buffer / bzx_cstream_* / bzx_compress_block(s)
  * call, blocks in stream order (a chunked stream: as many as the context's descriptor table holds, i.e. at least
  * the max_blocks of bzx_ctx_create; BZX_E_PARAM beyond) -- what the reference logs per block at -vvv
- * (src/compression/compress_block.rs:58-63, src/huffman_coding/huffman.rs:176-181).
+ * (src/compression/compress_block.rs:58-63, src/huffman_coding/huffman.rs:176-181).  After a bzx_compress_batch_*
+ * call it returns BZX_E_STATE: a batch keeps no per-block figures.
  */
 typedef struct bzx_block_info {
     uint32_t n;               /* RLE1'd bytes in the block */

@@ -2,7 +2,9 @@
 // and C bzip2's conventions: -z / -d / -t, -1..-9, -c, -k, -f, -q, -v.  SURVEY.md 8f N4.  Host glue only: every byte of
 // compression and decompression work happens on the device behind include/bzx.h; without a HIP device the tool fails.
 // Compression streams the input through bzx_cstream_feed in chunks (files larger than device memory are fine and the
-// output is written while the next chunk is compressed); decompression reads the whole .bz2.
+// output is written while the next chunk is compressed); decompression reads the whole .bz2.  Compressing two or more
+// named files (without -v), the regular files of at most 16 MiB are read and compressed together, one
+// bzx_compress_batch_buffer call per batch of up to 256 MiB, each into its own .bz2.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -137,6 +139,87 @@ static int do_unzip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char
     return 0;
 }
 
+// The end of one file's work: output flushed and closed (or removed after a failure), input removed unless -k.
+static int finish_file(const Opts &o, FILE *out, const std::string &oname, const std::string &f, int r)
+{
+    int wr = 0;                                  // the output is complete on disk only when flush and close succeed
+    if (out && out != stdout) {
+        if (fflush(out) != 0 || ferror(out)) wr = 1;
+        if (fclose(out) != 0) wr = 1;
+        if (wr && !r && !o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
+        if (r || wr) unlink(oname.c_str());      // never leave a partial output ...
+        else if (!o.keep && f != "-") unlink(f.c_str());   // ... and never remove the input unless the output is whole
+    } else if (out) {
+        if (fflush(out) != 0 || ferror(out)) wr = 1;
+    }
+    return r | wr;
+}
+
+// Opens the output of input f (after the same checks, with the same messages, as C bzip2): 0, or 1 after a message.
+static int open_output(const Opts &o, const std::string &f, bool std_in, FILE **out, std::string &oname)
+{
+    *out = nullptr;
+    if (o.mode == TEST) return 0;
+    if (std_in || o.to_stdout) {
+        *out = stdout;
+        return 0;
+    }
+    if (o.mode == ZIP) oname = f + ".bz2";
+    else if (f.size() > 4 && f.compare(f.size() - 4, 4, ".bz2") == 0) oname = f.substr(0, f.size() - 4);
+    else oname = f + ".out";
+    struct stat sb;
+    if (!o.force && stat(oname.c_str(), &sb) == 0) {
+        if (!o.quiet) fprintf(stderr, "bzx: %s already exists (use -f)\n", oname.c_str());
+        return 1;
+    }
+    *out = fopen(oname.c_str(), "wb");
+    if (!*out) {
+        if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
+        return 1;
+    }
+    return 0;
+}
+
+// Small files waiting for one batched compression call, in argument order.
+struct Pending {
+    std::string name, oname;
+    FILE *out;
+    std::vector<uint8_t> data;
+};
+static const size_t BATCH_FILE_MAX = (size_t)16 << 20;     // larger files take the chunked path
+static const size_t BATCH_BYTES = (size_t)256 << 20;       // input bytes per batch call
+static const size_t BATCH_FILES = 512;                     // files per batch call (their outputs stay open until it)
+static const uint32_t BATCH_SLABS = 320;                   // context slabs: a 256 MiB batch at -9 in one device round
+
+static int flush_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &pend, size_t &pend_bytes)
+{
+    if (pend.empty()) return 0;
+    const uint32_t n = (uint32_t)pend.size();
+    std::vector<const uint8_t *> raws(n);
+    std::vector<size_t> lens(n), offs(n, 0), olens(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        raws[i] = pend[i].data.data();
+        lens[i] = pend[i].data.size();
+    }
+    const size_t cap = bzx_compress_batch_bound(n, lens.data());
+    uint8_t *obuf = (uint8_t *)malloc(cap ? cap : 1);
+    const int rc = obuf ? bzx_compress_batch_buffer(ctx, n, raws.data(), lens.data(), o.level, obuf, cap, offs.data(),
+                                                    olens.data())
+                        : BZX_E_NOMEM;
+    int ret = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        Pending &p = pend[i];
+        int r = 0;
+        if (rc) r = fail(o, "compression failed", p.name.c_str(), obuf ? ctx : nullptr, rc);
+        else if (fwrite(obuf + offs[i], 1, olens[i], p.out) != olens[i]) r = fail(o, strerror(errno), p.name.c_str(), nullptr, BZX_OK);
+        ret |= finish_file(o, p.out, p.oname, p.name, r);
+    }
+    free(obuf);
+    pend.clear();
+    pend_bytes = 0;
+    return ret;
+}
+
 int main(int argc, char **argv)
 {
     Opts o;
@@ -178,61 +261,60 @@ int main(int argc, char **argv)
             }
         }
     }
+    if (o.files.empty()) o.files.push_back("-");
+    // two or more named files to compress, without -v: the small regular ones go through the batched entry point
+    const bool batching = o.mode == ZIP && o.files.size() >= 2 && !o.verbose;
     bzx_ctx *ctx = nullptr;
-    int rc = bzx_ctx_create(0, 0, &ctx);
+    int rc = bzx_ctx_create(0, batching ? BATCH_SLABS : 0, &ctx);
     if (rc) {
         fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
         return 2;
     }
-    if (o.files.empty()) o.files.push_back("-");
     int ret = 0;
+    std::vector<Pending> pend;
+    size_t pend_bytes = 0;
     for (const std::string &f : o.files) {
         const bool std_in = f == "-";
+        if (std_in && batching) ret |= flush_batch(o, ctx, pend, pend_bytes);
         FILE *in = std_in ? stdin : fopen(f.c_str(), "rb");
         if (!in) {
             if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", f.c_str(), strerror(errno));
             ret = 1;
             continue;
         }
+        struct stat sb;
+        const bool small = batching && !std_in && fstat(fileno(in), &sb) == 0 && S_ISREG(sb.st_mode) &&
+                           (size_t)sb.st_size <= BATCH_FILE_MAX;
+        if (batching && !small) {
+            ret |= flush_batch(o, ctx, pend, pend_bytes);
+        } else if (small && (pend_bytes + (size_t)sb.st_size > BATCH_BYTES || pend.size() >= BATCH_FILES)) {
+            ret |= flush_batch(o, ctx, pend, pend_bytes);
+        }
         std::string oname;
         FILE *out = nullptr;
-        if (o.mode != TEST) {
-            if (std_in || o.to_stdout) {
-                out = stdout;
-            } else {
-                if (o.mode == ZIP) oname = f + ".bz2";
-                else if (f.size() > 4 && f.compare(f.size() - 4, 4, ".bz2") == 0) oname = f.substr(0, f.size() - 4);
-                else oname = f + ".out";
-                struct stat sb;
-                if (!o.force && stat(oname.c_str(), &sb) == 0) {
-                    if (!o.quiet) fprintf(stderr, "bzx: %s already exists (use -f)\n", oname.c_str());
-                    fclose(in);
-                    ret = 1;
-                    continue;
-                }
-                out = fopen(oname.c_str(), "wb");
-                if (!out) {
-                    if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
-                    fclose(in);
-                    ret = 1;
-                    continue;
-                }
+        if (open_output(o, f, std_in, &out, oname)) {
+            if (!std_in) fclose(in);
+            ret = 1;
+            continue;
+        }
+        if (small) {
+            Pending p{f, oname, out, {}};
+            p.data.reserve((size_t)sb.st_size);
+            const bool ok = read_all(in, p.data);
+            fclose(in);
+            if (!ok) {
+                ret |= finish_file(o, out, oname, f, fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK));
+                continue;
             }
+            pend_bytes += p.data.size();
+            pend.push_back(std::move(p));
+            continue;
         }
         const int r = o.mode == ZIP ? do_zip(o, ctx, in, out, f.c_str()) : do_unzip(o, ctx, in, out, f.c_str());
         if (!std_in) fclose(in);
-        int wr = 0;                                  // the output is complete on disk only when flush and close succeed
-        if (out && out != stdout) {
-            if (fflush(out) != 0 || ferror(out)) wr = 1;
-            if (fclose(out) != 0) wr = 1;
-            if (wr && !r && !o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
-            if (r || wr) unlink(oname.c_str());      // never leave a partial output ...
-            else if (!o.keep) unlink(f.c_str());     // ... and never remove the input unless the output is whole
-        } else if (out) {
-            if (fflush(out) != 0 || ferror(out)) wr = 1;
-        }
-        ret |= r | wr;
+        ret |= finish_file(o, out, oname, f, r);
     }
+    ret |= flush_batch(o, ctx, pend, pend_bytes);
     bzx_ctx_destroy(ctx);
     return ret;
 }
