@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SRCS=$(ls csrc/*.hip)
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-function -I ../include"
+FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wl,-z,defs -Wall -Wno-unused-function -I ../include"
 if [ "$1" = "diag" ]; then
     shift
     $HIPCC $FLAGS -DBZX_DIAG $SRCS -o libbzx_diag.so "$@"

@@ -8,7 +8,7 @@
 //     Run starts are kept as tile0 * 8192 + local position + 1: each input's first byte starts a run, so the global
 //     max-scan carries nothing across inputs; the RLE1 offsets are a global sum-scan minus the input's base.
 //     C: one workgroup per input walks its chain of boundaries (bzx_split_chain) into slots of its own.
-//   per device round (whole inputs, at most R blocks; bzx_api.hip):
+//   per device round (whole inputs, at most R blocks; batch_run below):
 //     describe  block descriptors and block -> input map of the round (one wave per input)
 //     scatter   the RLE1'd bytes of every block into its slab (plain tiles are copied; no block is read in place,
 //               there is no single raw base)
@@ -19,7 +19,9 @@
 //     (emit, unchanged: streams start on 32-bit words, so no word is shared by two streams)
 //     frame     one wave per stream: "BZh<level>", footer magic, combined CRC over the stream's blocks (0 without blocks)
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include <string.h>
+#include <new>
+#include "bzx_host.h"
 #include "bzx_rle1.h"
 
 #define BT_NT 1024        // layout kernel (one workgroup)
@@ -290,9 +292,7 @@ __global__ __launch_bounds__(256) void bzx_bt_frame_kernel(BzxBatchWs ws, uint32
     }
 }
 
-// ---- host side (called from bzx_api.hip on the context's stream)
-void bzx_split_scan(hipStream_t st, uint64_t *v, uint64_t n, int is_max, uint64_t *segtot);
-
+// ---- host side (on the context's stream)
 static uint32_t bt_grid(uint64_t items, uint32_t ncu, uint32_t per_cu)
 {
     const uint64_t g = (uint64_t)ncu * per_cu;
@@ -300,7 +300,7 @@ static uint32_t bt_grid(uint64_t items, uint32_t ncu, uint32_t per_cu)
 }
 
 // Kernels A, B, C over every input of the call; writes ws.seg_nblk.
-void bzx_batch_launch_split(const BzxBatchWs &ws, int level, uint32_t ncu, hipStream_t st)
+static void bzx_batch_launch_split(const BzxBatchWs &ws, int level, uint32_t ncu, hipStream_t st)
 {
     const uint32_t grid = bt_grid(ws.ntiles, ncu, 8);
     hipLaunchKernelGGL(bzx_bt_runstart_kernel, dim3(grid), dim3(RL_NT), 0, st, ws);
@@ -313,8 +313,8 @@ void bzx_batch_launch_split(const BzxBatchWs &ws, int level, uint32_t ncu, hipSt
 }
 
 // One round, before the stage kernels: descriptors, slabs and CRCs of blocks [0, nb) (inputs [i0, i1), tiles [t0, t1)).
-void bzx_batch_launch_round(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint64_t t0, uint64_t t1, uint32_t rb0,
-                            uint32_t nb, uint8_t *slabs, BzxBlock *blk, uint32_t ncu, hipStream_t st)
+static void bzx_batch_launch_round(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint64_t t0, uint64_t t1,
+                                   uint32_t rb0, uint32_t nb, uint8_t *slabs, BzxBlock *blk, uint32_t ncu, hipStream_t st)
 {
     if (nb == 0) return;
     hipLaunchKernelGGL(bzx_bt_describe_kernel, dim3((i1 - i0 + 3) / 4), dim3(256), 0, st, ws, i0, i1, rb0, blk);
@@ -322,15 +322,347 @@ void bzx_batch_launch_round(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint
     hipLaunchKernelGGL(bzx_bt_crc_kernel, dim3(bt_grid(nb, ncu, 1)), dim3(CRC_NT), 0, st, ws, nb, rb0, blk);
 }
 
-void bzx_batch_launch_layout(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint32_t rb0, uint32_t nb, BzxBlock *blk,
-                             uint64_t base, hipStream_t st)
+static void bzx_batch_launch_layout(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint32_t rb0, uint32_t nb,
+                                    BzxBlock *blk, uint64_t base, hipStream_t st)
 {
     hipLaunchKernelGGL(bzx_bt_layout_kernel, dim3(1), dim3(BT_NT), 0, st, ws, i0, i1, rb0, nb, blk, base);
 }
 
-void bzx_batch_launch_frame(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint32_t rb0, const BzxBlock *blk, void *d_out,
-                            int level, hipStream_t st)
+static void bzx_batch_launch_frame(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint32_t rb0, const BzxBlock *blk,
+                                   void *d_out, int level, hipStream_t st)
 {
     hipLaunchKernelGGL(bzx_bt_frame_kernel, dim3((i1 - i0 + 3) / 4), dim3(256), 0, st, ws, i0, i1, rb0, blk,
                        (uint32_t *)d_out, level);
+}
+
+// ---- batched compression: count independent inputs -> count independent .bz2 streams (include/bzx.h)
+static size_t round_up4(size_t x) { return (x + 3) & ~(size_t)3; }
+
+extern "C" size_t bzx_compress_batch_bound(uint32_t count, const size_t *lens)
+{
+    size_t sum = 0;
+    for (uint32_t i = 0; lens && i < count; i++) sum += round_up4(lens[i] + lens[i] / 50 + 4096);
+    return sum;
+}
+
+// Carves the device tables of a batch call out of ctx->batch_ws (grown on demand).
+static int batch_ws_alloc(bzx_ctx *ctx, uint32_t count, uint64_t ntiles, uint64_t nslots, uint32_t max_round, BzxBatchWs *ws)
+{
+    const size_t words = (size_t)count * (sizeof(BzxSeg) / 8) + (ntiles + 8) / 2 + 3 * (ntiles + 2) + 2 * (nslots + 2) +
+                         (nslots + 8) / 2 + 2 * ((size_t)count + 2) / 2 + ((size_t)max_round + 8) / 2 + ((size_t)max_round + 2) +
+                         2 * ((size_t)count + 2) + 2 + bzx_split_scan_words(ntiles) + 16;
+    const size_t bytes = words * 8;
+    if (bytes > ctx->batch_ws_bytes) {
+        if (ctx->batch_ws) (void)hipFree(ctx->batch_ws);
+        ctx->batch_ws = nullptr;
+        ctx->batch_ws_bytes = 0;
+        if (hipMalloc(&ctx->batch_ws, bytes) != hipSuccess) {
+            ctx->err = "hipMalloc(batch tables) failed";
+            return BZX_E_NOMEM;
+        }
+        ctx->batch_ws_bytes = bytes;
+    }
+    uint64_t *q = (uint64_t *)ctx->batch_ws;
+    auto take = [&](size_t nwords) {
+        uint64_t *p = q;
+        q += nwords;
+        return p;
+    };
+    ws->seg = (BzxSeg *)take((size_t)count * (sizeof(BzxSeg) / 8));
+    ws->tile_seg = (uint32_t *)take((ntiles + 8) / 2);
+    ws->tile_rs = take(ntiles + 2);
+    ws->tile_off = take(ntiles + 2);
+    ws->tile_np = take(ntiles + 2);
+    ws->blk_raw = take(nslots + 2);
+    ws->blk_f = take(nslots + 2);
+    ws->blk_plain = (uint32_t *)take((nslots + 8) / 2);
+    ws->seg_nblk = (uint32_t *)take(((size_t)count + 2) / 2);
+    ws->seg_blk = (uint32_t *)take(((size_t)count + 2) / 2);
+    ws->blk_seg = (uint32_t *)take(((size_t)max_round + 8) / 2);
+    ws->pre = take((size_t)max_round + 2);
+    ws->s_off = take((size_t)count + 2);
+    ws->s_len = take((size_t)count + 2);
+    ws->round_end = take(2);
+    ws->segtot = take(bzx_split_scan_words(ntiles));
+    ws->ntiles = ntiles;
+    ws->count = count;
+    return BZX_OK;
+}
+
+// Argument checks shared by both forms; device: the inputs and the output are device pointers (alignment checked).
+static int batch_args(bzx_ctx *ctx, const char *fn, uint32_t count, const void *const *raws, const size_t *lens,
+                      const void *out, size_t *out_offs, size_t *out_lens, bool device)
+{
+    if (!raws || !lens || !out || !out_offs || !out_lens) {
+        ctx->err = std::string(fn) + ": NULL array or output pointer";
+        return BZX_E_PARAM;
+    }
+    if (device && ((uintptr_t)out & 3u)) {
+        ctx->err = std::string(fn) + ": d_out must be 4-byte aligned";
+        return BZX_E_PARAM;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        if (lens[i] && !raws[i]) {
+            ctx->err = std::string(fn) + ": input " + std::to_string(i) + ": NULL pointer with a non-zero length";
+            return BZX_E_PARAM;
+        }
+        if (device && lens[i] && ((uintptr_t)raws[i] & 15u)) {
+            ctx->err = std::string(fn) + ": input " + std::to_string(i) + ": d_raws[" + std::to_string(i) +
+                       "] must be 16-byte aligned";
+            return BZX_E_PARAM;
+        }
+    }
+    return BZX_OK;
+}
+
+// Adds the figures of the BWT, MTF and Huffman stages of a run (collect_stage_times) to an accumulator.
+static void add_stage_figures(bzx_stats &acc, const bzx_stats &run)
+{
+    acc.ms_bwt += run.ms_bwt;
+    acc.ms_mtf += run.ms_mtf;
+    acc.ms_huffman += run.ms_huffman;
+    acc.ms_bwt_split += run.ms_bwt_split;
+    acc.ms_bwt_sort += run.ms_bwt_sort;
+    acc.ms_bwt_general += run.ms_bwt_general;
+    acc.ms_bwt_rank += run.ms_bwt_rank;
+    acc.bwt_launches += run.bwt_launches;
+    acc.n_redo += run.n_redo;
+    acc.n_buckets += run.n_buckets;
+    acc.n_open_buckets += run.n_open_buckets;
+    acc.n_open_left += run.n_open_left;
+    acc.n_resume_left += run.n_resume_left;
+    acc.n_from_scratch += run.n_from_scratch;
+    acc.n_unsorted += run.n_unsorted;
+}
+
+// The batch on device buffers: split analysis of all inputs, then rounds of whole inputs (at most R blocks each).
+static int batch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, const size_t *lens, int level, void *d_out,
+                     size_t cap, size_t *out_offs, size_t *out_lens)
+{
+    hipStream_t st = ctx->stream;
+    const uint64_t nmax = (uint64_t)100000 * level - 19;
+    std::vector<BzxSeg> seg(count);
+    uint64_t ntiles = 0, nslots = 0;
+    uint32_t max_bound = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        const uint64_t len = lens[i];
+        const uint64_t bound = (len + len / 4) / nmax + 2;
+        if (bound > 0x7fffffffu) return BZX_E_PARAM;
+        seg[i].raw = (const uint8_t *)d_raws[i];
+        seg[i].len = len;
+        seg[i].tile0 = ntiles;
+        seg[i].slot0 = (uint32_t)nslots;
+        seg[i].nslot = (uint32_t)bound + 1;
+        ntiles += (len + 8191) / 8192;
+        nslots += bound + 1;
+        if (nslots > 0x7fffffffu) {
+            ctx->err = "bzx_compress_batch: too many inputs in one call";
+            return BZX_E_PARAM;
+        }
+        if (bound > max_bound) max_bound = (uint32_t)bound;
+    }
+    const uint32_t max_round = ctx->cap_slabs > max_bound ? ctx->cap_slabs : max_bound;
+    std::vector<uint32_t> tile_seg(ntiles);
+    for (uint32_t i = 0; i < count; i++) {
+        const uint64_t t1 = i + 1 < count ? seg[i + 1].tile0 : ntiles;
+        for (uint64_t t = seg[i].tile0; t < t1; t++) tile_seg[t] = i;
+    }
+    BzxBatchWs ws;
+    int rc = batch_ws_alloc(ctx, count, ntiles, nslots, max_round, &ws);
+    if (rc) return rc;
+    bzx_stats &stt = ctx->stats;
+    memset(&stt, 0, sizeof(stt));
+    ctx->stats_batch = true;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[5], st));
+    HIP_TRY(ctx, hipMemcpyAsync(ws.seg, seg.data(), count * sizeof(BzxSeg), hipMemcpyHostToDevice, st));
+    if (ntiles) HIP_TRY(ctx, hipMemcpyAsync(ws.tile_seg, tile_seg.data(), ntiles * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    bzx_batch_launch_split(ws, level, (uint32_t)ctx->n_cu, st);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[6], st));
+    std::vector<uint32_t> nblk(count), first(count);
+    HIP_TRY(ctx, hipMemcpyAsync(nblk.data(), ws.seg_nblk, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&stt.ms_split, ctx->ev[5], ctx->ev[6]);
+    // block numbering of the call; rounds of whole inputs with at most R blocks
+    uint32_t R = ctx->cap_slabs, total = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (nblk[i] >= seg[i].nslot || (lens[i] && nblk[i] == 0)) {
+            ctx->err = "device block splitter produced an impossible block count (input " + std::to_string(i) + ")";
+            return BZX_E_HIP;
+        }
+        first[i] = total;
+        total += nblk[i];
+        if (nblk[i] > R) R = nblk[i];
+    }
+    if ((rc = ensure_blocks(ctx, R))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ws.seg_blk, first.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    BzxBatch &B = ctx->B;
+    B.in = ctx->d_in;
+    B.raw = nullptr;                   // every block of a batch is in the slabs
+    B.blk_first = 0;
+    B.blk_step = 1;
+    B.packed = 0;
+    B.out = (uint32_t *)d_out;
+    const size_t cap4 = cap & ~(size_t)3;
+    uint64_t base = 0;
+    bool emit_pending = false;
+    std::vector<BzxBlock> hb;
+    for (uint32_t i0 = 0; i0 < count;) {
+        uint32_t i1 = i0, nb = 0;
+        while (i1 < count && nb + nblk[i1] <= R) nb += nblk[i1++];
+        const uint32_t rb0 = first[i0];
+        const uint64_t t0 = seg[i0].tile0, t1 = i1 < count ? seg[i1].tile0 : ntiles;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_bt[0], st));
+        bzx_batch_launch_round(ws, i0, i1, t0, t1, rb0, nb, ctx->d_in, B.blk, (uint32_t)ctx->n_cu, st);
+        if (nb && (rc = run_stages(ctx, nb, STG_BWT | STG_MTF | STG_HUF))) return rc;
+        bzx_batch_launch_layout(ws, i0, i1, rb0, nb, B.blk, base, st);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(out_offs + i0, ws.s_off + i0, (i1 - i0) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(out_lens + i0, ws.s_len + i0, (i1 - i0) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_scalars, ws.round_end, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (nb) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, nb * sizeof(BzxBlock), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));             // the round's one host synchronisation
+        const uint64_t end = ctx->h_scalars[0];
+        if (emit_pending) {                                  // emit time of the previous round
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ctx->ev_bt[1], ctx->ev_bt[2]);
+            stt.ms_emit += ms;
+            emit_pending = false;
+        }
+        if (nb) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ctx->ev_bt[0], ctx->ev[0]);
+            const bzx_stats before = stt;
+            collect_stage_times(ctx);                        // this round's figures, summed over the rounds
+            add_stage_figures(stt, before);
+            stt.ms_split = before.ms_split + ms;
+            stt.ms_emit = before.ms_emit;
+        }
+        if (end > cap4) {
+            ctx->err = "output buffer too small for the batch (input " + std::to_string(i0) + " onwards does not fit; "
+                       "bzx_compress_batch_bound always fits)";
+            return BZX_E_OUTBUF;
+        }
+        fold_blocks(stt, ctx->h_blk, 0, nb, 1);
+        for (uint32_t i = i0; i < i1; i++) {
+            stt.raw_bytes += lens[i];
+            stt.out_bits += (uint64_t)out_lens[i] * 8;
+        }
+        stt.nblk += nb;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_bt[1], st));
+        HIP_TRY(ctx, hipMemsetAsync((uint8_t *)d_out + base, 0, end - base, st));
+        B.nblk = nb;
+        if (nb) bzx_launch_emit(B, grid_for(ctx, nb, 2), st);
+        bzx_batch_launch_frame(ws, i0, i1, rb0, B.blk, d_out, level, st);
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_bt[2], st));
+        HIP_TRY(ctx, hipGetLastError());
+        emit_pending = true;
+        base = end;
+        i0 = i1;
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[7], st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (emit_pending) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ctx->ev_bt[1], ctx->ev_bt[2]);
+        stt.ms_emit += ms;
+    }
+    (void)hipEventElapsedTime(&stt.ms_total, ctx->ev[5], ctx->ev[7]);
+    return BZX_OK;
+}
+
+extern "C" int bzx_compress_batch_device(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, const size_t *lens,
+                                         int level, void *d_out, size_t cap, size_t *out_offs, size_t *out_lens)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    if (!ctx) return BZX_E_PARAM;
+    if (!level_ok(level)) {
+        ctx->err = "bzx_compress_batch_device: level must be 1..9";
+        return BZX_E_PARAM;
+    }
+    if (count == 0) return BZX_OK;
+    int rc = batch_args(ctx, "bzx_compress_batch_device", count, d_raws, lens, d_out, out_offs, out_lens, true);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    try {
+        rc = batch_run(ctx, count, d_raws, lens, level, d_out, cap, out_offs, out_lens);
+    } catch (const std::bad_alloc &) {             // (nothing may unwind across the C ABI)
+        ctx->err = "out of host memory";
+        rc = BZX_E_NOMEM;
+    }
+    if (rc) (void)hipStreamSynchronize(ctx->stream);     // nothing of a failed call is left in flight
+    return rc;
+}
+
+static int batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws, const size_t *lens, int level,
+                        uint8_t *out, size_t cap, size_t *out_offs, size_t *out_lens);
+
+// Host buffers: the inputs are staged to the device (each on a 16-byte boundary of one allocation), the streams come
+// back in one copy.  Both device buffers live for the call only.
+extern "C" int bzx_compress_batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws, const size_t *lens,
+                                         int level, uint8_t *out, size_t cap, size_t *out_offs, size_t *out_lens)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    if (!ctx) return BZX_E_PARAM;
+    if (!level_ok(level)) {
+        ctx->err = "bzx_compress_batch_buffer: level must be 1..9";
+        return BZX_E_PARAM;
+    }
+    if (count == 0) return BZX_OK;
+    int rc = batch_args(ctx, "bzx_compress_batch_buffer", count, (const void *const *)raws, lens, out, out_offs, out_lens,
+                        false);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    try {
+        return batch_buffer(ctx, count, raws, lens, level, out, cap, out_offs, out_lens);
+    } catch (const std::bad_alloc &) {             // (nothing may unwind across the C ABI)
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->err = "out of host memory";
+        return BZX_E_NOMEM;
+    }
+}
+
+static int batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws, const size_t *lens, int level,
+                        uint8_t *out, size_t cap, size_t *out_offs, size_t *out_lens)
+{
+    int rc = BZX_OK;
+    std::vector<size_t> at(count);
+    size_t staged = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        at[i] = staged;
+        staged += (lens[i] + 15) & ~(size_t)15;
+    }
+    std::vector<const void *> d_raws(count, nullptr);
+    const size_t bound = bzx_compress_batch_bound(count, lens);
+    const size_t dcap = (cap < bound ? cap : bound) & ~(size_t)3;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    if (hipMalloc((void **)&d_in, staged ? staged : 16) != hipSuccess) {
+        ctx->err = "hipMalloc(batch inputs) failed";
+        return BZX_E_NOMEM;
+    }
+    if (hipMalloc((void **)&d_out, dcap ? dcap : 4) != hipSuccess) {
+        (void)hipFree(d_in);
+        ctx->err = "hipMalloc(batch output) failed";
+        return BZX_E_NOMEM;
+    }
+    for (uint32_t i = 0; !rc && i < count; i++) {
+        if (!lens[i]) continue;
+        d_raws[i] = d_in + at[i];
+        if (hipMemcpyAsync(d_in + at[i], raws[i], lens[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+            ctx->err = "hipMemcpyAsync(batch input) failed";
+            rc = BZX_E_HIP;
+        }
+    }
+    if (!rc) rc = batch_run(ctx, count, d_raws.data(), lens, level, d_out, dcap, out_offs, out_lens);
+    if (!rc) {
+        const size_t end = out_offs[count - 1] + round_up4(out_lens[count - 1]);
+        if (hipMemcpyAsync(out, d_out, end, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+            ctx->err = "hipMemcpyAsync(batch output) failed";
+            rc = BZX_E_HIP;
+        }
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return rc;
 }

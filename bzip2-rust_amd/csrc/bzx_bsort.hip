@@ -24,7 +24,7 @@
 // runs its prefix-doubling rounds on whatever they leave -- it also detects periodic blocks.  Blocks the split kernel cannot handle (more split levels than BS_MAX_BIG
 // tracks) are sorted from scratch by the general sorter (B.redo_list).
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include "bzx_host.h"
 #include "bzx_wg.h"
 #include "bzx_pack.h"
 

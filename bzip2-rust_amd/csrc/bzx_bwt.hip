@@ -27,7 +27,7 @@
 // HBM-bound integer work: records stream coalesced as 8-byte words; see DESIGN.md section 6 for the
 // measured traffic per phase.
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include "bzx_host.h"
 #include "bzx_wg.h"
 #include "bzx_pack.h"
 
@@ -1027,8 +1027,8 @@ __device__ __forceinline__ void bwt_body(const BzxBatch &B)
         __syncthreads();
         const uint32_t j_ = s_bcast[0];
         __syncthreads();
-        if (j_ >= (B.redo == 2 ? B.counters[BZX_CTR_RESUME] : B.redo ? B.counters[BZX_CTR_REDO] : B.nblk)) break;
-        const uint32_t b = B.redo == 2 ? B.resume_list[j_] : B.redo ? B.redo_list[j_] : B.blk_first + j_ * B.blk_step;
+        if (j_ >= B.counters[B.redo == 2 ? BZX_CTR_RESUME : BZX_CTR_REDO]) break;
+        const uint32_t b = B.redo == 2 ? B.resume_list[j_] : B.redo_list[j_];
         if (B.redo == 2 && !(B.blk[b].status & BZX_ST_RESUME)) continue;      // finished by the bucket sorter's rank rounds
                                                                                // (or by this kernel's early launch)
         if (B.redo == 2 && tid == 0) atomicAdd(&B.counters[BZX_CTR_RESUME_LEFT], 1u);

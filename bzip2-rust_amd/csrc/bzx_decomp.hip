@@ -20,7 +20,9 @@
 // Integer/byte work, latency-bound (a serial bit stream and a serial pointer chase per block); all blocks of a
 // stream are in flight at once.
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include <algorithm>
+#include <new>
+#include "bzx_host.h"
 #include "bzx_wg.h"
 
 #define DC_MAGIC_BLOCK 0x314159265359ull
@@ -457,24 +459,272 @@ __global__ __launch_bounds__(64) void bzx_dc_expand_kernel(BzxBatch B, const uin
     }
 }
 
-void bzx_launch_dc_scan(const uint8_t *z, uint64_t nbytes, uint64_t *found, uint32_t *n_found, uint32_t cap, uint32_t grid,
-                        hipStream_t stream)
+static void bzx_launch_dc_scan(const uint8_t *z, uint64_t nbytes, uint64_t *found, uint32_t *n_found, uint32_t cap,
+                               uint32_t grid, hipStream_t stream)
 {
     hipLaunchKernelGGL(bzx_dc_scan_kernel, dim3(grid), dim3(256), 0, stream, z, nbytes, found, n_found, cap);
 }
-void bzx_launch_dc_decode(const BzxBatch &B, const uint8_t *z, uint64_t nbytes, const uint64_t *starts, uint32_t max_n,
-                          hipStream_t stream)
+static void bzx_launch_dc_decode(const BzxBatch &B, const uint8_t *z, uint64_t nbytes, const uint64_t *starts,
+                                 uint32_t max_n, hipStream_t stream)
 {
     hipLaunchKernelGGL(bzx_dc_decode_kernel, dim3(B.nblk), dim3(64), 0, stream, B, z, nbytes, starts, max_n);
 }
-void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream)
+static void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream)
 {
     hipLaunchKernelGGL(bzx_dc_scatter_kernel, dim3(32, B.nblk), dim3(256), 0, stream, B);
     hipLaunchKernelGGL(bzx_dc_pack_kernel, dim3(32, B.nblk), dim3(256), 0, stream, B);
     hipLaunchKernelGGL(bzx_dc_walk_kernel, dim3((B.nblk + 63) / 64), dim3(64), 0, stream, B, img_slabs);
 }
-void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const uint64_t *off, uint8_t *out, uint64_t cap,
-                          hipStream_t stream)
+static void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const uint64_t *off, uint8_t *out,
+                                 uint64_t cap, hipStream_t stream)
 {
     hipLaunchKernelGGL(bzx_dc_expand_kernel, dim3((DC_CK_STRIDE + 63) / 64, B.nblk), dim3(64), 0, stream, B, img_slabs, off, out, cap);
+}
+
+// ---- host side (include/bzx.h: bzx_decompress_*) ------------------------------------------------------------------
+#define DC_MAX_FOUND 262144u
+
+// One bzip2 stream at the start of d_bz2[0..len); *consumed = bytes up to and including its footer.
+static int decompress_one(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len, size_t *consumed)
+{
+    *consumed = 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    *out_len = 0;
+    const uint8_t *z = (const uint8_t *)d_bz2;
+    uint8_t head[4] = {0, 0, 0, 0};
+    if (len < 14) {
+        ctx->err = "shorter than the smallest bzip2 stream";
+        return BZX_E_DATA;
+    }
+    HIP_TRY(ctx, hipMemcpy(head, z, 4, hipMemcpyDeviceToHost));
+    if (head[0] != 'B' || head[1] != 'Z' || head[2] != 'h' || head[3] < '1' || head[3] > '9') {
+        ctx->err = "no BZh1..BZh9 header";
+        return BZX_E_DATA;
+    }
+    const uint32_t max_n = 100000u * (uint32_t)(head[3] - '0');
+    // ---- scan for block / end-of-stream magics at every bit offset
+    void *scratch = nullptr;
+    int rc = bzx_ctx_split_scratch(ctx, (size_t)DC_MAX_FOUND * 8 * 3 + 4096, &scratch);
+    if (rc) return rc;
+    uint64_t *d_found = (uint64_t *)scratch;
+    uint64_t *d_starts = d_found + DC_MAX_FOUND;
+    uint64_t *d_off = d_starts + DC_MAX_FOUND;
+    uint32_t *d_nfound = (uint32_t *)(d_off + DC_MAX_FOUND);
+    HIP_TRY(ctx, hipMemsetAsync(d_nfound, 0, 64, ctx->stream));
+    bzx_launch_dc_scan(z, len, d_found, d_nfound, DC_MAX_FOUND, (uint32_t)ctx->n_cu * 8, ctx->stream);
+    uint32_t nfound = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&nfound, d_nfound, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (nfound > DC_MAX_FOUND) {
+        ctx->err = "too many block-magic candidates";
+        return BZX_E_DATA;
+    }
+    std::vector<uint64_t> found, starts;
+    try {
+        found.resize(nfound);
+        if (nfound) HIP_TRY(ctx, hipMemcpy(found.data(), d_found, (size_t)nfound * 8, hipMemcpyDeviceToHost));
+        std::sort(found.begin(), found.end());
+        for (uint64_t f : found)
+            if (!(f & 1u)) starts.push_back(f >> 1);
+    } catch (const std::bad_alloc &) {
+        return BZX_E_NOMEM;
+    }
+    auto is_eos = [&](uint64_t bit) { return std::binary_search(found.begin(), found.end(), (bit << 1) | 1u); };
+    // ---- decode every candidate; keep the chain that starts at bit 32 (a chance match of the magic inside compressed
+    // data does not continue the chain: drop it and decode again without it)
+    uint64_t end_bit = 32;
+    uint32_t nblk = 0;
+    for (int attempt = 0;; attempt++) {
+        nblk = (uint32_t)starts.size();
+        end_bit = 32;
+        if (nblk == 0) break;
+        if ((rc = ensure_blocks(ctx, nblk))) return rc;
+        BzxBatch &B = ctx->B;
+        B.nblk = nblk;
+        B.blk_first = 0;
+        B.blk_step = 1;
+        HIP_TRY(ctx, hipMemcpyAsync(d_starts, starts.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, ctx->stream));
+        bzx_launch_dc_decode(B, z, len, d_starts, max_n, ctx->stream);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, (size_t)nblk * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        std::vector<uint64_t> chain;
+        bool clean = true;
+        uint32_t i = 0;
+        while (i < nblk) {
+            if (starts[i] != end_bit) {             // not where the previous block ended: a chance match
+                clean = false;
+                i++;
+                continue;
+            }
+            if (ctx->h_blk[i].status & BZX_ST_DC_RANDOMISED) {
+                ctx->err = "randomised block (written by bzip2 0.9.0 or older): not supported";
+                return BZX_E_DATA;
+            }
+            if (ctx->h_blk[i].status) {
+                ctx->err = "damaged block in the bzip2 stream";
+                return BZX_E_DATA;
+            }
+            chain.push_back(starts[i]);
+            end_bit = ctx->h_blk[i].bits;
+            i++;
+        }
+        if (clean) break;
+        if (attempt >= 3) {
+            ctx->err = "cannot follow the chain of blocks";
+            return BZX_E_DATA;
+        }
+        starts.swap(chain);
+    }
+    if (!is_eos(end_bit)) {
+        ctx->err = "blocks do not end at an end-of-stream marker";
+        return BZX_E_DATA;
+    }
+    uint8_t foot[16] = {0};
+    {
+        const size_t fb = (size_t)((end_bit + 48) >> 3);
+        const size_t nfb = len - fb < 5 ? len - fb : 5;
+        if ((end_bit + 80 + 7) / 8 > len) {
+            ctx->err = "truncated after the end-of-stream marker";
+            return BZX_E_DATA;
+        }
+        HIP_TRY(ctx, hipMemcpy(foot, z + fb, nfb, hipMemcpyDeviceToHost));
+    }
+    uint64_t fv = 0;
+    for (int i = 0; i < 5; i++) fv = (fv << 8) | foot[i];
+    const uint32_t stream_crc = (uint32_t)((fv << ((end_bit + 48) & 7u)) >> 8);
+    uint64_t total = 0;
+    uint32_t comb = 0;
+    if (nblk) {
+        BzxBatch &B = ctx->B;
+        // ---- inverse BWT, expanded sizes, offsets
+        bzx_launch_dc_ibwt(B, ctx->d_in, ctx->stream);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, (size_t)nblk * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        std::vector<uint64_t> off;
+        try {
+            off.resize((size_t)nblk + 1);
+        } catch (const std::bad_alloc &) {
+            return BZX_E_NOMEM;
+        }
+        for (uint32_t b = 0; b < nblk; b++) {
+            if (ctx->h_blk[b].status) {
+                ctx->err = "damaged block in the bzip2 stream (inverse BWT)";
+                return BZX_E_DATA;
+            }
+            off[b] = total;
+            total += ctx->h_blk[b].pack_word;
+            comb = ((comb << 1) | (comb >> 31)) ^ ctx->h_blk[b].crc;       // stored CRCs (crc.rs:25-27)
+        }
+        off[nblk] = total;
+        *out_len = (size_t)total;
+        if (total > cap) {
+            ctx->err = "output buffer too small for the decompressed data";
+            return BZX_E_OUTBUF;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)nblk + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        bzx_launch_dc_expand(B, ctx->d_in, d_off, (uint8_t *)d_out, total, ctx->stream);
+        // ---- block CRCs of the output (the compressor's CRC kernel), against the stored ones
+        std::vector<uint32_t> stored(nblk);
+        for (uint32_t b = 0; b < nblk; b++) stored[b] = ctx->h_blk[b].crc;
+        HIP_TRY(ctx, hipMemcpyAsync(d_nfound, &nblk, 4, hipMemcpyHostToDevice, ctx->stream));
+        bzx_launch_block_crcs(ctx, (const uint8_t *)d_out, d_off, d_nfound, B.blk, nblk);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, (size_t)nblk * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipGetLastError());
+        for (uint32_t b = 0; b < nblk; b++) {
+            if (ctx->h_blk[b].crc != stored[b]) {
+                ctx->err = "block CRC mismatch in block " + std::to_string(b);
+                return BZX_E_DATA;
+            }
+        }
+    }
+    if (comb != stream_crc) {
+        ctx->err = "combined CRC mismatch";
+        return BZX_E_DATA;
+    }
+    *out_len = (size_t)total;
+    *consumed = (size_t)((end_bit + 80 + 7) / 8);
+    ctx->stats.nblk = nblk;
+    ctx->stats_batch = false;
+    ctx->stats.raw_bytes = total;
+    return BZX_OK;
+}
+
+// true when another stream header (BZh1..BZh9) starts at d_bz2[at]
+static bool stream_follows(bzx_ctx *ctx, const void *d_bz2, size_t len, size_t at)
+{
+    uint8_t h[4] = {0, 0, 0, 0};
+    if (at + 14 > len) return false;
+    if (hipMemcpy(h, (const uint8_t *)d_bz2 + at, 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return h[0] == 'B' && h[1] == 'Z' && h[2] == 'h' && h[3] >= '1' && h[3] <= '9';
+}
+
+// Device buffer -> device buffer: ONE stream (the reference's decompress() also stops at the first footer,
+// decompress.rs:81-95).  Bytes behind the footer that are not another stream are ignored, as bzip2 does ("trailing
+// garbage"); a concatenated .bz2 (pbzip2 output, cat a.bz2 b.bz2) is refused here rather than decoded in part --
+// bzx_decompress_buffer decodes every stream of it.
+extern "C" int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    if (!ctx || !d_bz2 || !out_len || (cap && !d_out) || ((uintptr_t)d_out & 15u)) return BZX_E_PARAM;
+    size_t used = 0;
+    const int rc = decompress_one(ctx, d_bz2, len, d_out, cap, out_len, &used);
+    if (rc == BZX_OK && stream_follows(ctx, d_bz2, len, used)) {
+        ctx->err = "another bzip2 stream follows the first (concatenated .bz2): bzx_decompress_buffer decodes all of them";
+        return BZX_E_DATA;
+    }
+    return rc;
+}
+
+extern "C" int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    if (!ctx || !bz2 || !out_len || (cap && !out)) return BZX_E_PARAM;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void *d_z = nullptr, *d_o = nullptr;
+    if (hipMalloc(&d_z, len + 64) != hipSuccess) return BZX_E_NOMEM;
+    if (hipMalloc(&d_o, cap + 64) != hipSuccess) {
+        (void)hipFree(d_z);
+        return BZX_E_NOMEM;
+    }
+    int rc = hipMemcpyAsync(d_z, bz2, len, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? BZX_OK : BZX_E_HIP;
+    // every stream of a concatenated .bz2, one after the other (each stream starts on a byte boundary)
+    size_t at = 0, total = 0;
+    uint32_t nblk_all = 0;
+    *out_len = 0;
+    void *d_z2 = nullptr;                          // a later stream, moved to an aligned start (the kernels read words)
+    while (!rc) {
+        size_t n = 0, used = 0;
+        const void *src = d_z;
+        if (at) {
+            if (!d_z2 && hipMalloc(&d_z2, len + 64) != hipSuccess) {
+                rc = BZX_E_NOMEM;
+                break;
+            }
+            if (hipMemcpyAsync(d_z2, (const uint8_t *)d_z + at, len - at, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+                rc = BZX_E_HIP;
+                break;
+            }
+            src = d_z2;
+        }
+        rc = decompress_one(ctx, src, len - at, d_o, cap - total, &n, &used);
+        if (rc == BZX_E_OUTBUF) *out_len = total + n;          // (a lower bound when streams remain)
+        if (rc) break;
+        if (n && hipMemcpy(out + total, d_o, n, hipMemcpyDeviceToHost) != hipSuccess) rc = BZX_E_HIP;
+        total += n;
+        nblk_all += ctx->stats.nblk;
+        at += used;
+        *out_len = total;
+        if (!stream_follows(ctx, d_z, len, at)) break;
+    }
+    if (!rc) {
+        ctx->stats.nblk = nblk_all;
+        ctx->stats_batch = false;
+        ctx->stats.raw_bytes = total;
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_z);
+    if (d_z2) (void)hipFree(d_z2);
+    (void)hipFree(d_o);
+    return rc;
 }

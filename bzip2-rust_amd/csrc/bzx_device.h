@@ -36,7 +36,6 @@
 
 // counters[] slots (BzxBatch.counters, zeroed per batch)
 #define BZX_CTR_PERIODIC 5         // blocks flagged periodic
-#define BZX_CTR_BK_ITEMS 8         // (unused since the work list became eight lists)
 #define BZX_CTR_BK_LIST0 40        // [40..47] bucket work items in each of the eight lists (BzxBatch.bk_list)
 #ifndef BZX_DEEP_LEVELS
 #define BZX_DEEP_LEVELS 2          // launches of the deep-split kernel (levels of oversized bins dealt over the whole chip), <= 8:
@@ -105,8 +104,7 @@ struct BzxBatch {
     uint32_t nblk;          // blocks this launch works on: logical j in [0,nblk) -> block blk_first + j*blk_step
     uint32_t blk_first;     // round-robin sharding over GPUs: first = rank, step = world size
     uint32_t blk_step;
-    uint32_t ctr_bwt;       // index of the block-fetch counter this BWT launch uses (0, or 6 for a concurrent second launch)
-    uint32_t ctr_mtf;       // same for the MTF kernel (1 or 7)
+    uint32_t ctr_bwt;       // index of the block-fetch counter this BWT launch uses (BZX_CTR_REDO_FETCH or BZX_CTR_RESUME_FETCH)
     uint32_t packed;        // emit at blk.pack_word (packed per-rank buffer) instead of blk.out_bit (final stream)
     uint32_t *counters;     // [BZX_N_COUNTERS] atomic work counters, one per stage kernel (zeroed per batch); [5] = #periodic
     uint32_t *plist;        // [nblk] indices of the blocks flagged periodic by the BWT kernel

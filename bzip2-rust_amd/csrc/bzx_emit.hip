@@ -15,7 +15,7 @@
 // out_bit is its final position in the stream (scan over block sizes, bzx_layout_kernel), no
 // host-side or second-pass bit shifting is needed: the .bz2 is complete in HBM.
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include "bzx_host.h"
 #include "bzx_wg.h"
 
 #define EMIT_NT 512

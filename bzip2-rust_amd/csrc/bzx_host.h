@@ -1,0 +1,159 @@
+// bzx_host.h -- host side shared by the library's .hip files (internal, not installed): the context, the stage runner
+// and every function that one file defines and another calls.  Declared here once, so a prototype cannot drift from
+// its definition.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <condition_variable>
+#include <mutex>
+#include <string>
+#include <vector>
+#include "../../include/bzx.h"
+#include "bzx_device.h"
+
+struct BlockReq {
+    const uint8_t *blk;
+    size_t n;
+    uint32_t crc;
+    uint8_t *out;
+    size_t cap;
+    size_t out_len = 0;
+    uint8_t pad = 0;
+    int rc = 0;
+    bool done = false;
+};
+
+struct bzx_ctx {
+    int device = 0;
+    int n_cu = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    // Calls on one context from several host threads are serialised (api_mu); bzx_compress_block calls that arrive
+    // together (the reference's rayon workers, compress.rs:125-132) are collected into one device batch (bq_*).
+    std::recursive_mutex api_mu;
+    std::mutex bq_mu;
+    std::condition_variable bq_cv;
+    std::vector<struct BlockReq *> bq_pending;
+    bool bq_leader = false;
+    // second stream: the general sorter's early launch on the blocks the bucket sorter's split refused
+    hipStream_t aux = nullptr;
+    hipEvent_t ev_join = nullptr;
+    hipEvent_t ev_b3 = nullptr, ev_b4 = nullptr;     // ... around the rank rounds
+    hipEvent_t ev_b1 = nullptr, ev_b2 = nullptr;     // bucket sorter: after the split kernel, after the sort kernel
+    bool bsort_used = false;
+    uint32_t *h_counters = nullptr;                   // pinned copy of d_counters after a run
+    std::string err;
+
+    uint32_t cap_blocks = 0;   // block descriptor capacity (global block numbers)
+    uint32_t cap_slabs = 0;    // per-block slab capacity (owned blocks)
+    std::vector<void *> descs; // everything hipMalloc'ed for cap_blocks
+    uint32_t n_slots = 0;      // per-workgroup scratch slots
+    BzxBatch B;                // device pointers (by value into kernels)
+    std::vector<void *> slabs; // everything hipMalloc'ed for cap_blocks
+    std::vector<void *> slot_allocs;
+    uint8_t *d_in = nullptr;   // block slab buffer owned by the context
+    uint32_t *d_outbuf = nullptr;   // per-block output slabs (per-block entry points)
+    uint32_t *d_counters = nullptr;
+    uint64_t *d_scalars = nullptr;   // [0] total bits, [1] out bytes
+    unsigned long long *d_dbg = nullptr;   // [64] phase timers, only when bzx_dbg_phase_timers(ctx, 1)
+    BzxBlock *h_blk = nullptr;       // pinned mirror
+    uint64_t *h_scalars = nullptr;   // pinned
+    hipEvent_t ev[8];
+    bzx_stats stats;
+
+    // sharded run state (bzx_shard_prepare -> bzx_shard_emit)
+    uint32_t shard_total = 0, shard_rank = 0, shard_world = 1;
+    int shard_level = 0;
+    uint64_t shard_packed_max = 0;   // bytes of the longest packed buffer of any rank (known after bzx_shard_emit_packed)
+    size_t shard_len = 0;
+
+    struct bzx_cstream *cs = nullptr;        // chunked stream compressor kept for bzx_compress_buffer
+    std::vector<uint8_t> split_carry;        // bzx_split_rle1_chunk: raw bytes of the withheld block
+
+    // device split scratch (bzx_rle1.hip)
+    void *split_ws = nullptr;
+    size_t split_ws_bytes = 0;
+
+    // batched compression (bzx_compress_batch_*): tables and scratch of the batched splitter and layout
+    void *batch_ws = nullptr;
+    size_t batch_ws_bytes = 0;
+    hipEvent_t ev_bt[3] = {nullptr, nullptr, nullptr};   // round: before its split part, before emit, after framing
+    bool stats_batch = false;        // the stats describe a batch call: no per-block figures (bzx_get_block_info)
+};
+
+#define HIP_TRY(ctx, expr)                                                                       \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess) {                                                                  \
+            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                      \
+            return BZX_E_HIP;                                                                    \
+        }                                                                                        \
+    } while (0)
+
+// The lock of an entry point: serialises the calls on one context (none without a context: the argument check that
+// follows refuses the call).
+static inline std::unique_lock<std::recursive_mutex> ctx_lock(bzx_ctx *ctx)
+{
+    return ctx ? std::unique_lock<std::recursive_mutex>(ctx->api_mu) : std::unique_lock<std::recursive_mutex>();
+}
+
+static inline int level_ok(int level) { return level >= 1 && level <= 9; }
+
+// Number of workgroups for a one-workgroup-per-block kernel over nblk blocks.
+static inline uint32_t grid_for(const bzx_ctx *ctx, uint32_t nblk, uint32_t per_cu)
+{
+    uint32_t g = (uint32_t)ctx->n_cu * per_cu;
+    return nblk < g ? nblk : g;
+}
+
+enum { STG_BWT = 1, STG_MTF = 2, STG_HUF = 4, STG_EMIT = 8, STG_ALL = 15 };
+
+// ---- bzx_api.hip: context, stage runner, split, statistics
+int ensure_blocks(bzx_ctx *ctx, uint32_t nblk, uint32_t nslab = 0);
+int run_stages(bzx_ctx *ctx, uint32_t nblk, int stages, int out_level = 0, void *d_stream_out = nullptr,
+               size_t stream_cap = 0, uint64_t *d_phase = nullptr);
+int split_on_device(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, int level, uint32_t *nblk_out,
+                    uint32_t own_first = 0, uint32_t own_step = 1, uint64_t *last_raw_start = nullptr,
+                    uint64_t *gathered_tiles = nullptr);
+int bzx_ctx_split_scratch(bzx_ctx *ctx, size_t bytes, void **p);
+void collect_stage_times(bzx_ctx *ctx);
+void fold_blocks(bzx_stats &st, const BzxBlock *blk, uint32_t first, uint32_t end, uint32_t step);
+
+// ---- launchers of the stage kernels
+void bzx_launch_bwt(const BzxBatch &B, uint32_t grid, hipStream_t stream);                                  // bzx_bwt.hip
+uint32_t bzx_bwt_max_blocks_per_cu();
+void bzx_launch_bsplit(const BzxBatch &B, uint32_t grid, uint32_t grid_deep, hipStream_t stream);           // bzx_bsort.hip
+void bzx_launch_bsort(const BzxBatch &B, uint32_t grid, hipStream_t stream);
+void bzx_launch_brank(const BzxBatch &B, uint32_t grid, hipStream_t stream);
+void bzx_launch_bgiant(const BzxBatch &B, uint32_t grid, hipStream_t stream);
+uint32_t bzx_bsort_blocks_per_cu();
+void bzx_launch_periodic(const BzxBatch &B, uint32_t grid, hipStream_t stream);                             // bzx_periodic.hip
+void bzx_launch_mtf(const BzxBatch &B, uint32_t grid, hipStream_t stream);                                  // bzx_mtf.hip
+void bzx_launch_huffman(const BzxBatch &B, uint32_t grid, hipStream_t stream);                              // bzx_huff.hip
+void bzx_launch_emit(const BzxBatch &B, uint32_t grid, hipStream_t stream);                                 // bzx_emit.hip
+void bzx_launch_layout(const BzxBatch &B, uint64_t first_bit, uint64_t stride_bits, uint64_t *d_total_bits,
+                       hipStream_t stream, uint64_t *d_phase = nullptr);
+void bzx_launch_stream_frame(const BzxBatch &B, int level, const uint64_t *d_total_bits, uint64_t *d_out_bytes,
+                             hipStream_t stream);
+void bzx_launch_bits_export(const BzxBatch &B, long long *bits, hipStream_t stream);
+void bzx_launch_bits_import(const BzxBatch &B, const long long *bits, hipStream_t stream);
+void bzx_launch_pack_layout(const BzxBatch &B, uint32_t first, uint32_t step, uint32_t nown, uint64_t *d_total,
+                            hipStream_t stream);
+void bzx_launch_pack_max(const BzxBatch &B, uint32_t world, uint64_t *d_out, hipStream_t stream);
+void bzx_launch_zero_edges(const BzxBatch &B, const uint64_t *d_total, hipStream_t stream);
+void bzx_launch_unpack(const BzxBatch &B, const uint32_t *packed, uint32_t first, uint32_t step, uint32_t nown,
+                       uint32_t grid, hipStream_t stream);
+
+// ---- bzx_rle1.hip: the block splitter
+int bzx_split_launch_boundaries(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, int level, uint32_t max_blocks,
+                                BzxSplitWs *ws_out);
+uint64_t bzx_split_tiles_per_rank(size_t len, uint32_t world);
+int bzx_split_shard_runs(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, uint32_t rank, uint32_t world, uint64_t *tiles);
+int bzx_split_shard_counts(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, uint32_t rank, uint32_t world, uint64_t *tiles);
+int bzx_split_shard_boundaries(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, int level, uint32_t max_blocks,
+                               uint32_t world, uint64_t *tiles, BzxSplitWs *ws_out);
+void bzx_split_launch_scatter(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, const BzxSplitWs &ws, uint32_t nblk,
+                              uint8_t *d_slabs, BzxBlock *d_blk, uint32_t own_first, uint32_t own_step);
+void bzx_launch_block_crcs(bzx_ctx *ctx, const uint8_t *d_raw, const uint64_t *d_bounds, uint32_t *d_nblk, BzxBlock *d_blk,
+                           uint32_t nblk);
+void bzx_split_scan(hipStream_t st, uint64_t *v, uint64_t n, int is_max, uint64_t *segtot);
+uint64_t bzx_split_scan_words(uint64_t n);

@@ -14,7 +14,7 @@
 // LDS reads; rfreq in LDS atomics.  Also produces every section size so the emitter and the
 // stream layout know all bit offsets.
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include "bzx_host.h"
 #include "bzx_wg.h"
 
 #define HUF_NT 512

@@ -14,7 +14,7 @@
 // parallel pass over the heads: a head emits its rank (+1) and the RUNA/RUNB digits of the zeros behind it, whose
 // number is the distance to the next head (sum-scan for offsets).
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include "bzx_host.h"
 #include "bzx_wg.h"
 
 #define MTF_NT 1024
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(MTF_NT) void bzx_mtf_kernel(BzxBatch B)
     unsigned long long t_last = 0;
 
     for (;;) {
-        if (tid == 0) m_bcast[0] = atomicAdd(&B.counters[B.ctr_mtf], 1u);
+        if (tid == 0) m_bcast[0] = atomicAdd(&B.counters[1], 1u);
         __syncthreads();
         const uint32_t j_ = m_bcast[0];
         __syncthreads();

@@ -18,7 +18,7 @@
 // Small ranges (< PER_COOP_MIN) and the pivot-choice sequence stay serial on lane 0.  Exactly periodic blocks are
 // vanishingly rare outside all-equal-byte inputs (config 5a: 6 blocks); an all-zero 900 KB block takes ~90 ms.
 #include <hip/hip_runtime.h>
-#include "bzx_device.h"
+#include "bzx_host.h"
 #include "bzx_wg.h"
 
 #define N_RADIX 2

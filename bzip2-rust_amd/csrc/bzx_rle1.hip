@@ -21,7 +21,7 @@
 //      combined with x^(8*len) mod P multiplications (GF(2) polynomial arithmetic).
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include "bzx_device.h"
+#include "bzx_host.h"
 #include "bzx_rle1.h"
 
 // ---- A: last run start per tile (bzx_tile_runstart in bzx_rle1.h)
@@ -291,10 +291,6 @@ __global__ __launch_bounds__(CRC_NT) void bzx_rl_crc_kernel(const uint8_t *__res
 
 
 // ---- host orchestration
-struct bzx_ctx;
-int bzx_ctx_split_scratch(bzx_ctx *ctx, size_t bytes, void **p);   // bzx_api.hip
-hipStream_t bzx_ctx_stream(bzx_ctx *ctx);
-int bzx_ctx_ncu(bzx_ctx *ctx);
 
 // Scratch of the splitter: the three tile arrays (in the context's scratch, or -- sharded analysis -- in the caller's
 // array `tiles` of 3 x tile_stride words, which the ranks all-gather), the block arrays and the scans' segment totals.
@@ -332,7 +328,7 @@ static int split_ws(bzx_ctx *ctx, size_t len, uint32_t max_blocks, uint64_t *til
 
 static uint32_t tile_grid(bzx_ctx *ctx, uint64_t ntiles)
 {
-    const uint64_t g = (uint64_t)bzx_ctx_ncu(ctx) * 8;
+    const uint64_t g = (uint64_t)ctx->n_cu * 8;
     return (uint32_t)(ntiles < g ? (ntiles ? ntiles : 1) : g);
 }
 
@@ -345,7 +341,7 @@ int bzx_split_launch_boundaries(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, 
     uint64_t *segtot = nullptr;
     int rc = split_ws(ctx, len, max_blocks, nullptr, 0, &ws, &segtot);
     if (rc) return rc;
-    hipStream_t st = bzx_ctx_stream(ctx);
+    hipStream_t st = ctx->stream;
     const uint32_t grid = tile_grid(ctx, ntiles);
     const uint32_t nmax = 100000u * (uint32_t)level - 19u;
     hipLaunchKernelGGL(bzx_rl_runstart_kernel, dim3(grid), dim3(RL_NT), 0, st, d_raw, (uint64_t)len, (uint64_t)0, ntiles, ws);
@@ -378,7 +374,7 @@ int bzx_split_shard_runs(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, uint32_
     int rc = split_ws(ctx, len, 2, tiles, per * world, &ws, &segtot);
     if (rc) return rc;
     if (hi > lo)
-        hipLaunchKernelGGL(bzx_rl_runstart_kernel, dim3(tile_grid(ctx, hi - lo)), dim3(RL_NT), 0, bzx_ctx_stream(ctx), d_raw,
+        hipLaunchKernelGGL(bzx_rl_runstart_kernel, dim3(tile_grid(ctx, hi - lo)), dim3(RL_NT), 0, ctx->stream, d_raw,
                            (uint64_t)len, lo, hi, ws);
     return 0;
 }
@@ -394,7 +390,7 @@ int bzx_split_shard_counts(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, uint3
     uint64_t *segtot = nullptr;
     int rc = split_ws(ctx, len, 2, tiles, per * world, &ws, &segtot);
     if (rc) return rc;
-    hipStream_t st = bzx_ctx_stream(ctx);
+    hipStream_t st = ctx->stream;
     launch_scan(st, ws.tile_rs, ntiles, 1, segtot);
     if (hi > lo)
         hipLaunchKernelGGL(bzx_rl_count_kernel, dim3(tile_grid(ctx, (hi - lo + RL_NT - 1) / RL_NT)), dim3(RL_NT), 0, st, d_raw,
@@ -411,7 +407,7 @@ int bzx_split_shard_boundaries(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, i
     uint64_t *segtot = nullptr;
     int rc = split_ws(ctx, len, max_blocks, tiles, per * world, &ws, &segtot);
     if (rc) return rc;
-    hipStream_t st = bzx_ctx_stream(ctx);
+    hipStream_t st = ctx->stream;
     const uint32_t nmax = 100000u * (uint32_t)level - 19u;
     launch_scan(st, ws.tile_off, ntiles, 0, segtot);
     launch_scan(st, ws.tile_np, ntiles, 0, segtot);
@@ -425,15 +421,13 @@ void bzx_split_launch_scatter(bzx_ctx *ctx, const uint8_t *d_raw, size_t len, co
                               uint8_t *d_slabs, BzxBlock *d_blk, uint32_t own_first, uint32_t own_step)
 {
     const uint64_t ntiles = (len + RL_TILE - 1) / RL_TILE;
-    hipStream_t st = bzx_ctx_stream(ctx);
-    const uint32_t grid = (uint32_t)(ntiles < (uint64_t)bzx_ctx_ncu(ctx) * 8 ? ntiles : (uint64_t)bzx_ctx_ncu(ctx) * 8);
+    hipStream_t st = ctx->stream;
+    const uint32_t grid = (uint32_t)(ntiles < (uint64_t)ctx->n_cu * 8 ? ntiles : (uint64_t)ctx->n_cu * 8);
     hipLaunchKernelGGL(bzx_rl_scatter_kernel, dim3(grid), dim3(RL_NT), 0, st, d_raw, (uint64_t)len, ntiles, ws, d_slabs, d_blk, own_first, own_step);
     const uint32_t mine = nblk > own_first ? (nblk - own_first + own_step - 1) / own_step : 0;
-    const uint32_t cgrid = mine < (uint32_t)bzx_ctx_ncu(ctx) ? (mine ? mine : 1) : (uint32_t)bzx_ctx_ncu(ctx);
+    const uint32_t cgrid = mine < (uint32_t)ctx->n_cu ? (mine ? mine : 1) : (uint32_t)ctx->n_cu;
     hipLaunchKernelGGL(bzx_rl_crc_kernel, dim3(cgrid), dim3(CRC_NT), 0, st, d_raw, ws, d_blk, own_first, own_step);
 }
-
-uint32_t *bzx_split_nblk_ptr(const BzxSplitWs &ws) { return ws.nblk; }
 
 // CRC-32/BZIP2 of nblk consecutive byte ranges [bounds[b], bounds[b+1]) of d_raw into blk[b].crc (the decompressor
 // checks its output with the compressor's kernel).  d_nblk: device word holding nblk.
@@ -444,8 +438,8 @@ void bzx_launch_block_crcs(bzx_ctx *ctx, const uint8_t *d_raw, const uint64_t *d
     memset(&ws, 0, sizeof(ws));
     ws.blk_raw = const_cast<uint64_t *>(d_bounds);
     ws.nblk = d_nblk;
-    const uint32_t cgrid = nblk < (uint32_t)bzx_ctx_ncu(ctx) ? (nblk ? nblk : 1) : (uint32_t)bzx_ctx_ncu(ctx);
-    hipLaunchKernelGGL(bzx_rl_crc_kernel, dim3(cgrid), dim3(CRC_NT), 0, bzx_ctx_stream(ctx), d_raw, ws, d_blk, 0u, 1u);
+    const uint32_t cgrid = nblk < (uint32_t)ctx->n_cu ? (nblk ? nblk : 1) : (uint32_t)ctx->n_cu;
+    hipLaunchKernelGGL(bzx_rl_crc_kernel, dim3(cgrid), dim3(CRC_NT), 0, ctx->stream, d_raw, ws, d_blk, 0u, 1u);
 }
 
 // The tile scans for the batched splitter (bzx_batch.hip): v[0..n) -> exclusive scan in place, v[n] = total; segtot:

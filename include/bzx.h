@@ -252,8 +252,8 @@ typedef struct {
     uint64_t mtf_symbols;       /* nMTF summed */
     uint64_t out_bits;          /* compressed bits incl. stream header/footer when present */
     float ms_split, ms_bwt, ms_mtf, ms_huffman, ms_emit, ms_total;   /* HIP-event times of the stage kernels */
-    uint32_t bwt_launches;      /* launches of the BWT kernel in the last run (2 when its partial last round
-                                   ran beside the MTF stage on a second stream); ms_bwt covers all of them */
+    uint32_t bwt_launches;      /* 1 per run of the stage kernels (kept for the ABI; a batch call sums its rounds);
+                                   ms_bwt covers every sort kernel of the run */
     uint32_t n_redo;            /* blocks the bucket sorter handed to the general sorter (deep repeats, periodic) */
     uint32_t n_buckets;         /* bucket work items of the bucket sorter */
     float ms_bwt_split, ms_bwt_sort, ms_bwt_general;   /* parts of ms_bwt: split kernel, bucket sort kernel, everything after it */
