@@ -195,6 +195,9 @@ extern "C" void bzx_ctx_destroy(bzx_ctx *ctx)
     if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
     if (ctx->split_ws) (void)hipFree(ctx->split_ws);
     if (ctx->batch_ws) (void)hipFree(ctx->batch_ws);
+    if (ctx->dbatch_ws) (void)hipFree(ctx->dbatch_ws);
+    for (int i = 0; i < 2; i++)
+        if (ctx->dbatch_pin[i]) (void)hipHostFree(ctx->dbatch_pin[i]);
     if (ctx->h_blk) (void)hipHostFree(ctx->h_blk);
     if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);

@@ -137,11 +137,13 @@ __device__ static void dc_make_tables(uint32_t t, uint32_t alpha)
     d_minlen[t] = minl;
 }
 
-// One wave per block.  starts[j] = bit offset of the block magic.  Outputs: L bytes (B.bwt slab), occ ranks (u32,
-// B.rec_a slab), byte counts (B.freq slab), descriptor: n, crc (stored), orig_ptr, bits = bit after the block's last
-// symbol, status (DC_ERR_* on malformed data).
+// One wave per block.  Block j starts (its magic) at bit starts[j] of z[0, nbytes), or -- src non-null, the batch --
+// at bit src[j].bit of src[j].z[0, src[j].nbytes).  Outputs: L bytes (B.bwt slab), occ ranks (u32, B.rec_a slab), byte
+// counts (B.freq slab), descriptor: n, crc (stored), orig_ptr, bits = bit after the block's last symbol, status
+// (DC_ERR_* on malformed data).
 __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uint8_t *__restrict__ z, uint64_t nbytes,
-                                                          const uint64_t *__restrict__ starts, uint32_t max_n)
+                                                          const uint64_t *__restrict__ starts,
+                                                          const BzxDcSrc *__restrict__ src, uint32_t max_n)
 {
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
     if (b >= B.nblk) return;
@@ -149,8 +151,16 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
     uint8_t *__restrict__ L = B.bwt + (size_t)b * BZX_BLK_STRIDE;
     uint32_t *__restrict__ OCC = reinterpret_cast<uint32_t *>(B.rec_a + (size_t)b * BZX_MAX_N);
     uint8_t *__restrict__ SEL = B.selector + (size_t)b * BZX_SEL_STRIDE;
+    uint64_t start = 0;
+    if (src) {
+        z = src[b].z;
+        nbytes = src[b].nbytes;
+        start = src[b].bit;
+    } else {
+        start = starts[b];
+    }
     DcBits br;
-    br.init(z, nbytes, starts[b] + 48);
+    br.init(z, nbytes, start + 48);
     uint32_t err = 0;
     const uint32_t crc = br.get(32);
     const uint32_t randomised = br.get(1);
@@ -330,7 +340,7 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
         D.n = n;
         D.crc = crc;
         D.orig_ptr = orig;
-        D.out_bit = starts[b];
+        D.out_bit = start;
         D.bits = br.pos;
         D.status = err;
         D.n_in_use = n_in_use;
@@ -426,13 +436,16 @@ __global__ __launch_bounds__(64) void bzx_dc_walk_kernel(BzxBatch B, uint8_t *__
     B.blk[b].pack_word = out;                  // expanded length
 }
 
-// grid (segments, blocks): expands one 4096-byte segment of the RLE1 image from its checkpoint to out + off[b].
+// grid (segments, blocks): expands one 4096-byte segment of the RLE1 image from its checkpoint to dst[b].p (at most
+// dst[b].cap bytes from there; a null dst[b].p: the block is not written).
 __global__ __launch_bounds__(64) void bzx_dc_expand_kernel(BzxBatch B, const uint8_t *__restrict__ img_slabs,
-                                                          const uint64_t *__restrict__ off, uint8_t *__restrict__ out,
-                                                          uint64_t cap)
+                                                          const BzxDcDst *__restrict__ dst)
 {
     const uint32_t b = blockIdx.y;
     if (B.blk[b].status) return;
+    uint8_t *__restrict__ out = dst[b].p;
+    const uint64_t cap = dst[b].cap;
+    if (!out) return;
     const uint32_t n = B.blk[b].n;
     const uint32_t seg = blockIdx.x * 64 + threadIdx.x;
     const uint32_t k0 = seg << DC_CK_SHIFT;
@@ -440,7 +453,7 @@ __global__ __launch_bounds__(64) void bzx_dc_expand_kernel(BzxBatch B, const uin
     const uint32_t k1 = k0 + (1u << DC_CK_SHIFT) < n ? k0 + (1u << DC_CK_SHIFT) : n;
     const uint8_t *__restrict__ IMG = img_slabs + (size_t)b * BZX_BLK_STRIDE;
     const DcCheck c = reinterpret_cast<const DcCheck *>(B.gbits + (size_t)b * BZX_SEL_STRIDE)[seg];
-    uint64_t o = off[b] + c.out_pos;
+    uint64_t o = c.out_pos;
     uint32_t last = c.state & 0x1FFu, cnt = c.state >> 9;
     for (uint32_t k = k0; k < k1; k++) {
         const uint32_t ch = IMG[k];
@@ -464,21 +477,20 @@ static void bzx_launch_dc_scan(const uint8_t *z, uint64_t nbytes, uint64_t *foun
 {
     hipLaunchKernelGGL(bzx_dc_scan_kernel, dim3(grid), dim3(256), 0, stream, z, nbytes, found, n_found, cap);
 }
-static void bzx_launch_dc_decode(const BzxBatch &B, const uint8_t *z, uint64_t nbytes, const uint64_t *starts,
-                                 uint32_t max_n, hipStream_t stream)
+void bzx_launch_dc_decode(const BzxBatch &B, const uint8_t *z, uint64_t nbytes, const uint64_t *starts,
+                          const BzxDcSrc *src, uint32_t max_n, hipStream_t stream)
 {
-    hipLaunchKernelGGL(bzx_dc_decode_kernel, dim3(B.nblk), dim3(64), 0, stream, B, z, nbytes, starts, max_n);
+    hipLaunchKernelGGL(bzx_dc_decode_kernel, dim3(B.nblk), dim3(64), 0, stream, B, z, nbytes, starts, src, max_n);
 }
-static void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream)
+void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream)
 {
     hipLaunchKernelGGL(bzx_dc_scatter_kernel, dim3(32, B.nblk), dim3(256), 0, stream, B);
     hipLaunchKernelGGL(bzx_dc_pack_kernel, dim3(32, B.nblk), dim3(256), 0, stream, B);
     hipLaunchKernelGGL(bzx_dc_walk_kernel, dim3((B.nblk + 63) / 64), dim3(64), 0, stream, B, img_slabs);
 }
-static void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const uint64_t *off, uint8_t *out,
-                                 uint64_t cap, hipStream_t stream)
+void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const BzxDcDst *dst, hipStream_t stream)
 {
-    hipLaunchKernelGGL(bzx_dc_expand_kernel, dim3((DC_CK_STRIDE + 63) / 64, B.nblk), dim3(64), 0, stream, B, img_slabs, off, out, cap);
+    hipLaunchKernelGGL(bzx_dc_expand_kernel, dim3((DC_CK_STRIDE + 63) / 64, B.nblk), dim3(64), 0, stream, B, img_slabs, dst);
 }
 
 // ---- host side (include/bzx.h: bzx_decompress_*) ------------------------------------------------------------------
@@ -504,12 +516,13 @@ static int decompress_one(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_o
     const uint32_t max_n = 100000u * (uint32_t)(head[3] - '0');
     // ---- scan for block / end-of-stream magics at every bit offset
     void *scratch = nullptr;
-    int rc = bzx_ctx_split_scratch(ctx, (size_t)DC_MAX_FOUND * 8 * 3 + 4096, &scratch);
+    int rc = bzx_ctx_split_scratch(ctx, (size_t)DC_MAX_FOUND * 8 * 5 + 4096, &scratch);
     if (rc) return rc;
     uint64_t *d_found = (uint64_t *)scratch;
     uint64_t *d_starts = d_found + DC_MAX_FOUND;
     uint64_t *d_off = d_starts + DC_MAX_FOUND;
-    uint32_t *d_nfound = (uint32_t *)(d_off + DC_MAX_FOUND);
+    BzxDcDst *d_dst = (BzxDcDst *)(d_off + DC_MAX_FOUND);
+    uint32_t *d_nfound = (uint32_t *)(d_dst + DC_MAX_FOUND);
     HIP_TRY(ctx, hipMemsetAsync(d_nfound, 0, 64, ctx->stream));
     bzx_launch_dc_scan(z, len, d_found, d_nfound, DC_MAX_FOUND, (uint32_t)ctx->n_cu * 8, ctx->stream);
     uint32_t nfound = 0;
@@ -544,7 +557,7 @@ static int decompress_one(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_o
         B.blk_first = 0;
         B.blk_step = 1;
         HIP_TRY(ctx, hipMemcpyAsync(d_starts, starts.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, ctx->stream));
-        bzx_launch_dc_decode(B, z, len, d_starts, max_n, ctx->stream);
+        bzx_launch_dc_decode(B, z, len, d_starts, nullptr, max_n, ctx->stream);
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, (size_t)nblk * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         std::vector<uint64_t> chain;
@@ -621,8 +634,11 @@ static int decompress_one(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_o
             ctx->err = "output buffer too small for the decompressed data";
             return BZX_E_OUTBUF;
         }
+        std::vector<BzxDcDst> dst(nblk);
+        for (uint32_t b = 0; b < nblk; b++) dst[b] = BzxDcDst{(uint8_t *)d_out + off[b], total - off[b]};
         HIP_TRY(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)nblk + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        bzx_launch_dc_expand(B, ctx->d_in, d_off, (uint8_t *)d_out, total, ctx->stream);
+        HIP_TRY(ctx, hipMemcpyAsync(d_dst, dst.data(), (size_t)nblk * sizeof(BzxDcDst), hipMemcpyHostToDevice, ctx->stream));
+        bzx_launch_dc_expand(B, ctx->d_in, d_dst, ctx->stream);
         // ---- block CRCs of the output (the compressor's CRC kernel), against the stored ones
         std::vector<uint32_t> stored(nblk);
         for (uint32_t b = 0; b < nblk; b++) stored[b] = ctx->h_blk[b].crc;

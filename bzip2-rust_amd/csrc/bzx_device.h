@@ -204,6 +204,17 @@ struct BzxBatchWs {
     uint32_t count;
 };
 
+// Batched decompression (bzx_dbatch.hip): where the decoder reads a block and where the expansion writes it.
+struct BzxDcSrc {
+    const uint8_t *z;       // the block's input (any alignment)
+    uint64_t nbytes;        // ... its length: nothing at or past z + nbytes is read
+    uint64_t bit;           // bit offset of the block magic in z
+};
+struct BzxDcDst {
+    uint8_t *p;             // first output byte of the block (null: the block is not expanded)
+    uint64_t cap;           // bytes that may be written from p on
+};
+
 // Slab of block b.  Block DESCRIPTORS (B.blk, plist, redo_list) are indexed by the global block number; the per-block
 // slabs (bwt, rank, mtfv, tables, packed block, records, RLE1 bytes) exist only for the blocks a launch owns
 // (round-robin sharding over GPUs: b = blk_first + j * blk_step owns slab j), so a rank of an 8-GPU job holds 1/8

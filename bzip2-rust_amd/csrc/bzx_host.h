@@ -78,6 +78,12 @@ struct bzx_ctx {
     size_t batch_ws_bytes = 0;
     hipEvent_t ev_bt[3] = {nullptr, nullptr, nullptr};   // round: before its split part, before emit, after framing
     bool stats_batch = false;        // the stats describe a batch call: no per-block figures (bzx_get_block_info)
+
+    // batched decompression (bzx_decompress_batch_*): device tables and pinned host mirrors, grown on demand
+    void *dbatch_ws = nullptr;
+    size_t dbatch_ws_bytes = 0;
+    void *dbatch_pin[2] = {nullptr, nullptr};   // [0] candidates and round tables, [1] the _buffer form's bounce buffer
+    size_t dbatch_pin_bytes[2] = {0, 0};
 };
 
 #define HIP_TRY(ctx, expr)                                                                       \
@@ -157,3 +163,9 @@ void bzx_launch_block_crcs(bzx_ctx *ctx, const uint8_t *d_raw, const uint64_t *d
                            uint32_t nblk);
 void bzx_split_scan(hipStream_t st, uint64_t *v, uint64_t n, int is_max, uint64_t *segtot);
 uint64_t bzx_split_scan_words(uint64_t n);
+
+// ---- bzx_decomp.hip: the decoder's kernels (one stream, and the batch of bzx_dbatch.hip)
+void bzx_launch_dc_decode(const BzxBatch &B, const uint8_t *z, uint64_t nbytes, const uint64_t *starts,
+                          const BzxDcSrc *src, uint32_t max_n, hipStream_t stream);
+void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream);
+void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const BzxDcDst *dst, hipStream_t stream);

@@ -243,6 +243,40 @@ void bzx_host_free(void *p);
 int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len);
 int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len);
 
+/*
+ * Batched decompression: count independent .bz2 inputs decoded in one call, the counterpart of
+ * bzx_compress_batch_*.  Input i is a .bz2 file: one stream or several concatenated.
+ * The rule: given enough room, output i and status[i] are what bzx_decompress_buffer returns for input i alone -- the
+ * same bytes and BZX_OK, or BZX_E_DATA -- with its edge rules: an input shorter than 14 bytes or without a BZh1..9
+ * header is refused; bytes after a stream that do not begin another stream are ignored; a "BZh<d>" after a stream
+ * that does not decode refuses the input; randomised blocks, blocks longer than 100000 * level, selectors outside
+ * 1..32767 are refused.  (One difference: there is no fixed limit on the block-magic candidates of an input.)
+ * Independence: an input's status and bytes do not depend on its neighbours, in the call or in memory; nothing
+ * outside [srcs[i], srcs[i] + src_lens[i]) is read.
+ * Pointers: d_srcs and d_outs are HOST arrays of count DEVICE pointers.  Inputs may have any alignment; outputs must
+ * be 16-byte aligned (as for bzx_decompress_device).  An output may be NULL where caps[i] == 0.
+ * Output too small (per input): if the decoded size of input i exceeds caps[i], status[i] = BZX_E_OUTBUF,
+ * out_lens[i] = the exact size needed, outs[i] is not written and the input's block CRCs are not checked.  Damage
+ * found before the size is known is BZX_E_DATA.  After BZX_OK out_lens[i] is the decoded length, after BZX_E_DATA 0.
+ * Returns BZX_OK when every status[i] is BZX_OK; otherwise status[k] for the lowest failing k, and bzx_last_error
+ * names input k and the reason.  Errors of the whole call -- BZX_E_PARAM (NULL arrays, a misaligned output, a NULL
+ * output with caps[i] > 0), BZX_E_NOMEM, BZX_E_HIP -- are returned as themselves and every status[i] is set to that
+ * code.  count == 0 returns BZX_OK.  After any error the context stays usable.
+ * Rounds: the inputs run in device rounds of whole inputs with at most R blocks each, R = the larger of the block
+ * slabs the context holds and the block count of the largest input (block-magic candidates, chance matches
+ * included).  A call costs one host synchronisation after the magic scan (a second one only if the candidate table
+ * overflows, which takes chance matches of the magic) and two per round; none per input or stream.
+ * _buffer stages the inputs on the device in groups of at most 256 MiB of compressed bytes (or one larger input),
+ * and each round's outputs packed in a device area bounded by the round's decoded bytes (per input, the smaller of
+ * caps[i] and 259/5 of its inverse-BWT output), not by the sum of caps; one copy per round brings them back.
+ * bzx_get_stats after a batch call: nblk (blocks decoded), raw_bytes (decoded bytes) and ms_total;
+ * bzx_get_block_info returns BZX_E_STATE.
+ */
+int bzx_decompress_batch_device(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, const size_t *src_lens,
+                                void *const *d_outs, const size_t *caps, size_t *out_lens, int *status);
+int bzx_decompress_batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *srcs, const size_t *src_lens,
+                                uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
+
 /* Per-call telemetry of the last bzx_compress_device/_buffer/_blocks/_batch_* call. */
 typedef struct {
     uint32_t nblk;

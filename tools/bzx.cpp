@@ -4,13 +4,15 @@
 // Compression streams the input through bzx_cstream_feed in chunks (files larger than device memory are fine and the
 // output is written while the next chunk is compressed); decompression reads the whole .bz2.  Compressing two or more
 // named files (without -v), the regular files of at most 16 MiB are read and compressed together, one
-// bzx_compress_batch_buffer call per batch of up to 256 MiB, each into its own .bz2.
+// bzx_compress_batch_buffer call per batch of up to 256 MiB, each into its own .bz2; -d and -t do the same through
+// bzx_decompress_batch_buffer (a file it does not accept is decoded again on its own, for the one-file path's message).
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <new>
 #include <string>
 #include <vector>
 #include "../include/bzx.h"
@@ -118,10 +120,8 @@ static int do_zip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *
     return ret;
 }
 
-static int do_unzip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *name)
+static int unzip_data(const Opts &o, bzx_ctx *ctx, const std::vector<uint8_t> &z, FILE *out, const char *name)
 {
-    std::vector<uint8_t> z;
-    if (!read_all(in, z)) return fail(o, strerror(errno), name, nullptr, BZX_OK);
     size_t cap = z.size() * 6 + (1 << 20), n = 0;
     std::vector<uint8_t> raw;
     for (;;) {
@@ -137,6 +137,13 @@ static int do_unzip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char
     if (out && fwrite(raw.data(), 1, n, out) != n) return fail(o, strerror(errno), name, nullptr, BZX_OK);
     if (o.verbose) fprintf(stderr, "  %s: %s, %zu -> %zu bytes\n", name, o.mode == TEST ? "ok" : "done", z.size(), n);
     return 0;
+}
+
+static int do_unzip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *name)
+{
+    std::vector<uint8_t> z;
+    if (!read_all(in, z)) return fail(o, strerror(errno), name, nullptr, BZX_OK);
+    return unzip_data(o, ctx, z, out, name);
 }
 
 // The end of one file's work: output flushed and closed (or removed after a failure), input removed unless -k.
@@ -191,9 +198,55 @@ static const size_t BATCH_BYTES = (size_t)256 << 20;       // input bytes per ba
 static const size_t BATCH_FILES = 512;                     // files per batch call (their outputs stay open until it)
 static const uint32_t BATCH_SLABS = 320;                   // context slabs: a 256 MiB batch at -9 in one device round
 
+// -d / -t: the pending .bz2 files in one bzx_decompress_batch_buffer call.  A file whose status is not BZX_OK is
+// decoded again on its own (unzip_data), which prints the one-file path's message and retries after BZX_E_OUTBUF.
+static int flush_unzip_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &pend)
+{
+    const uint32_t n = (uint32_t)pend.size();
+    std::vector<const uint8_t *> srcs(n);
+    std::vector<uint8_t *> outs(n);
+    std::vector<size_t> lens(n), caps(n), olens(n, 0);
+    std::vector<int> status(n, BZX_E_NOMEM);
+    std::vector<std::vector<uint8_t>> raw(n);
+    int rc = BZX_OK;
+    try {
+        for (uint32_t i = 0; i < n; i++) {
+            srcs[i] = pend[i].data.data();
+            lens[i] = pend[i].data.size();
+            caps[i] = lens[i] * 6 + (1 << 20);          // as unzip_data
+            raw[i].resize(caps[i]);
+            outs[i] = raw[i].data();
+        }
+    } catch (const std::bad_alloc &) {
+        rc = BZX_E_NOMEM;
+    }
+    if (!rc) (void)bzx_decompress_batch_buffer(ctx, n, srcs.data(), lens.data(), outs.data(), caps.data(), olens.data(),
+                                               status.data());
+    int ret = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        Pending &p = pend[i];
+        int r = 0;
+        if (status[i] != BZX_OK) {
+            std::vector<uint8_t>().swap(raw[i]);
+            r = unzip_data(o, ctx, p.data, p.out, p.name.c_str());
+        } else if (p.out && fwrite(raw[i].data(), 1, olens[i], p.out) != olens[i]) {
+            r = fail(o, strerror(errno), p.name.c_str(), nullptr, BZX_OK);
+        }
+        std::vector<uint8_t>().swap(raw[i]);
+        ret |= finish_file(o, p.out, p.oname, p.name, r);
+    }
+    return ret;
+}
+
 static int flush_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &pend, size_t &pend_bytes)
 {
     if (pend.empty()) return 0;
+    if (o.mode != ZIP) {
+        const int ret = flush_unzip_batch(o, ctx, pend);
+        pend.clear();
+        pend_bytes = 0;
+        return ret;
+    }
     const uint32_t n = (uint32_t)pend.size();
     std::vector<const uint8_t *> raws(n);
     std::vector<size_t> lens(n), offs(n, 0), olens(n, 0);
@@ -262,8 +315,8 @@ int main(int argc, char **argv)
         }
     }
     if (o.files.empty()) o.files.push_back("-");
-    // two or more named files to compress, without -v: the small regular ones go through the batched entry point
-    const bool batching = o.mode == ZIP && o.files.size() >= 2 && !o.verbose;
+    // two or more named files, without -v: the small regular ones go through the batched entry points
+    const bool batching = o.files.size() >= 2 && !o.verbose;
     bzx_ctx *ctx = nullptr;
     int rc = bzx_ctx_create(0, batching ? BATCH_SLABS : 0, &ctx);
     if (rc) {
