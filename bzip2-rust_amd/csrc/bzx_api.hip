@@ -455,6 +455,7 @@ extern "C" int bzx_stage_bwt(bzx_ctx *ctx, const uint8_t *blk, size_t n, uint8_t
                              uint32_t *status)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !bwt_out || !orig_ptr || check_blk_args(blk, n)) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = ensure_blocks(ctx, 1);
@@ -506,6 +507,7 @@ extern "C" int bzx_stage_mtf(bzx_ctx *ctx, const uint8_t *bwt, size_t n, uint16_
                              uint32_t freq_out[258], uint8_t in_use_out[256])
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !mtfv_out || !n_mtf || !freq_out || !in_use_out || check_blk_args(bwt, n)) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = ensure_blocks(ctx, 1);
@@ -535,6 +537,7 @@ extern "C" int bzx_stage_huffman(bzx_ctx *ctx, const uint16_t *mtfv, uint32_t n_
                                  uint8_t len_out[6][258], uint32_t code_out[6][258])
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !mtfv || !freq || !n_groups || !n_selectors || !selectors || !len_out || !code_out) return BZX_E_PARAM;
     if (n_mtf == 0 || n_mtf > BZX_MAX_BLOCK + 1 || alpha_size < 3 || alpha_size > BZX_MAX_ALPHA) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -591,6 +594,7 @@ extern "C" int bzx_compress_blocks(bzx_ctx *ctx, uint32_t nblk, const uint8_t *c
                                    uint8_t *pads)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !blks || !ns || !crcs || !outs || !caps || !out_lens || !pads) return BZX_E_PARAM;
     if (nblk == 0) return BZX_OK;
     for (uint32_t b = 0; b < nblk; b++)
@@ -761,6 +765,7 @@ extern "C" int bzx_compress_device(bzx_ctx *ctx, const void *d_raw, size_t len, 
                                    size_t *out_len)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !d_out || !out_len || !level_ok(level) || (len && !d_raw)) return BZX_E_PARAM;
     if (((uintptr_t)d_raw & 15u) || ((uintptr_t)d_out & 3u) || cap < 16) {
         ctx->err = "bzx_compress_device: d_raw must be 16-byte aligned, d_out 4-byte aligned, cap >= 16";
@@ -834,6 +839,7 @@ extern "C" int bzx_split_rle1(bzx_ctx *ctx, const uint8_t *raw, size_t len, int 
                               uint32_t nblk_cap, uint32_t *ns, uint32_t *crcs, uint32_t *nblk_out)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !blocks_out || !ns || !crcs || !nblk_out || !level_ok(level) || (len && !raw)) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *nblk_out = 0;
@@ -847,6 +853,7 @@ static int shard_prepare(bzx_ctx *ctx, const void *d_raw, size_t len, int level,
                          uint32_t *nblk_total, long long *d_bits, size_t bits_cap, uint64_t *gathered_tiles)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !nblk_total || !d_bits || !level_ok(level) || world == 0 || rank >= world || (len && !d_raw)) return BZX_E_PARAM;
     if ((uintptr_t)d_raw & 15u) {
         ctx->err = "bzx_shard_prepare: d_raw must be 16-byte aligned";
@@ -905,6 +912,7 @@ extern "C" size_t bzx_shard_scan_entries(size_t len, uint32_t world)
 extern "C" int bzx_shard_scan_runs(bzx_ctx *ctx, const void *d_raw, size_t len, uint32_t rank, uint32_t world, long long *d_tiles)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     int rc = shard_scan_args(ctx, d_raw, len, rank, world, d_tiles);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -917,6 +925,7 @@ extern "C" int bzx_shard_scan_runs(bzx_ctx *ctx, const void *d_raw, size_t len, 
 extern "C" int bzx_shard_scan_counts(bzx_ctx *ctx, const void *d_raw, size_t len, uint32_t rank, uint32_t world, long long *d_tiles)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     int rc = shard_scan_args(ctx, d_raw, len, rank, world, d_tiles);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -949,6 +958,7 @@ static uint32_t shard_count(uint32_t nblk, uint32_t rank, uint32_t world)
 extern "C" int bzx_shard_packed_max(bzx_ctx *ctx, size_t *max_len)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !max_len) return BZX_E_PARAM;
     if (ctx->shard_level == 0 || ctx->shard_packed_max == 0) return BZX_E_STATE;
     *max_len = (size_t)ctx->shard_packed_max;
@@ -959,6 +969,7 @@ extern "C" int bzx_shard_emit_packed(bzx_ctx *ctx, const long long *d_bits_all, 
                                      size_t *packed_len, size_t *stream_len)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !d_bits_all || !d_packed || !packed_len || !stream_len || ((uintptr_t)d_packed & 3u)) return BZX_E_PARAM;
     if (ctx->shard_level == 0) return BZX_E_STATE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1020,6 +1031,7 @@ extern "C" int bzx_shard_emit_packed(bzx_ctx *ctx, const long long *d_bits_all, 
 extern "C" int bzx_shard_assemble_begin(bzx_ctx *ctx, void *d_out, size_t cap, size_t *stream_len)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !d_out || ((uintptr_t)d_out & 3u)) return BZX_E_PARAM;
     if (ctx->shard_level == 0) return BZX_E_STATE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1043,6 +1055,7 @@ extern "C" int bzx_shard_assemble_begin(bzx_ctx *ctx, void *d_out, size_t cap, s
 extern "C" int bzx_shard_assemble_rank(bzx_ctx *ctx, const void *d_packed_r, uint32_t r, void *d_out)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !d_packed_r || !d_out || ((uintptr_t)d_packed_r & 3u) || r >= ctx->shard_world) return BZX_E_PARAM;
     if (ctx->shard_level == 0) return BZX_E_STATE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1065,6 +1078,7 @@ extern "C" int bzx_split_rle1_chunk(bzx_ctx *ctx, const uint8_t *raw, size_t len
                                     uint32_t nblk_cap, uint32_t *ns, uint32_t *crcs, uint32_t *nblk_out)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !blocks_out || !ns || !crcs || !nblk_out || !level_ok(level) || (len && !raw)) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *nblk_out = 0;

@@ -575,6 +575,7 @@ extern "C" int bzx_compress_batch_device(bzx_ctx *ctx, uint32_t count, const voi
                                          int level, void *d_out, size_t cap, size_t *out_offs, size_t *out_lens)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx) return BZX_E_PARAM;
     if (!level_ok(level)) {
         ctx->err = "bzx_compress_batch_device: level must be 1..9";
@@ -603,6 +604,7 @@ extern "C" int bzx_compress_batch_buffer(bzx_ctx *ctx, uint32_t count, const uin
                                          int level, uint8_t *out, size_t cap, size_t *out_offs, size_t *out_lens)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx) return BZX_E_PARAM;
     if (!level_ok(level)) {
         ctx->err = "bzx_compress_batch_buffer: level must be 1..9";

@@ -73,6 +73,7 @@ extern "C" int bzx_cstream_begin(bzx_ctx *ctx, int level, size_t max_chunk, bzx_
     if (!ctx || !out || !level_ok(level)) return BZX_E_PARAM;
     *out = nullptr;
     std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (max_chunk == 0) max_chunk = (size_t)256 << 20;
     max_chunk = (max_chunk + 15) & ~(size_t)15;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -207,6 +208,7 @@ extern "C" int bzx_cstream_feed(bzx_cstream *s, const uint8_t *raw, size_t len, 
     if (!s || !s->ctx || !out || !produced || (len && !raw) || len > s->max_chunk || cap < 16) return BZX_E_PARAM;
     bzx_ctx *ctx = s->ctx;
     std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (s->finished) return BZX_E_STATE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (s->k == 0) {
@@ -320,6 +322,7 @@ extern "C" int bzx_compress_buffer(bzx_ctx *ctx, const uint8_t *raw, size_t len,
                                    size_t *out_len)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !out || !out_len || !level_ok(level) || (len && !raw) || cap < 16) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // chunk: 16 MiB doubling up to 128 MiB, then one block per compute unit (256 x 900,000 B on MI355X): the kernels that

@@ -603,6 +603,7 @@ extern "C" int bzx_decompress_batch_device(bzx_ctx *ctx, uint32_t count, const v
                                            void *const *d_outs, const size_t *caps, size_t *out_lens, int *status)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx) return BZX_E_PARAM;
     if (count == 0) return BZX_OK;
     const char *fn = "bzx_decompress_batch_device";
@@ -637,6 +638,7 @@ extern "C" int bzx_decompress_batch_buffer(bzx_ctx *ctx, uint32_t count, const u
                                            uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx) return BZX_E_PARAM;
     if (count == 0) return BZX_OK;
     const char *fn = "bzx_decompress_batch_buffer";

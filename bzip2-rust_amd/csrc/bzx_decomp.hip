@@ -682,6 +682,7 @@ static bool stream_follows(bzx_ctx *ctx, const void *d_bz2, size_t len, size_t a
 extern "C" int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !d_bz2 || !out_len || (cap && !d_out) || ((uintptr_t)d_out & 15u)) return BZX_E_PARAM;
     size_t used = 0;
     const int rc = decompress_one(ctx, d_bz2, len, d_out, cap, out_len, &used);
@@ -695,6 +696,7 @@ extern "C" int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len
 extern "C" int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len)
 {
     auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !bz2 || !out_len || (cap && !out)) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     void *d_z = nullptr, *d_o = nullptr;

@@ -1,0 +1,791 @@
+// bzx_dstream.hip -- streaming decompression on gfx950 (include/bzx.h: bzx_dstream_*): the .bz2 arrives in pieces, the
+// decoded bytes leave in pieces, device memory is fixed at bzx_dstream_begin.  The counterpart of bzx_cstream.hip.
+//
+// The kernels that decode a block (bzx_decomp.hip: decode, inverse BWT, expand) take per-block sources and
+// destinations; this file adds the state between calls, the windowing and the device-side pieces that let a window be
+// processed without the whole stream in view.
+//   window                the undecoded tail of the window before (the carry) + the bytes accepted since, contiguous in
+//                         one of two device input buffers: the accepted bytes go to the buffer that is not being
+//                         decoded, behind a gap of DS_CARRY_MAX bytes that the carry is copied into when the buffers
+//                         change roles.  Positions are bits from the start of the whole input, so the chain position
+//                         survives the change of window.
+//   scan, per window      every bit offset of [chain position, end) is tested for the block / end-of-stream magic; no
+//                         stream header is expected at the start (a window usually starts inside a stream).  The
+//                         candidates come back to the host once, are sorted there and go back to the device.  A full
+//                         table halves the scanned range and scans again (the rest is scanned when the chain gets
+//                         there): no limit on candidates per stream.                          [1 synchronisation]
+//   round, <= R blocks    decode the next R block candidates from the chain position on (bzx_dc_decode_kernel through
+//                         BzxDcSrc), then bzx_ds_chain_kernel: one wave walks the sorted candidates from the carried
+//                         chain bit, marks chance matches of the magic with the skip status, tells a block that runs
+//                         off the end of the window (withheld while more input may come; damage at `final` or when
+//                         DS_BLOCK_BOUND bytes did not end it) from a damaged one, recognises end-of-stream, checks the
+//                         stored combined CRC at its bit phase against the folded stored block CRCs, and follows a
+//                         "BZh<level>" at the next byte boundary into the next stream.  Inverse BWT unchanged.
+//   pass, <= 48 MiB       bzx_ds_layout_kernel: a wave-level scan of the expanded sizes gives the next chain blocks of
+//                         the round their places in a staging area and cuts after the last block that fits (a block
+//                         expands to at most 46.62 MB: every pass places at least one); blocks that did not fit stay
+//                         decoded in their slabs for the next pass.  Expand (bzx_dc_expand_kernel through BzxDcDst),
+//                         block CRCs (bzx_crc_range), bzx_ds_verdict_kernel compares them with the stored ones and
+//                         leaves ONE fixed-size record for the host.                          [1 synchronisation]
+//                         The first pass of a round is enqueued behind its decode/chain/inverse BWT without a
+//                         synchronisation in between: a round whose output fits one staging area costs one.
+//   overlap               three HIP streams: accepted bytes travel to the device beside the kernels of the window
+//                         before; the verified bytes of a pass travel to page-locked memory beside the kernels of the
+//                         next pass (two staging areas); the host copies from there into the caller's buffer.
+// Only verified bytes leave the device: the copy-back of a pass is sized by the record's verified byte count.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <algorithm>
+#include <new>
+#include "bzx_host.h"
+#include "bzx_rle1.h"
+#include "bzx_wg.h"
+
+#define DS_MAGIC_BLOCK 0x314159265359ull
+#define DS_MAGIC_EOS 0x177245385090ull
+#define DS_SKIP 0x800u                       // BzxBlock.status: off the chain or behind its stop (later kernels skip it)
+#define DS_BLOCK_BOUND 2400000ull            // bytes: no legal block image is longer (18,002 x 50 x 20 bits + tables)
+#define DS_CARRY_MAX (DS_BLOCK_BOUND + 4096) // gap in front of the accepted bytes: room for the longest carry
+#define DS_STAGE_BYTES ((size_t)48 << 20)    // output staging area: at least one expanded block (46.62 MB)
+#define DS_MIN_CHUNK ((size_t)16)               // (the carry has its own room: a small chunk only costs launches)
+#define DS_DEF_CHUNK ((size_t)128 << 20)
+
+enum { DS_STOP_GO = 0, DS_STOP_NOMAGIC, DS_STOP_WITHHELD, DS_STOP_END, DS_STOP_ERROR };
+enum { DS_ERR_RANDOMISED = 1, DS_ERR_DAMAGED, DS_ERR_TRUNC_EOS, DS_ERR_COMBINED };
+
+struct DsRec {                     // what the host reads of a pass (device -> page-locked host), fixed size
+    uint64_t chain_bit;            // chain: where it stands after the round (bit of the whole input)
+    uint64_t bytes;                // layout: bytes placed in the staging area by this pass
+    uint64_t good_bytes;           // verdict: ... of which lie before the first block whose CRC did not match
+    uint32_t nchain;               // chain: chain blocks of the round (slab numbers in d_chain, stream order)
+    uint32_t streams;              // chain: streams finished in the round
+    uint32_t comb;                 // chain: running combined CRC of the open stream
+    uint32_t level;                // chain: level of the open stream
+    uint32_t stop;                 // chain: DS_STOP_*
+    uint32_t err;                  // chain: DS_ERR_* behind the last chain block (stop == DS_STOP_ERROR)
+    uint32_t pass_j0;              // layout: first chain block of this pass
+    uint32_t placed;               // layout: chain blocks placed so far (this pass included)
+    uint32_t lay_err;              // layout: the next chain block failed its inverse BWT
+    uint32_t good;                 // verdict: blocks of this pass before the first CRC mismatch
+};
+
+// ---- scan: block / end-of-stream magics of window bytes [from, to), as bits of the whole input ---------------------
+__global__ __launch_bounds__(256) void bzx_ds_scan_kernel(const uint8_t *__restrict__ z, uint64_t wlen, uint64_t from,
+                                                          uint64_t to, uint64_t base_bit, uint64_t *__restrict__ found,
+                                                          uint32_t *__restrict__ n_found, uint32_t cap)
+{
+    const uint64_t nwords = (to - from + 3) / 4;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t byte0 = from + w * 4;
+        uint64_t hi = 0, lo = 0;                            // bytes byte0 .. byte0+15, big-endian
+#pragma unroll
+        for (int i = 0; i < 8; i++) hi = (hi << 8) | (byte0 + i < wlen ? z[byte0 + i] : 0u);
+#pragma unroll
+        for (int i = 8; i < 16; i++) lo = (lo << 8) | (byte0 + i < wlen ? z[byte0 + i] : 0u);
+#pragma unroll
+        for (uint32_t s = 0; s < 32; s++) {
+            const uint64_t x = s ? (hi << s) | (lo >> (64 - s)) : hi;
+            const uint64_t v = x >> 16;
+            const uint64_t bit = byte0 * 8 + s;
+            if ((v == DS_MAGIC_BLOCK || v == DS_MAGIC_EOS) && bit < to * 8 && bit + 48 <= wlen * 8) {
+                const uint32_t k = atomicAdd(n_found, 1u);
+                if (k < cap) found[k] = ((base_bit + bit) << 1) | (v == DS_MAGIC_EOS ? 1u : 0u);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t ds_byte(const uint8_t *__restrict__ z, uint64_t wlen, uint64_t i)
+{
+    return i < wlen ? z[i] : 0u;
+}
+
+// ---- chain and framing of a round: one wave ----------------------------------------------------------------------
+// cand[c0, c1): the round's candidates, sorted ((bit of the whole input) << 1 | end-of-stream); block candidate number
+// k of them was decoded into slab k (B.blk[k]: status, n, stored CRC, bits = window bit behind its last symbol).
+// Walks the chain from chain_bit; 64 candidates are loaded side by side, the walk over them is shuffles only.
+__global__ __launch_bounds__(64) void bzx_ds_chain_kernel(BzxBatch B, const uint8_t *__restrict__ z, uint64_t wlen,
+                                                         uint64_t base_bit, uint32_t final,
+                                                         const uint64_t *__restrict__ cand, uint32_t c0, uint32_t c1,
+                                                         uint64_t chain_bit, uint32_t comb, uint32_t level,
+                                                         uint32_t *__restrict__ chain, DsRec *__restrict__ rec)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint64_t wbits = wlen * 8;
+    uint64_t at_bit = chain_bit;
+    uint32_t nch = 0, streams = 0, stop = DS_STOP_GO, err = 0, nblk_before = 0;
+    for (uint32_t base = c0; base < c1; base += 64) {
+        const uint32_t k = base + lane;
+        const bool valid = k < c1;
+        const uint64_t pos = valid ? cand[k] : ~0ull;
+        const bool isblk = valid && !(pos & 1u);
+        const unsigned long long blks = __ballot(isblk);
+        const uint32_t slab = nblk_before + (uint32_t)__popcll(blks & ((1ull << lane) - 1ull));
+        uint32_t st = 0, n = 0, crc = 0;
+        uint64_t endw = 0;
+        if (isblk) {
+            const BzxBlock &d = B.blk[slab];
+            st = d.status;
+            n = d.n;
+            crc = d.crc;
+            endw = d.bits;
+        }
+        bool mine_on_chain = false;
+        const uint32_t cnt = c1 - base < 64u ? c1 - base : 64u;
+        for (uint32_t i = 0; i < cnt && stop == DS_STOP_GO; i++) {        // (everything below is wave-uniform)
+            const uint64_t p = __shfl(pos, (int)i);
+            const uint64_t bit = p >> 1;
+            if (bit < at_bit) continue;                                   // a chance match inside a chain block
+            if (bit > at_bit) {
+                stop = DS_STOP_NOMAGIC;
+                break;
+            }
+            const uint64_t rel = bit - base_bit;
+            if (!(p & 1u)) {
+                const uint32_t st_i = __shfl(st, (int)i), n_i = __shfl(n, (int)i), crc_i = __shfl(crc, (int)i);
+                const uint32_t slab_i = __shfl(slab, (int)i);
+                const uint64_t end_i = __shfl(endw, (int)i);
+                // the reader went past the window's end (it reads zeros there), or stopped on an error within reach of it
+                const bool ran_off = end_i > wbits || (st_i && end_i + 64 > wbits);
+                if (ran_off && !final && wbits - rel < DS_BLOCK_BOUND * 8) {
+                    stop = DS_STOP_WITHHELD;
+                    break;
+                }
+                if (st_i & BZX_ST_DC_RANDOMISED) {
+                    stop = DS_STOP_ERROR;
+                    err = DS_ERR_RANDOMISED;
+                    break;
+                }
+                if (st_i || ran_off || n_i > 100000u * level) {
+                    stop = DS_STOP_ERROR;
+                    err = DS_ERR_DAMAGED;
+                    break;
+                }
+                if (lane == i) mine_on_chain = true;
+                if (lane == 0) chain[nch] = slab_i;
+                nch++;
+                comb = ((comb << 1) | (comb >> 31)) ^ crc_i;              // stored CRCs (crc.rs:25-27)
+                at_bit = base_bit + end_i;
+            } else {
+                const uint64_t after = (rel + 80 + 7) / 8;                // first byte behind the footer
+                if (!final && after + 14 > wlen) {                        // is it a stream header?  not known yet
+                    stop = DS_STOP_WITHHELD;
+                    break;
+                }
+                if (rel + 80 > wbits) {
+                    stop = DS_STOP_ERROR;
+                    err = DS_ERR_TRUNC_EOS;
+                    break;
+                }
+                const uint64_t fb = (rel + 48) >> 3;
+                uint64_t fv = 0;
+                for (uint32_t q = 0; q < 5; q++) fv = (fv << 8) | ds_byte(z, wlen, fb + q);
+                const uint32_t stored = (uint32_t)((fv << ((rel + 48) & 7u)) >> 8);
+                if (stored != comb) {
+                    stop = DS_STOP_ERROR;
+                    err = DS_ERR_COMBINED;
+                    break;
+                }
+                streams++;
+                comb = 0;
+                const uint32_t lv = ds_byte(z, wlen, after + 3);
+                if (after + 14 <= wlen && ds_byte(z, wlen, after) == 'B' && ds_byte(z, wlen, after + 1) == 'Z' &&
+                    ds_byte(z, wlen, after + 2) == 'h' && lv >= '1' && lv <= '9') {
+                    level = lv - '0';
+                    at_bit = base_bit + after * 8 + 32;
+                } else {
+                    at_bit = base_bit + after * 8;
+                    stop = DS_STOP_END;
+                }
+            }
+        }
+        if (isblk && !mine_on_chain) B.blk[slab].status = st | DS_SKIP;
+        nblk_before += (uint32_t)__popcll(blks);
+    }
+    if (lane == 0) {
+        DsRec r;
+        r.chain_bit = at_bit;
+        r.bytes = 0;
+        r.good_bytes = 0;
+        r.nchain = nch;
+        r.streams = streams;
+        r.comb = comb;
+        r.level = level;
+        r.stop = stop;
+        r.err = err;
+        r.pass_j0 = 0;
+        r.placed = 0;
+        r.lay_err = 0;
+        r.good = 0;
+        *rec = r;
+    }
+}
+
+// ---- layout of a pass: one wave ------------------------------------------------------------------------------------
+// Chain blocks rec->placed .. of the round get their places in the staging area, in stream order, until one does not
+// fit or failed its inverse BWT; every other block of the round gets no place (the expansion skips it).
+__global__ __launch_bounds__(64) void bzx_ds_layout_kernel(BzxBatch B, const uint32_t *__restrict__ chain,
+                                                          uint8_t *stage, uint64_t stage_cap,
+                                                          BzxDcDst *__restrict__ dst, DsRec *__restrict__ rec)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t nch = rec->nchain, j0 = rec->placed;
+    for (uint32_t b = lane; b < B.nblk; b += 64) dst[b] = BzxDcDst{nullptr, 0};
+    __syncthreads();                                   // the places below are written after every "no place"
+    uint64_t off = 0;
+    uint32_t placed = j0, lay_err = 0;
+    bool stop = false;
+    for (uint32_t base = j0; base < nch && !stop; base += 64) {
+        const uint32_t j = base + lane;
+        const bool valid = j < nch;
+        const uint32_t b = valid ? chain[j] : 0u;
+        const uint64_t size = valid ? B.blk[b].pack_word : 0ull;
+        const uint32_t bad = (valid && B.blk[b].status) ? 1u : 0u;
+        uint64_t x = size;                             // inclusive scan of the expanded sizes over the wave
+        for (uint32_t k = 1; k < 64; k <<= 1) {
+            const uint64_t y = __shfl_up(x, k);
+            if (lane >= k) x += y;
+        }
+        const bool fits = valid && !bad && off + x <= stage_cap;
+        const unsigned long long nf = __ballot(valid && !fits);
+        const uint32_t cnt = nch - base < 64u ? nch - base : 64u;
+        const uint32_t first = nf ? (uint32_t)__ffsll(nf) - 1u : 64u;
+        const uint32_t take = first < cnt ? first : cnt;
+        if (lane < take) dst[b] = BzxDcDst{stage + off + (x - size), size};
+        const uint64_t gx = __shfl(x, (int)(take ? take - 1u : 0u));
+        const uint32_t bad_next = __shfl(bad, (int)(take < 64u ? take : 0u));
+        if (take) off += gx;
+        placed += take;
+        if (take < cnt) {
+            stop = true;
+            lay_err = bad_next;
+        }
+    }
+    if (lane == 0) {
+        rec->pass_j0 = j0;
+        rec->placed = placed;
+        rec->bytes = off;
+        rec->lay_err = lay_err;
+    }
+}
+
+// ---- CRC-32/BZIP2 of every block placed by the pass (bzx_crc_range, bzx_rle1.h) -----------------------------------
+__global__ __launch_bounds__(CRC_NT) void bzx_ds_crc_kernel(BzxBatch B, const BzxDcDst *__restrict__ dst,
+                                                            uint32_t *__restrict__ got)
+{
+    __shared__ BzxCrcLds lds;
+    const uint32_t my_weight = bzx_crc_setup(lds);
+    for (uint32_t b = blockIdx.x; b < B.nblk; b += gridDim.x) {
+        if (B.blk[b].status || !dst[b].p) continue;          // (uniform over the workgroup)
+        const uint32_t crc = bzx_crc_range(dst[b].p, 0, B.blk[b].pack_word, lds, my_weight);
+        if (threadIdx.x == 0) got[b] = crc;
+    }
+}
+
+// ---- verdict of a pass: computed against stored block CRCs, one wave -------------------------------------------------
+__global__ __launch_bounds__(64) void bzx_ds_verdict_kernel(BzxBatch B, const uint32_t *__restrict__ chain,
+                                                           const BzxDcDst *__restrict__ dst,
+                                                           const uint32_t *__restrict__ got, const uint8_t *stage,
+                                                           DsRec *__restrict__ rec)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t j0 = rec->pass_j0, j1 = rec->placed;
+    uint32_t good = j1 - j0;
+    uint64_t good_bytes = rec->bytes;
+    for (uint32_t base = j0; base < j1; base += 64) {
+        const uint32_t j = base + lane;
+        const bool valid = j < j1;
+        const uint32_t b = valid ? chain[j] : 0u;
+        const bool bad = valid && got[b] != B.blk[b].crc;
+        const unsigned long long m = __ballot(bad);
+        if (m) {
+            const uint32_t f = base + (uint32_t)__ffsll(m) - 1u;
+            good = f - j0;
+            good_bytes = (uint64_t)(dst[chain[f]].p - stage);
+            break;
+        }
+    }
+    if (lane == 0) {
+        rec->good = good;
+        rec->good_bytes = good_bytes;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+struct DsSlot {                    // an output staging area: the verified bytes of one pass
+    uint64_t bytes = 0, off = 0;   // bytes of the pass, bytes of them delivered
+    bool arrived = false;          // its copy-back has been awaited
+};
+
+struct bzx_dstream {
+    bzx_ctx *ctx = nullptr;
+    size_t max_chunk = 0, in_cap = 0;
+    uint32_t cap_cand = 0, R = 0;
+    uint8_t *d_in[2] = {nullptr, nullptr};
+    uint8_t *d_stage[2] = {nullptr, nullptr}, *h_stage[2] = {nullptr, nullptr};
+    uint64_t *d_cand = nullptr, *h_cand = nullptr;         // h_cand[cap_cand]: the window's candidates, sorted
+    uint32_t *d_ncand = nullptr, *h_ncand = nullptr;
+    BzxDcSrc *d_src = nullptr, *h_src = nullptr;
+    BzxDcDst *d_dst = nullptr;
+    uint32_t *d_chain = nullptr, *d_got = nullptr;
+    DsRec *d_rec = nullptr, *h_rec = nullptr;
+    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
+    hipEvent_t ev_h2d = nullptr, ev_carry = nullptr, ev_d2h[2] = {nullptr, nullptr};
+    // input
+    uint32_t acc = 0;                  // the input buffer that accepts bytes (the other one holds the window)
+    size_t acc_fill = 0;
+    uint8_t head[4] = {0, 0, 0, 0};    // first bytes of the input (stream header)
+    bool final_seen = false;
+    // window
+    bool have_win = false, wfinal = false, need_more = false, need_scan = false;
+    uint8_t *wptr = nullptr;
+    uint64_t wlen = 0, wbase = 0;      // its length, and the offset of its first byte in the whole input
+    uint64_t scan_to = 0;              // window bytes [.., scan_to) have been scanned
+    uint32_t ncand = 0, ci = 0;        // candidates, and the first one no round has taken
+    // chain
+    bool started = false;
+    uint64_t chain_bit = 0;
+    uint32_t comb = 0, level = 0;
+    // round
+    bool rd_active = false;            // the slabs hold chain blocks that have not been placed yet
+    uint32_t rd_nb = 0;
+    DsRec rd = {};                     // the chain part of the round's record
+    // output: passes in flight or being delivered, oldest first
+    DsSlot slot[2];
+    uint32_t q_head = 0, q_n = 0;
+    // verdict
+    bool finished = false, done = false;
+    int pend_rc = 0, err_rc = 0;       // an error waits behind the verified bytes still to be delivered / is raised
+    std::string pend_text, err_text;
+    bzx_dstream_info info = {};
+    float ms = 0.f;
+};
+
+extern "C" void bzx_dstream_end(bzx_dstream *s)
+{
+    if (!s) return;
+    bzx_ctx *ctx = s->ctx;
+    std::unique_lock<std::recursive_mutex> api_lock_;
+    if (ctx) {
+        api_lock_ = std::unique_lock<std::recursive_mutex>(ctx->api_mu);
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    if (s->s_h2d) (void)hipStreamSynchronize(s->s_h2d);
+    if (s->s_d2h) (void)hipStreamSynchronize(s->s_d2h);
+    for (int i = 0; i < 2; i++) {
+        if (s->d_in[i]) (void)hipFree(s->d_in[i]);
+        if (s->d_stage[i]) (void)hipFree(s->d_stage[i]);
+        if (s->h_stage[i]) (void)hipHostFree(s->h_stage[i]);
+        if (s->ev_d2h[i]) (void)hipEventDestroy(s->ev_d2h[i]);
+    }
+    if (s->d_cand) (void)hipFree(s->d_cand);
+    if (s->h_cand) (void)hipHostFree(s->h_cand);
+    if (s->d_ncand) (void)hipFree(s->d_ncand);
+    if (s->h_ncand) (void)hipHostFree(s->h_ncand);
+    if (s->d_src) (void)hipFree(s->d_src);
+    if (s->h_src) (void)hipHostFree(s->h_src);
+    if (s->d_dst) (void)hipFree(s->d_dst);
+    if (s->d_chain) (void)hipFree(s->d_chain);
+    if (s->d_got) (void)hipFree(s->d_got);
+    if (s->d_rec) (void)hipFree(s->d_rec);
+    if (s->h_rec) (void)hipHostFree(s->h_rec);
+    if (s->ev_h2d) (void)hipEventDestroy(s->ev_h2d);
+    if (s->ev_carry) (void)hipEventDestroy(s->ev_carry);
+    if (s->s_h2d) (void)hipStreamDestroy(s->s_h2d);
+    if (s->s_d2h) (void)hipStreamDestroy(s->s_d2h);
+    if (ctx && ctx->ds == s) ctx->ds = nullptr;
+    delete s;
+}
+
+extern "C" int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **out)
+{
+    if (!ctx || !out) return BZX_E_PARAM;
+    *out = nullptr;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
+    if (max_chunk == 0) max_chunk = DS_DEF_CHUNK;
+    if (max_chunk < DS_MIN_CHUNK) max_chunk = DS_MIN_CHUNK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_blocks(ctx, ctx->cap_slabs ? ctx->cap_slabs : 16);
+    if (rc) return rc;
+    bzx_dstream *s = new (std::nothrow) bzx_dstream();
+    if (!s) return BZX_E_NOMEM;
+    s->ctx = ctx;
+    s->max_chunk = max_chunk;
+    s->R = ctx->cap_slabs;
+    s->in_cap = DS_CARRY_MAX + max_chunk + 64;
+    s->cap_cand = (uint32_t)std::min<size_t>(s->in_cap / 256 + 1024, 0x7fffffffu);
+    const size_t R = s->R;
+    uint64_t dev = 0, pin = 0;
+    auto dmal = [&](void **p, size_t n) {
+        dev += n;
+        return hipMalloc(p, n) == hipSuccess;
+    };
+    auto hmal = [&](void **p, size_t n) {
+        pin += n;
+        return hipHostMalloc(p, n, 0) == hipSuccess;
+    };
+    bool ok = true;
+    for (int i = 0; i < 2 && ok; i++)
+        ok = dmal((void **)&s->d_in[i], s->in_cap) && dmal((void **)&s->d_stage[i], DS_STAGE_BYTES) &&
+             hmal((void **)&s->h_stage[i], DS_STAGE_BYTES) &&
+             hipEventCreateWithFlags(&s->ev_d2h[i], hipEventDisableTiming) == hipSuccess;
+    ok = ok && dmal((void **)&s->d_cand, (size_t)s->cap_cand * 8) && hmal((void **)&s->h_cand, (size_t)s->cap_cand * 8) &&
+         dmal((void **)&s->d_ncand, 64) && hmal((void **)&s->h_ncand, 64) && dmal((void **)&s->d_src, R * sizeof(BzxDcSrc)) &&
+         hmal((void **)&s->h_src, R * sizeof(BzxDcSrc)) && dmal((void **)&s->d_dst, R * sizeof(BzxDcDst)) &&
+         dmal((void **)&s->d_chain, R * 4) && dmal((void **)&s->d_got, R * 4) && dmal((void **)&s->d_rec, sizeof(DsRec)) &&
+         hmal((void **)&s->h_rec, sizeof(DsRec)) && hipEventCreateWithFlags(&s->ev_h2d, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&s->ev_carry, hipEventDisableTiming) == hipSuccess &&
+         hipStreamCreateWithFlags(&s->s_h2d, hipStreamNonBlocking) == hipSuccess &&
+         hipStreamCreateWithFlags(&s->s_d2h, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) {
+        s->ctx = nullptr;                      // (the lock is held here)
+        bzx_dstream_end(s);
+        ctx->err = "bzx_dstream_begin: device or pinned allocation failed";
+        return BZX_E_NOMEM;
+    }
+    s->info.slabs = s->R;
+    s->info.device_bytes = dev;
+    s->info.pinned_bytes = pin;
+    ctx->ds = s;
+    *out = s;
+    return BZX_OK;
+}
+
+extern "C" int bzx_dstream_get_info(const bzx_dstream *s, bzx_dstream_info *out)
+{
+    if (!s || !out || !s->ctx) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(s->ctx->api_mu);
+    *out = s->info;
+    out->slabs = s->ctx->cap_slabs;
+    return BZX_OK;
+}
+
+static void ds_fail(bzx_dstream *s, const std::string &why)
+{
+    s->pend_rc = BZX_E_DATA;
+    s->pend_text = why;
+    s->rd_active = false;
+}
+
+// Scans the window from the chain position on; a full table halves the range and scans again.
+static int ds_scan(bzx_dstream *s)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const uint64_t from = s->chain_bit / 8 - s->wbase;
+    uint64_t to = s->wlen;
+    for (;;) {
+        HIP_TRY(ctx, hipMemsetAsync(s->d_ncand, 0, 4, st));
+        if (to > from) {
+            const uint64_t nwords = (to - from + 3) / 4, g = (uint64_t)ctx->n_cu * 8;
+            const uint64_t need = (nwords + 255) / 256;
+            hipLaunchKernelGGL(bzx_ds_scan_kernel, dim3((uint32_t)(need < g ? need : g)), dim3(256), 0, st, s->wptr, s->wlen,
+                               from, to, s->wbase * 8, s->d_cand, s->d_ncand, s->cap_cand);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_ncand, s->d_ncand, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_cand, s->d_cand, (size_t)s->cap_cand * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));              // the scan's synchronisation
+        s->info.scans++;
+        if (*s->h_ncand <= s->cap_cand) break;
+        to = from + (to - from) / 2;                         // (cap_cand >= 1024 magics of 6 bytes: ends above 6 KiB)
+    }
+    s->ncand = *s->h_ncand;
+    std::sort(s->h_cand, s->h_cand + s->ncand);
+    if (s->ncand) HIP_TRY(ctx, hipMemcpyAsync(s->d_cand, s->h_cand, (size_t)s->ncand * 8, hipMemcpyHostToDevice, st));
+    s->scan_to = to;
+    s->ci = 0;
+    s->need_scan = false;
+    return BZX_OK;
+}
+
+// The chain found no magic where it stands (or the candidates are used up).
+static void ds_no_magic(bzx_dstream *s, bool used_up)
+{
+    const uint64_t rel = s->chain_bit - s->wbase * 8;
+    if (used_up && s->scan_to < s->wlen && rel >= s->scan_to * 8) {
+        s->need_scan = true;                                 // the rest of a window whose scan was cut short
+        return;
+    }
+    if (rel + 48 > s->wlen * 8 && !s->wfinal) s->need_more = true;
+    else ds_fail(s, "blocks do not end at an end-of-stream marker");
+}
+
+static void ds_round_complete(bzx_dstream *s)
+{
+    const DsRec &r = s->rd;
+    s->rd_active = false;
+    s->chain_bit = r.chain_bit;
+    s->comb = r.comb;
+    s->level = r.level;
+    s->info.nstreams += r.streams;
+    switch (r.stop) {
+    case DS_STOP_GO:
+        break;
+    case DS_STOP_NOMAGIC:
+        ds_no_magic(s, false);
+        break;
+    case DS_STOP_WITHHELD:
+        s->need_more = true;
+        break;
+    case DS_STOP_END:
+        s->finished = true;
+        break;
+    default:
+        ds_fail(s, r.err == DS_ERR_RANDOMISED  ? "randomised block (written by bzip2 0.9.0 or older): not supported"
+                   : r.err == DS_ERR_TRUNC_EOS ? "truncated after the end-of-stream marker"
+                   : r.err == DS_ERR_COMBINED  ? "combined CRC mismatch"
+                                               : "damaged block in the bzip2 stream");
+    }
+}
+
+// One pass: a new round (decode, chain, inverse BWT) when no decoded chain block waits in the slabs, then layout,
+// expansion, CRCs and verdict into the staging area `q`, the record, ONE synchronisation, and the copy-back of the
+// verified bytes on its own stream.
+static int ds_pass(bzx_dstream *s, uint32_t q)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    BzxBatch &B = ctx->B;
+    const bool fresh = !s->rd_active;
+    if (fresh) {
+        if (s->need_scan) {
+            const int rc = ds_scan(s);
+            if (rc) return rc;
+        }
+        while (s->ci < s->ncand && (s->h_cand[s->ci] >> 1) < s->chain_bit) s->ci++;
+        if (s->ci == s->ncand) {
+            ds_no_magic(s, true);
+            return BZX_OK;
+        }
+        const uint32_t c0 = s->ci;
+        uint32_t c1 = c0, nb = 0;
+        for (; c1 < s->ncand; c1++) {
+            if (s->h_cand[c1] & 1u) continue;
+            if (nb == s->R) break;
+            s->h_src[nb++] = BzxDcSrc{s->wptr, s->wlen, (s->h_cand[c1] >> 1) - s->wbase * 8};
+        }
+        s->ci = c1;
+        s->rd_nb = nb;
+        B.nblk = nb;
+        B.blk_first = 0;
+        B.blk_step = 1;
+        (void)hipEventRecord(ctx->ev[5], st);
+        if (nb) {
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_src, s->h_src, nb * sizeof(BzxDcSrc), hipMemcpyHostToDevice, st));
+            bzx_launch_dc_decode(B, nullptr, 0, nullptr, s->d_src, BZX_MAX_N, st);
+        }
+        hipLaunchKernelGGL(bzx_ds_chain_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8,
+                           s->wfinal ? 1u : 0u, s->d_cand, c0, c1, s->chain_bit, s->comb, s->level, s->d_chain, s->d_rec);
+        if (nb) bzx_launch_dc_ibwt(B, ctx->d_in, st);
+    } else {
+        B.nblk = s->rd_nb;
+        B.blk_first = 0;
+        B.blk_step = 1;
+        (void)hipEventRecord(ctx->ev[5], st);
+    }
+    const uint32_t nb = s->rd_nb;
+    if (nb) {
+        hipLaunchKernelGGL(bzx_ds_layout_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_stage[q],
+                           (uint64_t)DS_STAGE_BYTES, s->d_dst, s->d_rec);
+        bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
+        hipLaunchKernelGGL(bzx_ds_crc_kernel, dim3(nb < (uint32_t)ctx->n_cu ? nb : (uint32_t)ctx->n_cu), dim3(CRC_NT), 0, st, B,
+                           s->d_dst, s->d_got);
+        hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_dst, s->d_got, s->d_stage[q],
+                           s->d_rec);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_rec, s->d_rec, sizeof(DsRec), hipMemcpyDeviceToHost, st));
+    (void)hipEventRecord(ctx->ev[7], st);
+    HIP_TRY(ctx, hipStreamSynchronize(st));                  // the pass's one synchronisation
+    s->info.rounds++;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[7]) == hipSuccess) s->ms += ms;
+    const DsRec r = *s->h_rec;
+    if (fresh) {
+        s->rd = r;
+        s->rd_active = true;
+    }
+    if (r.good_bytes) {                                      // the verified bytes travel beside the next pass
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_stage[q], s->d_stage[q], r.good_bytes, hipMemcpyDeviceToHost, s->s_d2h));
+        HIP_TRY(ctx, hipEventRecord(s->ev_d2h[q], s->s_d2h));
+        s->slot[q].bytes = r.good_bytes;
+        s->slot[q].off = 0;
+        s->slot[q].arrived = false;
+        s->q_n++;
+    }
+    const uint32_t first_blk = s->info.nblk;
+    s->info.nblk += r.good;
+    if (r.good < r.placed - r.pass_j0) {
+        ds_fail(s, "block CRC mismatch in block " + std::to_string(first_blk + r.good));
+        return BZX_OK;
+    }
+    if (r.placed < r.nchain && r.lay_err) {
+        ds_fail(s, "damaged block in the bzip2 stream (inverse BWT)");
+        return BZX_OK;
+    }
+    if (r.placed >= r.nchain) ds_round_complete(s);
+    return BZX_OK;
+}
+
+// The accepted bytes become the window: the carry of the window before moves in front of them.
+static int ds_promote(bzx_dstream *s)
+{
+    bzx_ctx *ctx = s->ctx;
+    const uint32_t a = s->acc;
+    uint64_t carry_off = 0, carry_len = 0;
+    if (s->have_win) {
+        carry_off = s->chain_bit / 8 - s->wbase;
+        carry_len = s->wlen - carry_off;
+        if (carry_len > DS_CARRY_MAX) {                      // (cannot happen: a withheld block is shorter)
+            ctx->err = "bzx_dstream: the withheld tail exceeds its reserve";
+            return BZX_E_STATE;
+        }
+    }
+    uint8_t *np = s->d_in[a] + DS_CARRY_MAX - carry_len;
+    if (carry_len)
+        HIP_TRY(ctx, hipMemcpyAsync(np, s->wptr + carry_off, carry_len, hipMemcpyDeviceToDevice, ctx->stream));
+    // later accepted bytes land in the buffer the carry is read from: behind that copy
+    HIP_TRY(ctx, hipEventRecord(s->ev_carry, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(s->s_h2d, s->ev_carry, 0));
+    HIP_TRY(ctx, hipEventRecord(s->ev_h2d, s->s_h2d));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s->ev_h2d, 0));
+    s->wbase += carry_off;
+    s->wptr = np;
+    s->wlen = carry_len + s->acc_fill;
+    s->wfinal = s->final_seen;
+    s->have_win = true;
+    s->need_more = false;
+    s->need_scan = true;
+    s->acc = a ^ 1u;
+    s->acc_fill = 0;
+    s->info.windows++;
+    if (!s->started) {
+        s->started = true;
+        if (s->wlen < 14) {
+            ds_fail(s, "shorter than the smallest bzip2 stream");
+        } else if (s->head[0] != 'B' || s->head[1] != 'Z' || s->head[2] != 'h' || s->head[3] < '1' || s->head[3] > '9') {
+            ds_fail(s, "no BZh1..BZh9 header");
+        } else {
+            s->level = (uint32_t)(s->head[3] - '0');
+            s->chain_bit = 32;
+            s->comb = 0;
+        }
+    }
+    return BZX_OK;
+}
+
+static int ds_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, size_t *consumed, uint8_t *out, size_t cap,
+                   size_t *produced, int *done, bool *copied)
+{
+    bzx_ctx *ctx = s->ctx;
+    for (;;) {
+        // ---- accept input (after the end of the last stream, or behind an error: swallowed)
+        if (s->finished || s->pend_rc) {
+            s->info.in_bytes += len - *consumed;
+            *consumed = len;
+        } else if (*consumed < len && s->acc_fill < s->max_chunk) {
+            const size_t k = std::min(len - *consumed, s->max_chunk - s->acc_fill);
+            for (size_t i = 0; i < k && s->info.in_bytes + i < 4; i++) s->head[s->info.in_bytes + i] = bz2[*consumed + i];
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_in[s->acc] + DS_CARRY_MAX + s->acc_fill, bz2 + *consumed, k, hipMemcpyHostToDevice,
+                                        s->s_h2d));
+            *copied = true;
+            s->acc_fill += k;
+            s->info.in_bytes += k;
+            *consumed += k;
+        }
+        if (final && *consumed == len) s->final_seen = true;
+        // ---- everything verified has been delivered: the verdict
+        if (s->q_n == 0 && s->pend_rc) {
+            if (*produced) return BZX_OK;                    // (the bytes of this call count: the error is the next call's)
+            s->err_rc = s->pend_rc;
+            s->err_text = s->pend_text;
+            ctx->err = s->err_text;
+            return s->err_rc;
+        }
+        if (s->q_n == 0 && s->finished) {
+            s->done = true;
+            *done = 1;
+            memset(&ctx->stats, 0, sizeof(ctx->stats));
+            ctx->stats_batch = true;
+            ctx->stats.nblk = s->info.nblk;
+            ctx->stats.raw_bytes = s->info.out_bytes;
+            ctx->stats.ms_total = s->ms;
+            return BZX_OK;
+        }
+        const bool live = !s->pend_rc && !s->finished;
+        // ---- a pass, when there is something to decode or place and a staging area is free
+        if (live && (s->rd_active || (s->have_win && !s->need_more)) && s->q_n < 2) {
+            const uint32_t q = (s->q_head + s->q_n) & 1u;
+            const int rc = ds_pass(s, q);
+            if (rc) return rc;
+            continue;
+        }
+        // ---- the window is used up: the next one, when it is full or nothing follows
+        if (live && !s->rd_active && (!s->have_win || s->need_more) &&
+            (s->acc_fill == s->max_chunk || (s->final_seen && !(s->have_win && s->wfinal)))) {
+            const int rc = ds_promote(s);
+            if (rc) return rc;
+            continue;
+        }
+        // ---- deliver
+        if (s->q_n && *produced < cap) {
+            DsSlot &sl = s->slot[s->q_head];
+            if (!sl.arrived) {
+                HIP_TRY(ctx, hipEventSynchronize(s->ev_d2h[s->q_head]));
+                sl.arrived = true;
+            }
+            const size_t k = (size_t)std::min<uint64_t>(cap - *produced, sl.bytes - sl.off);
+            memcpy(out + *produced, s->h_stage[s->q_head] + sl.off, k);
+            sl.off += k;
+            *produced += k;
+            s->info.out_bytes += k;
+            if (sl.off == sl.bytes) {
+                s->q_head ^= 1u;
+                s->q_n--;
+            }
+            continue;
+        }
+        return BZX_OK;                                       // buffered, or the caller's room is used up
+    }
+}
+
+extern "C" int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, size_t *consumed, uint8_t *out,
+                                size_t cap, size_t *produced, int *done)
+{
+    if (!s || !s->ctx || !consumed || !produced || !done || (len && !bz2) || (cap && !out)) return BZX_E_PARAM;
+    bzx_ctx *ctx = s->ctx;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    *consumed = 0;
+    *produced = 0;
+    *done = 0;
+    if (s->err_rc) {
+        ctx->err = s->err_text;
+        return s->err_rc;
+    }
+    if (s->done) {
+        ctx->err = "bzx_dstream_feed: the stream is done";
+        return BZX_E_STATE;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    bool copied = false;
+    int rc;
+    try {
+        rc = ds_feed(s, bz2, len, final, consumed, out, cap, produced, done, &copied);
+    } catch (const std::bad_alloc &) {                       // (nothing may unwind across the C ABI)
+        ctx->err = "out of host memory";
+        rc = BZX_E_NOMEM;
+    }
+    // the accepted bytes have left the caller's buffer when the call returns (it may be page-locked and reused)
+    if (copied && hipStreamSynchronize(s->s_h2d) != hipSuccess && !rc) {
+        ctx->err = "hipStreamSynchronize(input copy) failed";
+        rc = BZX_E_HIP;
+    }
+    if (rc && !s->err_rc) {                                  // a runtime error ends the stream too
+        s->err_rc = rc;
+        s->err_text = ctx->err;
+    }
+    return rc;
+}

@@ -68,6 +68,7 @@ struct bzx_ctx {
 
     struct bzx_cstream *cs = nullptr;        // chunked stream compressor kept for bzx_compress_buffer
     std::vector<uint8_t> split_carry;        // bzx_split_rle1_chunk: raw bytes of the withheld block
+    struct bzx_dstream *ds = nullptr;        // open streaming decompressor (bzx_dstream_begin .. _end): it owns the slabs
 
     // device split scratch (bzx_rle1.hip)
     void *split_ws = nullptr;
@@ -101,6 +102,17 @@ static inline std::unique_lock<std::recursive_mutex> ctx_lock(bzx_ctx *ctx)
 {
     return ctx ? std::unique_lock<std::recursive_mutex>(ctx->api_mu) : std::unique_lock<std::recursive_mutex>();
 }
+
+// Between bzx_dstream_begin and bzx_dstream_end the slabs hold the stream's decoded blocks: every other compute entry
+// point of the context is refused (after its lock is taken; the stream stays intact).
+#define BZX_REFUSE_WHILE_STREAMING(ctx)                                                                              \
+    do {                                                                                                             \
+        if ((ctx) && (ctx)->ds) {                                                                                    \
+            (ctx)->err = "the context is busy with an open bzx_dstream (its block slabs hold the stream's decoded "  \
+                         "blocks): call bzx_dstream_end first";                                                      \
+            return BZX_E_STATE;                                                                                      \
+        }                                                                                                            \
+    } while (0)
 
 static inline int level_ok(int level) { return level >= 1 && level <= 9; }
 

@@ -277,6 +277,64 @@ int bzx_decompress_batch_device(bzx_ctx *ctx, uint32_t count, const void *const 
 int bzx_decompress_batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *srcs, const size_t *src_lens,
                                 uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
 
+/*
+ * bzx_dstream_*: streaming decompression, the counterpart of bzx_cstream_* (replaces decompress()'s reader loop,
+ * decompress.rs:38-404): the .bz2 arrives in pieces of any size, the decoded bytes leave in pieces of any size, and the
+ * device memory is fixed at bzx_dstream_begin.  Shaped like the inflate loop of libbz2 / zlib, because the output of
+ * a piece of input is unbounded (a few hundred bytes of .bz2 decode to hundreds of megabytes of zeros).
+ *   feed: takes bz2[0, len), accepts *consumed <= len bytes of it and writes *produced <= cap decoded bytes to out;
+ *   the caller presents the unconsumed rest again.  final != 0: no bytes follow those presented.  *done becomes 1
+ *   once everything is decoded, verified and delivered.  A call with len >= 1 and cap >= 1 (or final) makes progress:
+ *   it consumes input, or produces output, or sets *done.  len == 0 without final does nothing and returns BZX_OK.
+ *   feed may only buffer: accepted bytes are copied to the device at once, but a window is decoded when max_chunk
+ *   bytes have been accepted or at final, so one-byte feeds cost a copy each and not a launch each.
+ * The rule: for any way of cutting the input into feed calls and any sequence of cap values, the concatenated output
+ * and the final status are what bzx_decompress_buffer returns for the whole input with enough room -- the same bytes
+ * and BZX_OK, or BZX_E_DATA -- with its edge rules: every stream of a concatenated .bz2 is decoded; bytes after a
+ * stream that do not begin another stream ("BZh1".."BZh9" with at least 14 bytes left) are ignored -- the decision
+ * waits until 14 bytes or final have arrived, and once it has fallen *done can be set before final; a "BZh<d>" after
+ * a stream that does not decode refuses the input; randomised blocks, blocks longer than 100000 x level and selector
+ * counts outside 1..32767 are refused; the end of the input inside a header, block or footer is BZX_E_DATA.  (One
+ * difference: a block image longer than 2,400,000 bytes -- no coder writes one: 18,002 groups of 50 symbols of 20
+ * bits are 2,250,250 -- is refused as damaged.)
+ * Only verified bytes leave: a block's bytes are delivered after its CRC matched.  After BZX_E_DATA the bytes
+ * delivered so far are a prefix of the true output made of whole verified blocks (what bzip2 -dc shows of a damaged
+ * file); a call that returns an error has produced nothing.  The error is sticky: later feed calls return it again;
+ * bzx_dstream_end is still required, and the context stays usable.  feed after *done is BZX_E_STATE.
+ * Between begin and end the block slabs of the context belong to the stream (decoded blocks wait in them from one
+ * feed to the next): a second bzx_dstream_begin and every other compute entry point of that context return
+ * BZX_E_STATE (bzx_last_error says why) and leave the stream intact.
+ * Memory: two device input buffers of max_chunk + 2.4 MB, two device and two page-locked output staging areas of
+ * 48 MiB (a block expands to at most 259/5 x 900,000 = 46.62 MB), tables sized by max_chunk, and the R block slabs
+ * the context holds at begin (at least the max_blocks of bzx_ctx_create; about 28 MB each).  Nothing grows with the
+ * length of the input, the number of its blocks or streams, or its expansion ratio.  max_chunk: 0 = 128 MiB; values
+ * below 16 bytes are raised to 16 (the withheld tail has room of its own; a small chunk only costs launches).
+ * A window (the undecoded tail of the last one plus the accepted bytes) is decoded in rounds of at most R blocks; a
+ * round whose output exceeds a staging area leaves in several passes.
+ * Overlap: accepted bytes travel to the device beside the kernels of the window before, and a round's output travels
+ * back beside the kernels of the next round (three HIP streams).  Pass page-locked memory (bzx_host_alloc) as bz2
+ * for truly asynchronous copies; feed returns after the bytes it accepted have left the caller's buffer.
+ * bzx_get_stats after *done: nblk, raw_bytes and ms_total (device time of the rounds), as after a batch call.
+ */
+typedef struct bzx_dstream bzx_dstream;
+typedef struct {
+    uint64_t in_bytes;          /* bytes accepted */
+    uint64_t out_bytes;         /* bytes delivered */
+    uint32_t nblk;              /* blocks verified */
+    uint32_t nstreams;          /* streams finished (end-of-stream marker seen, combined CRC matched) */
+    uint32_t slabs;             /* block slabs of the context (R) */
+    uint32_t windows;           /* windows scanned */
+    uint32_t rounds;            /* output passes: one host synchronisation each */
+    uint32_t scans;             /* magic scans: one host synchronisation each */
+    uint64_t device_bytes;      /* device memory of the stream object (without the context's slabs) */
+    uint64_t pinned_bytes;      /* page-locked host memory of the stream object */
+} bzx_dstream_info;
+int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **out);
+int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, size_t *consumed, uint8_t *out,
+                     size_t cap, size_t *produced, int *done);
+void bzx_dstream_end(bzx_dstream *s);
+int bzx_dstream_get_info(const bzx_dstream *s, bzx_dstream_info *out);
+
 /* Per-call telemetry of the last bzx_compress_device/_buffer/_blocks/_batch_* call. */
 typedef struct {
     uint32_t nblk;

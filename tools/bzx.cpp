@@ -2,7 +2,8 @@
 // and C bzip2's conventions: -z / -d / -t, -1..-9, -c, -k, -f, -q, -v.  SURVEY.md 8f N4.  Host glue only: every byte of
 // compression and decompression work happens on the device behind include/bzx.h; without a HIP device the tool fails.
 // Compression streams the input through bzx_cstream_feed in chunks (files larger than device memory are fine and the
-// output is written while the next chunk is compressed); decompression reads the whole .bz2.  Compressing two or more
+// output is written while the next chunk is compressed); decompression of one file, of a file above the batch limit and
+// of standard input streams through bzx_dstream_feed the same way (no size guess, bounded memory).  Compressing two or more
 // named files (without -v), the regular files of at most 16 MiB are read and compressed together, one
 // bzx_compress_batch_buffer call per batch of up to 256 MiB, each into its own .bz2; -d and -t do the same through
 // bzx_decompress_batch_buffer (a file it does not accept is decoded again on its own, for the one-file path's message).
@@ -120,30 +121,50 @@ static int do_zip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *
     return ret;
 }
 
-static int unzip_data(const Opts &o, bzx_ctx *ctx, const std::vector<uint8_t> &z, FILE *out, const char *name)
+// .bz2 on `in` (or, with in == nullptr, in `mem`) -> raw bytes on `out` (none for -t) through bzx_dstream_feed: read in
+// chunks into page-locked memory, written as it is produced; no guess of the output size, one decode, device memory
+// independent of the file.
+static int do_unzip(const Opts &o, bzx_ctx *ctx, FILE *in, const std::vector<uint8_t> *mem, FILE *out, const char *name)
 {
-    size_t cap = z.size() * 6 + (1 << 20), n = 0;
-    std::vector<uint8_t> raw;
-    for (;;) {
-        raw.resize(cap);
-        const int rc = bzx_decompress_buffer(ctx, z.data(), z.size(), raw.data(), cap, &n);
-        if (rc == BZX_E_OUTBUF && n > cap) {
-            cap = n;
-            continue;
+    const size_t CH = (size_t)64 << 20, OC = (size_t)64 << 20;
+    const char *what = o.mode == TEST ? "integrity check failed" : "decompression failed";
+    bzx_dstream *ds = nullptr;
+    int rc = bzx_dstream_begin(ctx, CH, &ds);
+    if (rc) return fail(o, "cannot start", name, ctx, rc);
+    uint8_t *ibuf = in ? (uint8_t *)bzx_host_alloc(CH) : nullptr, *obuf = (uint8_t *)malloc(OC);
+    const uint8_t *src = in ? ibuf : mem->data();
+    int ret = 0, done = 0;
+    if ((in && !ibuf) || !obuf) ret = fail(o, "out of memory", name, nullptr, BZX_E_NOMEM);
+    size_t have = in ? 0 : mem->size(), off = 0, total_in = 0, total_out = 0;
+    bool eof = !in;
+    while (!ret && !done) {
+        if (off == have && !eof) {
+            have = fread(ibuf, 1, CH, in);
+            off = 0;
+            if (have < CH) {
+                if (ferror(in)) {
+                    ret = fail(o, strerror(errno), name, nullptr, BZX_OK);
+                    break;
+                }
+                eof = true;
+            }
         }
-        if (rc) return fail(o, o.mode == TEST ? "integrity check failed" : "decompression failed", name, ctx, rc);
-        break;
+        size_t used = 0, made = 0;
+        rc = bzx_dstream_feed(ds, src + off, have - off, eof ? 1 : 0, &used, obuf, OC, &made, &done);
+        if (rc) {
+            ret = fail(o, what, name, ctx, rc);
+            break;
+        }
+        off += used;
+        total_in += used;
+        total_out += made;
+        if (made && out && fwrite(obuf, 1, made, out) != made) ret = fail(o, strerror(errno), name, nullptr, BZX_OK);
     }
-    if (out && fwrite(raw.data(), 1, n, out) != n) return fail(o, strerror(errno), name, nullptr, BZX_OK);
-    if (o.verbose) fprintf(stderr, "  %s: %s, %zu -> %zu bytes\n", name, o.mode == TEST ? "ok" : "done", z.size(), n);
-    return 0;
-}
-
-static int do_unzip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *name)
-{
-    std::vector<uint8_t> z;
-    if (!read_all(in, z)) return fail(o, strerror(errno), name, nullptr, BZX_OK);
-    return unzip_data(o, ctx, z, out, name);
+    if (!ret && o.verbose) fprintf(stderr, "  %s: %s, %zu -> %zu bytes\n", name, o.mode == TEST ? "ok" : "done", total_in, total_out);
+    bzx_dstream_end(ds);
+    if (ibuf) bzx_host_free(ibuf);
+    free(obuf);
+    return ret;
 }
 
 // The end of one file's work: output flushed and closed (or removed after a failure), input removed unless -k.
@@ -197,9 +218,11 @@ static const size_t BATCH_FILE_MAX = (size_t)16 << 20;     // larger files take 
 static const size_t BATCH_BYTES = (size_t)256 << 20;       // input bytes per batch call
 static const size_t BATCH_FILES = 512;                     // files per batch call (their outputs stay open until it)
 static const uint32_t BATCH_SLABS = 320;                   // context slabs: a 256 MiB batch at -9 in one device round
+static const uint32_t UNZIP_SLABS = 256;                   // ... of a streamed -d / -t: blocks per round (one per compute unit)
 
 // -d / -t: the pending .bz2 files in one bzx_decompress_batch_buffer call.  A file whose status is not BZX_OK is
-// decoded again on its own (unzip_data), which prints the one-file path's message and retries after BZX_E_OUTBUF.
+// decoded again on its own from memory through the stream path (do_unzip), which prints the one-file path's message
+// and needs no guess of the output size.
 static int flush_unzip_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &pend)
 {
     const uint32_t n = (uint32_t)pend.size();
@@ -213,7 +236,7 @@ static int flush_unzip_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &
         for (uint32_t i = 0; i < n; i++) {
             srcs[i] = pend[i].data.data();
             lens[i] = pend[i].data.size();
-            caps[i] = lens[i] * 6 + (1 << 20);          // as unzip_data
+            caps[i] = lens[i] * 6 + (1 << 20);          // (a larger output: the stream path below)
             raw[i].resize(caps[i]);
             outs[i] = raw[i].data();
         }
@@ -228,7 +251,7 @@ static int flush_unzip_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &
         int r = 0;
         if (status[i] != BZX_OK) {
             std::vector<uint8_t>().swap(raw[i]);
-            r = unzip_data(o, ctx, p.data, p.out, p.name.c_str());
+            r = do_unzip(o, ctx, nullptr, &p.data, p.out, p.name.c_str());
         } else if (p.out && fwrite(raw[i].data(), 1, olens[i], p.out) != olens[i]) {
             r = fail(o, strerror(errno), p.name.c_str(), nullptr, BZX_OK);
         }
@@ -318,7 +341,7 @@ int main(int argc, char **argv)
     // two or more named files, without -v: the small regular ones go through the batched entry points
     const bool batching = o.files.size() >= 2 && !o.verbose;
     bzx_ctx *ctx = nullptr;
-    int rc = bzx_ctx_create(0, batching ? BATCH_SLABS : 0, &ctx);
+    int rc = bzx_ctx_create(0, batching ? BATCH_SLABS : o.mode != ZIP ? UNZIP_SLABS : 0, &ctx);
     if (rc) {
         fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
         return 2;
@@ -363,7 +386,7 @@ int main(int argc, char **argv)
             pend.push_back(std::move(p));
             continue;
         }
-        const int r = o.mode == ZIP ? do_zip(o, ctx, in, out, f.c_str()) : do_unzip(o, ctx, in, out, f.c_str());
+        const int r = o.mode == ZIP ? do_zip(o, ctx, in, out, f.c_str()) : do_unzip(o, ctx, in, nullptr, out, f.c_str());
         if (!std_in) fclose(in);
         ret |= finish_file(o, out, oname, f, r);
     }
