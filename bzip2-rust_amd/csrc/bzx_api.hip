@@ -10,6 +10,7 @@
 #include <chrono>
 #include <new>
 #include "bzx_host.h"
+#include "bzx_wg.h"
 
 extern "C" const char *bzx_version(void) { return "bzx 0.1 (gfx950)"; }
 
@@ -1112,7 +1113,8 @@ extern "C" int bzx_split_rle1_chunk(bzx_ctx *ctx, const uint8_t *raw, size_t len
 extern "C" void *bzx_host_alloc(size_t bytes)
 {
     void *p = nullptr;
-    return hipHostMalloc(&p, bytes ? bytes : 1, 0) == hipSuccess ? p : nullptr;
+    // portable: bzx_mstream_* copies from one such buffer to every device of the process
+    return hipHostMalloc(&p, bytes ? bytes : 1, BZX_HOST_PORTABLE) == hipSuccess ? p : nullptr;
 }
 extern "C" void bzx_host_free(void *p)
 {

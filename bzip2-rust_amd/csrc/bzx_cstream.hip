@@ -66,7 +66,24 @@ extern "C" void bzx_cstream_end(bzx_cstream *s)
 }
 
 // A block covers at most nblockMAX RLE1 bytes = nblockMAX / 5 runs of 255: the withheld raw tail never exceeds this.
-static size_t cstream_max_carry(int level) { return ((size_t)100000 * level / 5 + 2) * 255 + 4096; }
+size_t cstream_max_carry(int level) { return ((size_t)100000 * level / 5 + 2) * 255 + 4096; }
+
+// Footer of a stream whose last block ends at bit `end`: magic, combined CRC (crc.rs:25-27), zero padding to a byte
+// (bitwriter.rs:103-114,158-172); need = (end + 80 + 7) / 8 bytes of out are the stream.
+void stream_write_footer(uint8_t *out, uint64_t end, size_t need, uint32_t crc_comb)
+{
+    const uint8_t foot[10] = {0x17, 0x72, 0x45, 0x38, 0x50, 0x90, (uint8_t)(crc_comb >> 24), (uint8_t)(crc_comb >> 16),
+                              (uint8_t)(crc_comb >> 8), (uint8_t)crc_comb};
+    const size_t ebyte = (size_t)(end >> 3);
+    const uint32_t sh = (uint32_t)(end & 7u);
+    // bytes from the end of the last word written on are untouched so far: clear, then OR the shifted footer in
+    const size_t clear_from = (size_t)((end + 31) >> 5) * 4;
+    for (size_t i = clear_from; i < need; i++) out[i] = 0;
+    for (int i = 0; i < 10; i++) {
+        out[ebyte + i] |= (uint8_t)(foot[i] >> sh);
+        if (sh) out[ebyte + i + 1] |= (uint8_t)(foot[i] << (8 - sh));
+    }
+}
 
 extern "C" int bzx_cstream_begin(bzx_ctx *ctx, int level, size_t max_chunk, bzx_cstream **out)
 {
@@ -171,7 +188,7 @@ static int cstream_collect_finish(bzx_cstream *s)
     fold_blocks(s->st, s->h_blk[slot], 0, s->pend_nblk, 1);
     for (uint32_t b = 0; b < s->pend_nblk; b++) {
         const BzxBlock &d = s->h_blk[slot][b];
-        s->crc_comb = ((s->crc_comb << 1) | (s->crc_comb >> 31)) ^ d.crc;
+        s->crc_comb = crc_fold(s->crc_comb, d.crc);
         // (bzx_get_block_info: the stream's descriptors in order, as far as the context's descriptor table reaches)
         if (ctx->h_blk && s->nblk_total + b < ctx->cap_blocks) ctx->h_blk[s->nblk_total + b] = d;
     }
@@ -279,7 +296,6 @@ extern "C" int bzx_cstream_feed(bzx_cstream *s, const uint8_t *raw, size_t len, 
         if ((rc = cstream_collect(s))) return rc;
         if ((rc = cstream_collect_finish(s))) return rc;
         collect_stage_times(ctx);
-        // footer: magic, combined CRC (crc.rs:25-27), zero padding to a byte (bitwriter.rs:103-114,158-172)
         const uint64_t end = s->bits;
         const size_t need = (size_t)((end + 80 + 7) >> 3);
         if (need > cap) {
@@ -287,17 +303,7 @@ extern "C" int bzx_cstream_feed(bzx_cstream *s, const uint8_t *raw, size_t len, 
             s->need_hint = need;
             return BZX_E_OUTBUF;
         }
-        const uint8_t foot[10] = {0x17, 0x72, 0x45, 0x38, 0x50, 0x90, (uint8_t)(s->crc_comb >> 24), (uint8_t)(s->crc_comb >> 16),
-                                  (uint8_t)(s->crc_comb >> 8), (uint8_t)s->crc_comb};
-        const size_t ebyte = (size_t)(end >> 3);
-        const uint32_t sh = (uint32_t)(end & 7u);
-        // bytes from the end of the last word written on are untouched so far: clear, then OR the shifted footer in
-        const size_t clear_from = (size_t)((end + 31) >> 5) * 4;
-        for (size_t i = clear_from; i < need; i++) out[i] = 0;
-        for (int i = 0; i < 10; i++) {
-            out[ebyte + i] |= (uint8_t)(foot[i] >> sh);
-            if (sh) out[ebyte + i + 1] |= (uint8_t)(foot[i] << (8 - sh));
-        }
+        stream_write_footer(out, end, need, s->crc_comb);
         *produced = need;
         s->finished = true;
         ctx->stats.nblk = (uint32_t)s->nblk_total;

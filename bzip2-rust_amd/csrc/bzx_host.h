@@ -136,6 +136,16 @@ int bzx_ctx_split_scratch(bzx_ctx *ctx, size_t bytes, void **p);
 void collect_stage_times(bzx_ctx *ctx);
 void fold_blocks(bzx_stats &st, const BzxBlock *blk, uint32_t first, uint32_t end, uint32_t step);
 
+// ---- bzx_cstream.hip: what the chunked stream compressors (one device, several devices) share
+size_t cstream_max_carry(int level);            // longest withheld raw tail of a chunk
+void stream_write_footer(uint8_t *out, uint64_t end, size_t need, uint32_t crc_comb);
+// combined CRC of a stream after one more block (crc.rs:25-27)
+static inline uint32_t crc_fold(uint32_t comb, uint32_t crc) { return ((comb << 1) | (comb >> 31)) ^ crc; }
+
+// ---- bzx_mdev.hip: shift of a finished chunk to its bit phase
+void bzx_launch_shift_bits(const uint32_t *d_in, uint32_t n_words, uint32_t p, uint32_t *d_out, uint32_t n_cu,
+                           hipStream_t stream);
+
 // ---- launchers of the stage kernels
 void bzx_launch_bwt(const BzxBatch &B, uint32_t grid, hipStream_t stream);                                  // bzx_bwt.hip
 uint32_t bzx_bwt_max_blocks_per_cu();

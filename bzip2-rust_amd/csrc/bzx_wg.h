@@ -85,6 +85,33 @@ __device__ __forceinline__ uint32_t bzx_tid_here()
 #define bzx_drain_stores() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #endif
 
+// BZX_HOST_PORTABLE: the flag of page-locked host memory that every device of the process reads (the withheld tail
+// of bzx_mdev.hip, the callers' bzx_host_alloc buffers); the emulator's runtime subset has no such flag.
+// BZX_MBUF_CHUNK_MIN: smallest chunk bzx_mcompress_buffer cuts; 64 KiB on the emulator, so that its multi-chunk loop
+// over several entries runs on inputs the emulator can afford.
+#ifdef BZX_HIP_EMU
+#define BZX_HOST_PORTABLE 0u
+#define BZX_MBUF_CHUNK_MIN ((size_t)64 << 10)
+#else
+#define BZX_HOST_PORTABLE hipHostMallocPortable
+#define BZX_MBUF_CHUNK_MIN ((size_t)16 << 20)
+#endif
+
+// bzx_lane_prev(): the value of lane - 1 of the wave, 0 in lane 0 (all lanes active).  On the device one DPP move
+// (wave_shr:1, a plain vector instruction on GFX9); the emulator has no DPP and takes the shuffle.
+#ifdef BZX_HIP_EMU
+__device__ inline uint32_t bzx_lane_prev(uint32_t v)
+{
+    const uint32_t y = __shfl_up(v, 1);
+    return (threadIdx.x & 63u) ? y : 0u;
+}
+#else
+__device__ __forceinline__ uint32_t bzx_lane_prev(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);      // wave_shr:1
+}
+#endif
+
 __device__ __forceinline__ uint32_t bzx_lane() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t bzx_wave() { return threadIdx.x >> 6; }
 

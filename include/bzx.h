@@ -381,6 +381,93 @@ typedef struct bzx_block_info {
 int bzx_get_block_info(const bzx_ctx *ctx, uint32_t block, bzx_block_info *out);
 
 /*
+ * bzx_mctx_* / bzx_mstream_* / bzx_mcompress_buffer: ONE process, SEVERAL devices, one .bz2 (the
+ * reference's single process that fans blocks out and concatenates the results in order, compress.rs:66-132, ordered
+ * writer :74-122, bit concatenation bitwriter.rs:77-132).  A bzx_mctx owns one private bzx_ctx, three HIP streams and
+ * buffers of its own per entry of devices[]; the chunks of the input are dealt round-robin over the entries and the
+ * host assembles their outputs in order.  No peer access, no collective, no second process, no torch: the devices
+ * talk to the host only.  (The bzx_shard_* family above is the form for one process per GPU.)
+ * The rule: for every devices[], every way of cutting the input into feed calls and every level, the output is
+ * byte-identical to bzx_compress_buffer on the whole input (hence to libbz2 1.0.8 at that level); an empty input gives
+ * the 14-byte empty stream.
+ * devices[]: HIP ordinals; the same ordinal may appear several times -- each entry gets a context, streams and buffers
+ * of its own (two entries on one device keep two chunks in flight there).  ndev == 0, ndev > BZX_MAX_DEVICES, a NULL
+ * list or NULL out: BZX_E_PARAM; an ordinal the runtime does not have: BZX_E_NODEVICE; a failed create leaks nothing.
+ * max_blocks: as for bzx_ctx_create, per entry (a context grows to the blocks of its largest chunk, about 28 MB each).
+ * bzx_mctx_last_error names the entry of devices[] a failure belongs to.  bzx_mctx_destroy ends a stream that is still
+ * open on the object: its bzx_mstream handle is invalid afterwards and must not be passed to bzx_mstream_end.
+ * Every call sets the calling thread's current HIP device (hipSetDevice is per thread) and leaves it at the entry it
+ * touched last, which differs from call to call: a caller with HIP work of its own sets its device again.
+ *   begin: one open stream per bzx_mctx (a second begin, or bzx_mcompress_buffer, while one is open: BZX_E_STATE).
+ *   feed: one call is one chunk (len <= max_chunk, 0 = 256 MiB; BZX_E_PARAM beyond) and the k-th call goes to entry
+ *   k mod ndev.  `out`/`cap` is the WHOLE output buffer, the same on every call; *produced = length of the prefix of
+ *   out that can no longer change (never a word a later chunk still has to touch).  feed returns after the bytes it
+ *   was given have left the caller's buffer.  The call with final != 0 (len may be 0) completes the stream:
+ *   *produced = length of the .bz2.  feed after it: BZX_E_STATE.
+ *   BZX_E_OUTBUF as bzx_cstream_feed / bzx_compress_buffer report it (bzx_mcompress_buffer: bytes needed so far in
+ *   *out_len, a lower bound while chunks remain).  An error is sticky for the stream object: later feed calls return
+ *   it again; bzx_mstream_end is still required and the bzx_mctx stays usable for the next stream.
+ * What a chunk needs from its predecessor goes through the host: the raw bytes of the withheld, unfinished block (one
+ * page-locked tail buffer, refilled from the caller's bytes after every split) and its bit position (a sum kept by the
+ * host).  Every chunk is emitted at bit phase 0 into a device buffer of its entry as soon as its Huffman stage is
+ * done; when the host learns the chunk's real start and that is not a multiple of 32, a shift kernel on the entry's
+ * copy-back stream moves it to its phase before it travels to `out`; the word two chunks share is OR-merged by the
+ * host.  Chunks are collected strictly in order.  BWT, MTF, Huffman and emit of a chunk wait for nothing of the chunk
+ * before it; only the splits form a chain (the split of chunk k needs the tail chunk k-1's split left).
+ * Threads: a single host thread issues all work; the calls on one bzx_mctx are serialised by a lock of its own.  feed
+ * blocks in two places: the split's synchronisation on the entry being fed (which waits for that entry's chunk
+ * k - ndev while the other entries run) and the copy-back of chunk k - ndev.  Pass page-locked buffers
+ * (bzx_host_alloc; allocated as portable, known to every device of the process) for truly asynchronous copies: with pageable memory the
+ * runtime stages each copy and blocks the issuing thread while it lasts, which here stalls the feeding of the other
+ * entries as well.
+ * Memory is fixed at begin: per entry two device input buffers of max_chunk + the longest withheld tail (about 46 MB),
+ * two device output buffers sized as bzx_cstream_begin sizes them and one more of that size for the shifted copy; on
+ * the host one page-locked tail buffer and a few descriptors per entry.  Nothing grows with the input.
+ * bzx_mcompress_buffer is a loop over feed.  Chunk size: 16 MiB, doubled while ndev chunks do not cover the input and
+ * the chunk is below 128 MiB (len <= ndev x 128 MiB: the smallest such power of two that gives every entry one chunk); beyond that one block per compute unit of the smallest device (256 x 900,000 bytes on
+ * MI355X) -- the rule of bzx_compress_buffer, which it equals for ndev == 1.  An input of at most one chunk uses entry
+ * 0 only.  Its stream object is kept in the bzx_mctx from call to call.
+ * bzx_mctx_get_stats: nblk, n_periodic, raw_bytes, rle1_bytes, mtf_symbols and out_bits of the last finished stream;
+ * the stage times are summed over all chunks and entries, ms_total is the largest device time of an entry.
+ */
+#define BZX_MAX_DEVICES 64
+typedef struct bzx_mctx bzx_mctx;
+typedef struct bzx_mstream bzx_mstream;
+typedef struct {
+    uint32_t ndev;              /* entries of devices[] */
+    uint32_t chunks;            /* feed calls of the current / last stream */
+    uint32_t shifted;           /* chunks whose output went through the shift kernel (start not on a 32-bit boundary) */
+    uint32_t reserved;
+    uint64_t nblk;              /* blocks collected so far */
+    struct {
+        int32_t device;         /* HIP ordinal */
+        uint32_t chunks;        /* chunks with at least one block this entry compressed */
+        uint64_t blocks;
+        float ms_device;        /* HIP-event time of its stage kernels, summed over its chunks */
+        uint32_t reserved;
+        uint64_t device_bytes;  /* device memory the stream object holds for the entry (without its context's slabs) */
+        uint64_t pinned_bytes;  /* page-locked host memory the stream object holds for it */
+    } dev[BZX_MAX_DEVICES];
+} bzx_mdev_info;
+int bzx_mctx_create(const int *devices, uint32_t ndev, uint32_t max_blocks, bzx_mctx **out);
+void bzx_mctx_destroy(bzx_mctx *m);
+const char *bzx_mctx_last_error(const bzx_mctx *m);
+int bzx_mcompress_buffer(bzx_mctx *m, const uint8_t *raw, size_t len, int level, uint8_t *out, size_t cap,
+                         size_t *out_len);
+int bzx_mstream_begin(bzx_mctx *m, int level, size_t max_chunk, bzx_mstream **out);
+int bzx_mstream_feed(bzx_mstream *s, const uint8_t *raw, size_t len, int final, uint8_t *out, size_t cap,
+                     size_t *produced);
+void bzx_mstream_end(bzx_mstream *s);
+int bzx_mctx_get_stats(const bzx_mctx *m, bzx_stats *out);
+int bzx_mctx_get_info(const bzx_mctx *m, bzx_mdev_info *out);
+/*
+ * The shift kernel alone, for the parity tests (host pointers): out = in shifted right by p bits (0..31) in
+ * byte-stream bit order, most significant bit of byte 0 first: output bit i + p = input bit i, the first p bits zero.
+ * out holds nbytes + 4 rounded up to 4 bytes.
+ */
+int bzx_stage_shift_bits(bzx_ctx *ctx, const uint8_t *in, size_t nbytes, uint32_t p, uint8_t *out);
+
+/*
  * Stream assembler (replaces BitWriter, bitwriter.rs:42-172): header "BZh<level>", bit-granular
  * append of block images minus their padding, footer magic + combined CRC (crc.rs:25-27).
  * Host-side; used with bzx_compress_block(s) when the caller keeps the reference's structure.

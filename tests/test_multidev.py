@@ -1,0 +1,392 @@
+"""Single-process multi-device compression (include/bzx.h: bzx_mctx_*, bzx_mstream_*, bzx_mcompress_buffer,
+bzx_stage_shift_bits).
+
+The rule under test: for every devices[], every cutting into feed calls and every level the output is byte-identical
+to libbz2's at that level.  The same ordinal may appear several times in devices[] -- each entry has a context,
+streams and buffers of its own -- which is how the whole state machine (round-robin dealing, the withheld tail through
+the host, in-order collection, the shift of a chunk to its bit phase, the shared boundary word) runs on one GPU and,
+for the CPU tests, on the fiber emulator of tests/emu."""
+import bz2
+import ctypes as C
+import hashlib
+import json
+import os
+import random
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+
+import pytest
+
+from bzx_ctypes import EMU_PATH, ROOT, BzxLib
+from bzx_mdev_ctypes import (BZX_MAX_DEVICES, E_NODEVICE, E_OUTBUF, E_PARAM, E_STATE, BzxError, MDev, bind,
+                             mctx_create_rc, shift_bits, shift_bits_ref)
+
+GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "streams.json")))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# CPU: the emulator build
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def emu_path():
+    csrc = os.path.join(ROOT, "bzip2-rust_amd", "csrc")
+    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(ROOT, "tests", "emu", "hip", "hip_runtime.h")]
+    if not os.path.exists(EMU_PATH) or any(os.path.getmtime(s) > os.path.getmtime(EMU_PATH) for s in srcs):
+        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "emu", "build_emu.sh")])
+    return EMU_PATH
+
+
+def _emu_cases(oracle):
+    """(name, data, level, chunk sizes, empty final call) -- the inputs of test_emu_chunked_stream_and_chunked_split,
+    plus one text whose four chunks each complete a block (so that up to three entries all get blocks)."""
+    rnd = random.Random(3)
+    runs = bytearray()
+    while len(runs) < 220000:
+        runs += bytes([rnd.choice(b"ab\0")]) * rnd.randint(1, 700)
+    edge = oracle.synthtext(99981) + b"\0" * 5000 + oracle.synthtext(20000)
+    return [("empty", b"", 1, 1000, False),
+            ("xyz", b"xyz", 9, 2, False),
+            ("text", oracle.synthtext(205000), 1, 70000, False),
+            ("runs", bytes(runs), 1, 33333, False),
+            ("zeros", b"\0" * 700000, 1, 300000, False),
+            ("edge", edge, 1, [1, 99980, 4999, 3, 50000], False),
+            ("empty_final", oracle.synthtext(30000) + b"q" * 600, 1, 20000, True),
+            ("text4", oracle.synthtext(320000), 1, 105000, False)]
+
+
+@pytest.fixture(scope="module")
+def emu_runs(emu_path, oracle):
+    """Every case through bzx_mstream_* and bzx_mcompress_buffer for devices (0,), (0,0), (0,0,0): the bytes and the
+    figures the tests below look at."""
+    res = {}
+    cases = _emu_cases(oracle)
+    for devices in ((0,), (0, 0), (0, 0, 0)):
+        md = MDev(devices, emu_path)
+        try:
+            for name, data, level, chunk, empty_final in cases:
+                deal = []                       # per feed call: (entry that got blocks or None, blocks)
+
+                def after_feed(k, md=md, deal=deal, n=len(devices)):
+                    i = md.info()
+                    now = [(i.dev[e].chunks, i.dev[e].blocks) for e in range(n)]
+                    prev = deal[-1][2] if deal else [(0, 0)] * n
+                    grew = [e for e in range(n) if now[e][0] != prev[e][0]]
+                    deal.append((k, grew, now))
+                z = md.mstream_compress(data, level, chunk, empty_final=empty_final, after_feed=after_feed)
+                info, st = md.info(), md.stats()
+                # (the emulator build cuts chunks from 64 KiB up instead of 16 MiB, bzx_wg.h: with two and three
+                # entries the larger inputs are several chunks here, dealt over the entries)
+                zb = md.compress_buffer(data, level)
+                info_b = md.info()
+                res[(name, devices)] = dict(z=z, zb=zb, deal=deal, nblk=st.nblk, raw=st.raw_bytes,
+                                            out_bits=st.out_bits, shifted=info.shifted, chunks=info.chunks,
+                                            per_entry=[(info.dev[e].chunks, info.dev[e].blocks) for e in range(len(devices))],
+                                            info_nblk=info.nblk, ndev=info.ndev, zb_chunks=info_b.chunks,
+                                            zb_entries=[info_b.dev[e].chunks for e in range(len(devices))])
+        finally:
+            md.close()
+    return cases, res
+
+
+def test_emu_mdev_identity(emu_runs):
+    """mstream output and bzx_mcompress_buffer == bz2.compress for every case and every devices[]."""
+    cases, res = emu_runs
+    for name, data, level, chunk, _ in cases:
+        want = bz2.compress(data, level)
+        for devices in ((0,), (0, 0), (0, 0, 0)):
+            r = res[(name, devices)]
+            assert r["z"] == want, (name, devices, "mstream")
+            assert r["zb"] == want, (name, devices, "mcompress_buffer")
+            assert r["raw"] == len(data) and r["out_bits"] == 8 * len(want)
+    assert len(bz2.compress(b"", 1)) == 14 and res[("empty", (0, 0))]["z"] == bz2.compress(b"", 1)
+    # the one-shot call's own loop: one chunk on entry 0 for an input of at most one chunk, several chunks over the
+    # entries otherwise (320,000 bytes: 1 x 512 KiB, 2 x 256 KiB, 3 x 128 KiB)
+    for devices in ((0,), (0, 0), (0, 0, 0)):
+        assert res[("xyz", devices)]["zb_chunks"] == 1
+        assert res[("text4", devices)]["zb_chunks"] == len(devices), devices
+    assert all(c >= 1 for c in res[("text4", (0, 0, 0))]["zb_entries"])
+
+
+def test_emu_mdev_distribution(emu_runs, oracle):
+    """Chunks are dealt round-robin: a chunk's blocks are booked on entry k mod ndev; per-entry blocks sum to the
+    stream's block count, which is the one-device figure (and the oracle's); in the text whose four chunks each
+    complete a block every entry reports a chunk; and some chunk of the set went through the shift kernel."""
+    cases, res = emu_runs
+    shifted = 0
+    for name, data, level, chunk, _ in cases:
+        one = res[(name, (0,))]
+        assert one["nblk"] == oracle.compress(data, level)[1], name
+        for devices in ((0,), (0, 0), (0, 0, 0)):
+            r, n = res[(name, devices)], len(devices)
+            assert r["ndev"] == n and r["chunks"] == len(r["deal"])
+            for k, grew, _ in r["deal"]:
+                assert grew in ([], [k % n]), (name, devices, k, grew)
+            assert sum(b for _, b in r["per_entry"]) == r["nblk"] == r["info_nblk"] == one["nblk"], (name, devices)
+            with_blocks = [k for k, grew, _ in r["deal"] if grew]
+            assert sum(c for c, _ in r["per_entry"]) == len(with_blocks)
+            shifted += r["shifted"]
+    for devices in ((0,), (0, 0), (0, 0, 0)):           # four chunks, each completes a block
+        assert all(c >= 1 and b >= 1 for c, b in res[("text4", devices)]["per_entry"]), devices
+        assert len(res[("text4", devices)]["deal"]) == 4
+    assert all(c >= 1 for c, _ in res[("text", (0, 0))]["per_entry"])
+    assert shifted > 0
+
+
+SHIFT_SIZES = (0, 1, 3, 4, 5, 255, 256, 257, 4099)
+
+
+def test_emu_shift_bits(emu_path):
+    """bzx_stage_shift_bits against a big-integer shift: every phase, sizes around the word, vector and wave edges."""
+    rnd = random.Random(11)
+    lib = BzxLib(emu_path)
+    try:
+        for n in SHIFT_SIZES:
+            data = rnd.randbytes(n)
+            for p in range(32):
+                assert shift_bits(lib, data, p) == shift_bits_ref(data, p), (n, p)
+        assert shift_bits(lib, b"\xff" * 8, 1) == bytes([0x7f]) + b"\xff" * 7 + b"\x80\0\0\0"
+        with pytest.raises(BzxError) as e:
+            shift_bits(lib, b"abcd", 32)
+        assert e.value.code == E_PARAM
+    finally:
+        lib.close()
+
+
+def test_emu_mdev_errors(emu_path, oracle):
+    L = bind(C.CDLL(emu_path))
+    # create
+    assert mctx_create_rc(L, [0], ndev=0) == E_PARAM
+    assert mctx_create_rc(L, [0] * (BZX_MAX_DEVICES + 1)) == E_PARAM
+    assert mctx_create_rc(L, [0], null_list=True) == E_PARAM
+    assert mctx_create_rc(L, [0], null_out=True) == E_PARAM
+    assert mctx_create_rc(L, [0, 99]) == E_NODEVICE
+    assert mctx_create_rc(L, [-1]) == E_NODEVICE
+    assert mctx_create_rc(L, [0] * BZX_MAX_DEVICES, max_blocks=1) == 0
+    data = oracle.synthtext(120000)
+    want = bz2.compress(data, 1)
+    md = MDev((0, 0), emu_path)
+    try:
+        src = C.create_string_buffer(data, len(data))
+        cap = len(data) + 8192
+        out = C.create_string_buffer(cap)
+        # len > max_chunk; bad pointers; cap below 16
+        s = md.mstream(1, 64000)
+        assert s.feed_raw(C.addressof(src), 64001, False, C.addressof(out), cap)[0] == E_PARAM
+        assert s.feed_raw(None, 5, False, C.addressof(out), cap)[0] == E_PARAM
+        assert s.feed_raw(C.addressof(src), 5, False, None, cap)[0] == E_PARAM
+        assert s.feed_raw(C.addressof(src), 5, False, C.addressof(out), 15)[0] == E_PARAM
+        # a second begin while a stream is open, and the one-shot call
+        with pytest.raises(BzxError) as e:
+            md.mstream(1, 64000)
+        assert e.value.code == E_STATE and "open" in md.last_error()
+        assert md.compress_buffer_rc(data, 1, cap)[0] == E_STATE
+        # (the refused calls left the stream intact) feed after final
+        assert s.feed_raw(C.addressof(src), 60000, False, C.addressof(out), cap)[0] == 0
+        rc, made = s.feed_raw(C.addressof(src) + 60000, 60000, True, C.addressof(out), cap)
+        assert rc == 0 and out.raw[:made] == want
+        assert s.feed_raw(C.addressof(src), 0, True, C.addressof(out), cap)[0] == E_STATE
+        assert s.feed_raw(C.addressof(src), 10, False, C.addressof(out), cap)[0] == E_STATE
+        s.end()
+        # cap too small: BZX_E_OUTBUF, sticky on the stream; the mctx stays usable
+        small = 2000
+        s = md.mstream(1, 64000)
+        rcs = [s.feed_raw(C.addressof(src), 60000, False, C.addressof(out), small)[0],
+               s.feed_raw(C.addressof(src) + 60000, 60000, True, C.addressof(out), small)[0]]
+        assert rcs[1] == E_OUTBUF and rcs[0] in (0, E_OUTBUF)
+        assert s.feed_raw(C.addressof(src), 0, True, C.addressof(out), cap)[0] == E_OUTBUF
+        assert s.feed_raw(C.addressof(src), 10, False, C.addressof(out), cap)[0] == E_OUTBUF
+        assert "devices[" in md.last_error() or "output buffer too small" in md.last_error()
+        s.end()
+        assert md.compress_buffer(data, 1) == want
+        # the one-shot call reports the bytes needed so far; granted, they suffice
+        rc, _, need = md.compress_buffer_rc(data, 1, small)
+        assert rc == E_OUTBUF and small < need <= len(want) + 4
+        rc, z, n = md.compress_buffer_rc(data, 1, need)
+        assert rc == 0 and z == want and n == len(want)
+        assert md.compress_buffer(b"xyz", 9) == bz2.compress(b"xyz", 9)
+        # arguments of the one-shot call
+        assert md.compress_buffer_rc(data, 0, cap)[0] == E_PARAM
+        assert md.compress_buffer_rc(data, 10, cap)[0] == E_PARAM
+        assert md.compress_buffer_rc(data, 1, 8)[0] == E_PARAM
+    finally:
+        md.close()
+    assert L.bzx_mctx_last_error(None) == b""
+    L.bzx_mctx_destroy(None)
+    L.bzx_mstream_end(None)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------------------------------------------
+GPU_DEVICES = ((0,), (0, 0), (0, 0, 0, 0))
+MAX_BLOCKS = 32
+
+
+def _chunk(level):
+    return (3 << 20) * level          # about 32 blocks of a level
+
+
+def _gpu_inputs(oracle):
+    """name -> (data, level, chunk sizes).  Ten chunks unless the name says otherwise."""
+    rnd = random.Random(5)
+    c9 = _chunk(9)
+    text9 = oracle.synthtext(10 * c9, seed=77)
+    # run-heavy mix: text, short runs and runs of more than 255 bytes; a long run lies across every chunk border
+    pat = bytearray()
+    while len(pat) < (1 << 20):
+        r = rnd.random()
+        if r < 0.3:
+            pat += text9[rnd.randrange(1 << 20):][:rnd.randint(1, 3000)]
+        else:
+            pat += bytes([rnd.choice(b"ab\0\xff z")]) * rnd.randint(1, 1200 if r < 0.8 else 6)
+    runs = bytearray((bytes(pat) * (10 * c9 // len(pat) + 1))[:10 * c9])
+    for k in range(1, 10):
+        runs[k * c9 - 700:k * c9 + 900] = b"R" * 1600
+    # text with duplicated stretches of 30..80 KB (deep repeats inside a block)
+    dups = bytearray(text9)
+    for _ in range(300):
+        n = rnd.randint(30_000, 80_000)
+        src = rnd.randrange(len(dups) - n)
+        dst = min(len(dups) - n, src + rnd.randint(100_000, 700_000))
+        dups[dst:dst + n] = dups[src:src + n]
+    uneven = [c9, 500_000, c9 - 12345, 3, 2 * (1 << 20), c9, 7 * (1 << 20) + 1]
+    return {
+        "text_l1": (oracle.synthtext(10 * _chunk(1), seed=71), 1, _chunk(1)),
+        "text_l5": (oracle.synthtext(10 * _chunk(5), seed=75), 5, _chunk(5)),
+        "text_l9": (text9, 9, c9),
+        "runs_l9": (bytes(runs), 9, c9),
+        "dups_l9": (bytes(dups), 9, c9),
+        "random_l9": (oracle.randbytes(10 * c9, seed=79), 9, c9),
+        "chunk_and_a_half_l9": (text9[:c9 + c9 // 2], 9, c9),
+        "uneven_l9": (text9[1000:1000 + sum(uneven) * 2 + 17], 9, uneven),
+    }
+
+
+@pytest.fixture(scope="module")
+def gpu_inputs(oracle):
+    inputs = _gpu_inputs(oracle)
+    with ThreadPoolExecutor(max_workers=8) as ex:          # (libbz2 releases the interpreter lock)
+        futs = {name: ex.submit(bz2.compress, data, level) for name, (data, level, _) in inputs.items()}
+        want = {name: f.result() for name, f in futs.items()}
+    return inputs, want
+
+
+@pytest.fixture(scope="module")
+def gpu_mdevs(bzx):
+    """One bzx_mctx per devices[] (the bzx fixture has initialised the runtime the way the suite does)."""
+    mds = {devices: MDev(devices, max_blocks=MAX_BLOCKS) for devices in GPU_DEVICES}
+    yield mds
+    for md in mds.values():
+        md.close()
+
+
+@pytest.mark.gpu
+def test_gpu_shift_bits(bzx):
+    """The shift kernel on the device: every phase for the small sizes, and sizes of many waves and grid strides."""
+    rnd = random.Random(12)
+    for n in SHIFT_SIZES:
+        data = rnd.randbytes(n)
+        for p in range(32):
+            assert shift_bits(bzx, data, p) == shift_bits_ref(data, p), (n, p)
+    for n, ps in ((1024, range(32)), (1028, (1, 31)), (64 * 16 * 4 + 1, (0, 5)), ((1 << 20) + 5, (0, 1, 13, 31)),
+                  (40_000_003, (7, 24))):
+        data = rnd.randbytes(n)
+        for p in ps:
+            assert shift_bits(bzx, data, p) == shift_bits_ref(data, p), (n, p)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["text_l1", "text_l5", "text_l9", "runs_l9", "dups_l9", "random_l9",
+                                  "chunk_and_a_half_l9", "uneven_l9"])
+def test_gpu_mdev_identity(gpu_inputs, gpu_mdevs, name):
+    """bzx_mstream_* (pageable and page-locked buffers) and bzx_mcompress_buffer == bz2.compress on (0,), (0,0) and
+    (0,0,0,0); the per-entry blocks sum to the stream's; the memory figures do not move between the first and the last
+    feed."""
+    inputs, wants = gpu_inputs
+    data, level, chunk = inputs[name]
+    want = wants[name]
+    nblk = None
+    for devices in GPU_DEVICES:
+        md = gpu_mdevs[devices]
+        n = len(devices)
+        for pinned in (False, True):
+            mem = []
+            z = md.mstream_compress(data, level, chunk, pinned=pinned, after_feed=lambda k: mem.append(
+                [(md.info().dev[e].device_bytes, md.info().dev[e].pinned_bytes) for e in range(n)]))
+            assert z == want, (name, devices, pinned)
+            assert mem[0] == mem[-1] and all(d > 0 and h > 0 for d, h in mem[0]), (name, devices)
+            info, st = md.info(), md.stats()
+            assert sum(info.dev[e].blocks for e in range(n)) == st.nblk == info.nblk
+            nblk = st.nblk if nblk is None else nblk
+            assert st.nblk == nblk and st.raw_bytes == len(data) and st.out_bits == 8 * len(want)
+            nfeeds = info.chunks
+            if nfeeds >= 2 * n and name.startswith(("text", "runs", "dups", "random")):
+                assert all(info.dev[e].chunks >= 2 for e in range(n)), (name, devices)
+                assert info.shifted > 0
+        assert md.compress_buffer(data, level) == want, (name, devices, "mcompress_buffer")
+
+
+@pytest.mark.gpu
+def test_gpu_mdev_small_and_errors(gpu_mdevs):
+    md = gpu_mdevs[(0, 0)]
+    assert md.compress_buffer(b"", 9) == bz2.compress(b"", 9)
+    assert md.mstream_compress(b"", 3, 1000) == bz2.compress(b"", 3)
+    assert md.mstream_compress(b"xyz", 9, 2, empty_final=True) == bz2.compress(b"xyz", 9)
+    L = md.lib
+    assert mctx_create_rc(L, [0], ndev=0) == E_PARAM
+    assert mctx_create_rc(L, [0, 4096]) == E_NODEVICE
+    data = os.urandom(3_000_000)
+    want = bz2.compress(data, 9)
+    rc, _, need = md.compress_buffer_rc(data, 9, 100_000)
+    assert rc == E_OUTBUF and need > 100_000
+    rc, z, _ = md.compress_buffer_rc(data, 9, need)
+    assert rc == 0 and z == want
+
+
+@pytest.mark.gpu
+def test_gpu_mdev_1GiB(bzx, oracle):
+    """1 GiB of text at -9 over (0,0), page-locked to page-locked, against the committed sha256 of libbz2's stream."""
+    g = GOLDEN["streams"]["config3_text_1GiB_l9"]
+    n = g["raw_len"]
+    cap = n + n // 50 + 4096
+    md = MDev((0, 0), max_blocks=260)
+    L = md.lib
+    p_src, p_out = L.bzx_host_alloc(n), L.bzx_host_alloc(cap)
+    try:
+        assert p_src and p_out
+        oracle.lib.bzo_synthtext(0x9E3779B97F4A7C15, (C.c_char * n).from_address(p_src), n)
+        got = md.compress_ptr(p_src, n, g["level"], p_out, cap)
+        assert got == g["bz2_len"]
+        assert hashlib.sha256((C.c_char * got).from_address(p_out)).hexdigest() == g["bz2_sha256"]
+        info = md.info()
+        print("1 GiB over (0,0):", [(info.dev[e].chunks, info.dev[e].blocks, round(info.dev[e].ms_device, 1)) for e in range(2)],
+              "shifted", info.shifted)
+        assert info.dev[0].chunks >= 1 and info.dev[1].chunks >= 1
+        assert info.dev[0].blocks + info.dev[1].blocks == md.stats().nblk
+    finally:
+        L.bzx_host_free(p_src)
+        L.bzx_host_free(p_out)
+        md.close()
+
+
+@pytest.mark.gpu
+def test_gpu_mdev_real_devices(bzx, gpu_inputs):
+    """Entries on different devices: (0,1) and all devices of the process on the level-9 text.  Skips on a machine
+    that shows the process one device (the only test of this file that may skip)."""
+    import torch
+    have = torch.cuda.device_count()
+    if have < 2:
+        pytest.skip("the process sees one device")
+    inputs, wants = gpu_inputs
+    data, level, chunk = inputs["text_l9"]
+    for devices in ((0, 1), tuple(range(have))):
+        md = MDev(devices, max_blocks=MAX_BLOCKS)
+        try:
+            for pinned in (False, True):
+                assert md.mstream_compress(data, level, chunk, pinned=pinned) == wants["text_l9"], (devices, pinned)
+            info = md.info()
+            if info.chunks >= len(devices):
+                assert all(info.dev[e].chunks >= 1 for e in range(len(devices)))
+            assert md.compress_buffer(data, level) == wants["text_l9"]
+        finally:
+            md.close()

@@ -7,6 +7,8 @@
 // named files (without -v), the regular files of at most 16 MiB are read and compressed together, one
 // bzx_compress_batch_buffer call per batch of up to 256 MiB, each into its own .bz2; -d and -t do the same through
 // bzx_decompress_batch_buffer (a file it does not accept is decoded again on its own, for the one-file path's message).
+// --devices LIST (HIP ordinals, comma-separated, repeats allowed): the chunked compression path deals its chunks over
+// these devices through bzx_mstream_feed, one process, host-side assembly; the bytes are the same.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,6 +28,7 @@ struct Opts {
     int verbose = 0;
     bool quiet = false;
     std::vector<std::string> files;
+    std::vector<int> devices;          // --devices: entries of a bzx_mctx for the chunked compression path
 };
 
 static void help()
@@ -37,6 +40,7 @@ static void help()
          "  -1 .. -9          block size 100k .. 900k   --fast = -1, --best = -9 (default)\n"
          "  -q --quiet        no warnings               -v --verbose      statistics (-vv more)\n"
          "  -s --small        accepted, ignored         -h --help  -V --version  -L --license\n"
+         "  --devices LIST    compress one stream on several devices: ordinals, comma-separated, repeats allowed\n"
          "With no file, or when a file is -, reads standard input and writes standard output.");
 }
 
@@ -56,12 +60,21 @@ static int fail(const Opts &o, const char *what, const char *name, bzx_ctx *ctx,
 }
 
 // input stream -> .bz2 on `out`, chunk by chunk
-static int do_zip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *name)
+static int mfail(const Opts &o, const char *what, const char *name, bzx_mctx *m, int rc)
+{
+    if (!o.quiet) fprintf(stderr, "bzx: %s: %s: %s%s%s\n", name, what, bzx_strerror(rc), bzx_mctx_last_error(m)[0] ? ": " : "",
+                          bzx_mctx_last_error(m));
+    return 1;
+}
+
+// (mctx: with --devices the chunks go through bzx_mstream_feed, dealt over its entries, instead of bzx_cstream_feed)
+static int do_zip(const Opts &o, bzx_ctx *ctx, bzx_mctx *mctx, FILE *in, FILE *out, const char *name)
 {
     const size_t CH = (size_t)64 << 20;
     bzx_cstream *cs = nullptr;
-    int rc = bzx_cstream_begin(ctx, o.level, CH, &cs);
-    if (rc) return fail(o, "cannot start", name, ctx, rc);
+    bzx_mstream *ms = nullptr;
+    int rc = mctx ? bzx_mstream_begin(mctx, o.level, CH, &ms) : bzx_cstream_begin(ctx, o.level, CH, &cs);
+    if (rc) return mctx ? mfail(o, "cannot start", name, mctx, rc) : fail(o, "cannot start", name, ctx, rc);
     uint8_t *buf[2] = {(uint8_t *)bzx_host_alloc(CH), (uint8_t *)bzx_host_alloc(CH)};
     size_t cap = CH + CH / 50 + (1 << 20), total_in = 0, flushed = 0, produced = 0;
     uint8_t *obuf = (uint8_t *)malloc(cap);
@@ -84,9 +97,10 @@ static int do_zip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *
             obuf = nb;
             cap = need * 2;
         }
-        rc = bzx_cstream_feed(cs, buf[k & 1], have, fin, obuf, cap, &produced);
+        rc = mctx ? bzx_mstream_feed(ms, buf[k & 1], have, fin, obuf, cap, &produced)
+                  : bzx_cstream_feed(cs, buf[k & 1], have, fin, obuf, cap, &produced);
         if (rc) {
-            ret = fail(o, "compression failed", name, ctx, rc);
+            ret = mctx ? mfail(o, "compression failed", name, mctx, rc) : fail(o, "compression failed", name, ctx, rc);
             break;
         }
         total_in += have;
@@ -100,7 +114,17 @@ static int do_zip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *
         if (fin) break;
         have = next;
     }
-    if (!ret && o.verbose) {
+    if (!ret && o.verbose && mctx) {
+        bzx_stats st;
+        bzx_mdev_info *mi = new (std::nothrow) bzx_mdev_info;
+        bzx_mctx_get_stats(mctx, &st);
+        fprintf(stderr, "  %s: %zu -> %zu bytes, %.3f:1, %u blocks (%u periodic)\n", name, total_in, produced,
+                produced ? (double)total_in / (double)produced : 0.0, st.nblk, st.n_periodic);
+        for (uint32_t e = 0; mi && bzx_mctx_get_info(mctx, mi) == BZX_OK && e < mi->ndev; e++)
+            fprintf(stderr, "    devices[%u] = %d: %u chunks, %llu blocks, %.1f ms\n", e, mi->dev[e].device, mi->dev[e].chunks,
+                    (unsigned long long)mi->dev[e].blocks, mi->dev[e].ms_device);
+        delete mi;
+    } else if (!ret && o.verbose) {
         bzx_stats st;
         bzx_get_stats(ctx, &st);
         fprintf(stderr, "  %s: %zu -> %zu bytes, %.3f:1, %u blocks (%u periodic)\n", name, total_in, produced,
@@ -114,7 +138,8 @@ static int do_zip(const Opts &o, bzx_ctx *ctx, FILE *in, FILE *out, const char *
                     bi.n_selectors, bi.bits_symbol_map, bi.bits_selectors, bi.bits_tables, bi.bits_payload,
                     (unsigned long long)bi.bits);
     }
-    bzx_cstream_end(cs);
+    if (mctx) bzx_mstream_end(ms);
+    else bzx_cstream_end(cs);
     bzx_host_free(buf[0]);
     bzx_host_free(buf[1]);
     free(obuf);
@@ -317,6 +342,24 @@ int main(int argc, char **argv)
             else if (a == "--small") {}
             else if (a == "--fast") o.level = 1;
             else if (a == "--best") o.level = 9;
+            else if (a == "--devices" || a.rfind("--devices=", 0) == 0) {
+                std::string list = a == "--devices" ? (i + 1 < argc ? argv[++i] : "") : a.substr(10);
+                o.devices.clear();
+                for (size_t p = 0; p <= list.size();) {
+                    const size_t q = list.find(',', p) == std::string::npos ? list.size() : list.find(',', p);
+                    const std::string t = list.substr(p, q - p);
+                    if (t.empty() || t.size() > 4 || t.find_first_not_of("0123456789") != std::string::npos) {
+                        fprintf(stderr, "bzx: --devices takes ordinals separated by commas, e.g. 0,1 (got \"%s\")\n", list.c_str());
+                        return 1;
+                    }
+                    o.devices.push_back(atoi(t.c_str()));
+                    p = q + 1;
+                }
+                if (o.devices.size() > BZX_MAX_DEVICES) {
+                    fprintf(stderr, "bzx: --devices takes at most %d entries\n", BZX_MAX_DEVICES);
+                    return 1;
+                }
+            }
             else { fprintf(stderr, "bzx: unexpected argument %s\n", a.c_str()); return 1; }
         } else {
             for (size_t k = 1; k < a.size(); k++) {
@@ -345,6 +388,17 @@ int main(int argc, char **argv)
     if (rc) {
         fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
         return 2;
+    }
+    bzx_mctx *mctx = nullptr;
+    if (!o.devices.empty() && o.mode != ZIP) {
+        if (o.verbose) fprintf(stderr, "bzx: --devices applies to compression only: ignored\n");
+    } else if (!o.devices.empty()) {
+        rc = bzx_mctx_create(o.devices.data(), (uint32_t)o.devices.size(), 0, &mctx);
+        if (rc) {
+            fprintf(stderr, "bzx: --devices: %s\n", bzx_strerror(rc));
+            bzx_ctx_destroy(ctx);
+            return 2;
+        }
     }
     int ret = 0;
     std::vector<Pending> pend;
@@ -386,11 +440,12 @@ int main(int argc, char **argv)
             pend.push_back(std::move(p));
             continue;
         }
-        const int r = o.mode == ZIP ? do_zip(o, ctx, in, out, f.c_str()) : do_unzip(o, ctx, in, nullptr, out, f.c_str());
+        const int r = o.mode == ZIP ? do_zip(o, ctx, mctx, in, out, f.c_str()) : do_unzip(o, ctx, in, nullptr, out, f.c_str());
         if (!std_in) fclose(in);
         ret |= finish_file(o, out, oname, f, r);
     }
     ret |= flush_batch(o, ctx, pend, pend_bytes);
+    bzx_mctx_destroy(mctx);
     bzx_ctx_destroy(ctx);
     return ret;
 }
