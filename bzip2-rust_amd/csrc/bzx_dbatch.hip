@@ -1,7 +1,7 @@
-// bzx_dbatch.hip -- batched decompression on gfx950: many .bz2 inputs (each one stream or several concatenated) in
-// one call.
+// bzx_dbatch.hip -- the host decoder on gfx950: many .bz2 inputs (each one stream or several concatenated) in one
+// call (bzx_decompress_batch_*); the one-shot calls (bzx_decompress_device / _buffer) are its count = 1.
 //
-// The kernels that decode one block (bzx_decomp.hip: decode, inverse BWT, expand) already work over any set of blocks;
+// The kernels that decode one block (bzx_decomp.hip: decode, inverse BWT, expand, CRC) work over any set of blocks;
 // what a batch needs around them is segmented:
 //   scan, once per call   every input gets scan tiles of its own (tile -> input map), so no read window crosses an
 //                         input's end.  A candidate is (input, bit, kind); an end-of-stream candidate also carries
@@ -19,7 +19,7 @@
 //     layout              one workgroup: per input, an exclusive scan of its chain blocks' sizes -> every block's
 //                         destination; an input whose total exceeds its cap (or whose walk failed) is flagged and
 //                         neither expanded nor checked
-//     expand, CRC         bzx_dc_expand_kernel through BzxDcDst; block CRCs with bzx_crc_range (bzx_rle1.h)
+//     expand, CRC         bzx_dc_expand_kernel and bzx_dc_crc_kernel through BzxDcDst
 //     [sync 2]            one copy of CRCs, sizes and flags; the host checks block and combined CRCs
 // Host synchronisations: one after the scan (two after a table overflow), two per round, none per input or stream.
 #include <hip/hip_runtime.h>
@@ -27,12 +27,9 @@
 #include <algorithm>
 #include <new>
 #include "bzx_host.h"
-#include "bzx_rle1.h"
+#include "bzx_wg.h"
 
-#define DB_MAGIC_BLOCK 0x314159265359ull
-#define DB_MAGIC_EOS 0x177245385090ull
 #define DB_TILE 1024               // scan tile: 256 lanes x 4 byte offsets
-#define DB_SKIP 0x800u             // BzxBlock.status: off the chain, or its input is refused (the later kernels skip it)
 #define DB_NT 1024                 // layout kernel (one workgroup)
 
 struct DbIn {                      // one input of the call (scan)
@@ -67,37 +64,24 @@ __global__ __launch_bounds__(256) void bzx_db_scan_kernel(const DbIn *__restrict
         const uint32_t i = tile_in[tile];
         const DbIn s = in[i];
         const uint8_t *__restrict__ z = s.z;
-        if (tile == s.tile0 && threadIdx.x == 0) {
-            const bool ok = s.len >= 14 && z[0] == 'B' && z[1] == 'Z' && z[2] == 'h' && z[3] >= '1' && z[3] <= '9';
-            level[i] = ok ? (uint32_t)(z[3] - '0') : 0u;
-        }
+        if (tile == s.tile0 && threadIdx.x == 0) level[i] = s.len >= 14 ? bzx_bzh_level(z) : 0u;
         const uint64_t byte0 = (tile - s.tile0) * DB_TILE + (uint64_t)threadIdx.x * 4;
         if (byte0 >= s.len) continue;
-        uint64_t hi = 0, lo = 0;                            // bytes byte0 .. byte0+15 of the input, big-endian
-#pragma unroll
-        for (int k = 0; k < 8; k++) hi = (hi << 8) | (byte0 + k < s.len ? z[byte0 + k] : 0u);
-#pragma unroll
-        for (int k = 8; k < 16; k++) lo = (lo << 8) | (byte0 + k < s.len ? z[byte0 + k] : 0u);
-        for (uint32_t sh = 0; sh < 32; sh++) {
-            const uint64_t x = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
-            const uint64_t v = x >> 16;
-            const uint64_t bit = byte0 * 8 + sh;
-            if ((v != DB_MAGIC_BLOCK && v != DB_MAGIC_EOS) || bit < 32 || bit + 48 > s.len * 8) continue;
+        bzx_dc_scan_word(z, s.len, byte0, [&](uint64_t bit, bool eos, uint64_t x, uint64_t y) {
+            if (bit < 32) return;                           // (the stream header)
             DbCand c;
             c.input = i;
             c.crc = 0;
             uint32_t next = 0;
-            if (v == DB_MAGIC_EOS) {
-                if (bit + 80 <= s.len * 8) c.crc = (uint32_t)(((x & 0xFFFFull) << 16) | ((lo << sh) >> 48));
+            if (eos) {
+                if (bit + 80 <= s.len * 8) c.crc = (uint32_t)(((x & 0xFFFFull) << 16) | (y >> 48));
                 const uint64_t at = (bit + 80 + 7) / 8;
-                if (at + 14 <= s.len && z[at] == 'B' && z[at + 1] == 'Z' && z[at + 2] == 'h' && z[at + 3] >= '1' &&
-                    z[at + 3] <= '9')
-                    next = (uint32_t)(z[at + 3] - '0');
+                if (at + 14 <= s.len) next = bzx_bzh_level(z + at);
             }
-            c.pos = (bit << 5) | (next << 1) | (v == DB_MAGIC_EOS ? 1u : 0u);
+            c.pos = (bit << 5) | (next << 1) | (eos ? 1u : 0u);
             const uint32_t k = atomicAdd(n_cand, 1u);
             if (k < cap) cand[k] = c;
-        }
+        });
     }
 }
 
@@ -107,7 +91,7 @@ __global__ __launch_bounds__(DB_NT) void bzx_db_layout_kernel(BzxBatch B, DbIo *
                                                               BzxDcDst *__restrict__ dst, uint64_t *__restrict__ end)
 {
     __shared__ uint64_t wsum[DB_NT / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = bzx_lane(), wave = bzx_wave();
     uint64_t carry = 0;
     for (uint32_t r0 = 0; r0 < nio; r0 += DB_NT) {
         const uint32_t r = r0 + tid;
@@ -125,11 +109,7 @@ __global__ __launch_bounds__(DB_NT) void bzx_db_layout_kernel(BzxBatch B, DbIo *
         }
         const uint64_t size = (r < nio && d.live && !flag) ? total : 0;
         // exclusive scan of the sizes over the workgroup (the staging offsets of the _buffer form)
-        uint64_t x = size;
-        for (uint32_t k = 1; k < 64; k <<= 1) {
-            const uint64_t y = __shfl_up(x, k);
-            if (lane >= k) x += y;
-        }
+        const uint64_t x = bzx_wave_incl_sum64(size);
         if (lane == 63) wsum[wave] = x;
         __syncthreads();
         uint64_t pre = 0, tot = 0;
@@ -154,19 +134,6 @@ __global__ __launch_bounds__(DB_NT) void bzx_db_layout_kernel(BzxBatch B, DbIo *
         }
     }
     if (tid == 0) end[0] = carry;
-}
-
-// ---- CRC-32/BZIP2 of every expanded block of the round (bzx_crc_range, bzx_rle1.h) ---------------------------------
-__global__ __launch_bounds__(CRC_NT) void bzx_db_crc_kernel(BzxBatch B, const BzxDcDst *__restrict__ dst,
-                                                            uint32_t *__restrict__ got)
-{
-    __shared__ BzxCrcLds lds;
-    const uint32_t my_weight = bzx_crc_setup(lds);
-    for (uint32_t b = blockIdx.x; b < B.nblk; b += gridDim.x) {
-        if (B.blk[b].status || !dst[b].p) continue;          // (uniform over the workgroup)
-        const uint32_t crc = bzx_crc_range(dst[b].p, 0, B.blk[b].pack_word, lds, my_weight);
-        if (threadIdx.x == 0) got[b] = crc;
-    }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
@@ -216,9 +183,11 @@ struct DbResult {
 
 // The batch on device inputs.  d_outs null (the _buffer form): each round's outputs are packed into a device staging
 // area and copied, one copy per round, into the pinned bounce buffer; then into h_outs[i] on the host.
+// one_stream (bzx_decompress_device): an input whose first stream is followed by another is refused, once that first
+// stream has passed every check of its own.
 static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, const size_t *src_lens,
                       void *const *d_outs, uint8_t *const *h_outs, const size_t *caps, size_t *out_lens, int *status,
-                      DbResult &res)
+                      DbResult &res, bool one_stream = false)
 {
     hipStream_t st = ctx->stream;
     res.reason.assign(count, std::string());
@@ -302,7 +271,7 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
     for (uint32_t i = 0; i < count; i++) {
         if (!level[i]) {
             status[i] = BZX_E_DATA;
-            res.reason[i] = src_lens[i] < 14 ? "shorter than the smallest bzip2 stream" : "no BZh1..BZh9 header";
+            res.reason[i] = dc_why_text(src_lens[i] < 14 ? DC_WHY_SHORT : DC_WHY_NO_HEADER);
             nblkc[i] = 0;
         }
         if (nblkc[i] > R) R = nblkc[i];
@@ -379,14 +348,14 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
         B.nblk = nb;
         if (nb) {
             HIP_TRY(ctx, hipMemcpyAsync(d_src, src.data(), nb * sizeof(BzxDcSrc), hipMemcpyHostToDevice, st));
-            bzx_launch_dc_decode(B, nullptr, 0, nullptr, d_src, BZX_MAX_N, st);
+            bzx_launch_dc_decode(B, d_src, st);
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, nb * sizeof(BzxBlock), hipMemcpyDeviceToHost, st));
         }
         if (nb || !pending.empty()) HIP_TRY(ctx, hipStreamSynchronize(st));   // round synchronisation 1: descriptors
         drain();
         // ---- chain walk of every input of the round
-        std::vector<uint8_t> on_chain(nb, 0);
+        std::vector<uint8_t> on_chain(nb, 0), follows(nio, 0);
         chain.clear();
         streams.assign(nio, {});
         uint64_t staging_need = 0;
@@ -411,12 +380,12 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
             };
             uint64_t end_bit = 32;
             uint32_t lvl = level[i], s_first = (uint32_t)chain.size();
-            const char *why = nullptr;
+            uint32_t why = DC_OK;
             uint64_t bound = 0;
             for (;;) {
                 const int64_t k = find(end_bit);
                 if (k < 0) {
-                    why = "blocks do not end at an end-of-stream marker";
+                    why = DC_WHY_NO_EOS;
                     break;
                 }
                 const DbCand &c = cand[c_first[i] + k];
@@ -424,11 +393,11 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
                     const uint32_t b = blk_of[k];
                     const BzxBlock &d = ctx->h_blk[b];
                     if (d.status & BZX_ST_DC_RANDOMISED) {
-                        why = "randomised block (written by bzip2 0.9.0 or older): not supported";
+                        why = DC_WHY_RANDOMISED;
                         break;
                     }
                     if (d.status || d.n > 100000u * lvl) {
-                        why = "damaged block in the bzip2 stream";
+                        why = DC_WHY_DAMAGED;
                         break;
                     }
                     chain.push_back(b);
@@ -438,19 +407,20 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
                     continue;
                 }
                 if ((end_bit + 80 + 7) / 8 > in[i].len) {
-                    why = "truncated after the end-of-stream marker";
+                    why = DC_WHY_TRUNC_EOS;
                     break;
                 }
                 streams[r].push_back({(uint32_t)chain.size() - s_first, c.crc});
                 s_first = (uint32_t)chain.size();
                 const uint32_t next = (uint32_t)(c.pos >> 1) & 15u;
-                if (!next) break;
+                follows[r] = one_stream && next;
+                if (!next || one_stream) break;
                 end_bit = 8 * ((end_bit + 80 + 7) / 8) + 32;
                 lvl = next;
             }
             if (why) {
                 status[i] = BZX_E_DATA;
-                res.reason[i] = why;
+                res.reason[i] = dc_why_text(why);
                 for (uint32_t b = io.c0; b < chain.size(); b++) on_chain[chain[b]] = 0;
                 chain.resize(io.c0);
                 streams[r].clear();
@@ -461,7 +431,7 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
             staging_need += al16(std::min<uint64_t>(caps[i], bound));
         }
         for (uint32_t b = 0; b < nb; b++)
-            if (!on_chain[b]) ctx->h_blk[b].status |= DB_SKIP;
+            if (!on_chain[b]) ctx->h_blk[b].status |= DC_SKIP;
         if (!d_outs && staging_need > stg.bytes) {
             if (stg.p) (void)hipFree(stg.p);
             stg.p = nullptr;
@@ -484,8 +454,7 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
                            d_outs ? nullptr : stg.p, d_dst, d_end);
         if (nb) {
             bzx_launch_dc_expand(B, ctx->d_in, d_dst, st);
-            hipLaunchKernelGGL(bzx_db_crc_kernel, dim3(nb < (uint32_t)ctx->n_cu ? nb : (uint32_t)ctx->n_cu), dim3(CRC_NT), 0,
-                               st, B, d_dst, d_got);
+            bzx_launch_dc_crc(B, d_dst, d_got, (uint32_t)ctx->n_cu, st);
             HIP_TRY(ctx, hipMemcpyAsync(h_got, d_got, nb * 4, hipMemcpyDeviceToHost, st));
         }
         HIP_TRY(ctx, hipGetLastError());
@@ -499,29 +468,33 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
             if (status[i] || !io.live) continue;
             if (io.flag == 1) {
                 status[i] = BZX_E_DATA;
-                res.reason[i] = "damaged block in the bzip2 stream (inverse BWT)";
+                res.reason[i] = dc_why_text(DC_WHY_IBWT);
                 continue;
             }
             if (io.flag == 2) {
                 status[i] = BZX_E_OUTBUF;
                 out_lens[i] = (size_t)io.total;
-                res.reason[i] = "output buffer too small for the decompressed data";
+                res.reason[i] = dc_why_text(DC_WHY_OUTBUF);
                 continue;
             }
-            const char *why = nullptr;
+            uint32_t why = DC_OK, bad_blk = 0;                 // (bad_blk: the block's number within its input)
             uint32_t k = io.c0;
             for (const auto &s : streams[r]) {
                 uint32_t comb = 0;
                 for (uint32_t j = 0; j < s.first; j++, k++) {
                     const uint32_t b = chain[k];
-                    if (!why && h_got[b] != ctx->h_blk[b].crc) why = "block CRC mismatch";
-                    comb = ((comb << 1) | (comb >> 31)) ^ ctx->h_blk[b].crc;    // stored CRCs (crc.rs:25-27)
+                    if (!why && h_got[b] != ctx->h_blk[b].crc) {
+                        why = DC_WHY_BLOCK_CRC;
+                        bad_blk = k - io.c0;
+                    }
+                    comb = crc_fold(comb, ctx->h_blk[b].crc);      // stored CRCs
                 }
-                if (!why && comb != s.second) why = "combined CRC mismatch";
+                if (!why && comb != s.second) why = DC_WHY_COMBINED_CRC;
             }
+            if (!why && follows[r]) why = DC_WHY_STREAM_FOLLOWS;
             if (why) {
                 status[i] = BZX_E_DATA;
-                res.reason[i] = why;
+                res.reason[i] = dc_why_text(why, bad_blk);
                 continue;
             }
             out_lens[i] = (size_t)io.total;
@@ -707,4 +680,66 @@ extern "C" int bzx_decompress_batch_buffer(bzx_ctx *ctx, uint32_t count, const u
         }
     }
     return dbatch_finish(ctx, fn, rc, count, status, all);
+}
+
+// ---- the one-shot calls: one input through the core; its status is the return value, its reason the error text ------
+static int dbatch_one(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len, bool one_stream)
+{
+    DbResult res;
+    int status = BZX_OK, rc;
+    try {
+        rc = dbatch_run(ctx, 1, &d_bz2, &len, &d_out, nullptr, &cap, out_len, &status, res, one_stream);
+    } catch (const std::bad_alloc &) {                 // (nothing may unwind across the C ABI)
+        ctx->err = "out of host memory";
+        rc = BZX_E_NOMEM;
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);             // nothing of a failed call is left in flight
+        return rc;
+    }
+    if (status) {
+        ctx->err = res.reason[0];
+        return status;
+    }
+    ctx->stats.nblk = res.nblk;                              // (the other fields stay: the last compression's)
+    ctx->stats.raw_bytes = res.raw_bytes;
+    ctx->stats_batch = true;                                 // the pinned descriptors are candidates, not blocks
+    return BZX_OK;
+}
+
+// Device buffer -> device buffer: ONE stream (the reference's decompress() also stops at the first footer,
+// decompress.rs:81-95).  Bytes behind the footer that are not another stream are ignored, as bzip2 does ("trailing
+// garbage"); a concatenated .bz2 (pbzip2 output, cat a.bz2 b.bz2) is refused here rather than decoded in part --
+// bzx_decompress_buffer decodes every stream of it.
+extern "C" int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
+    if (!ctx || !d_bz2 || !out_len || (cap && !d_out) || ((uintptr_t)d_out & 15u)) return BZX_E_PARAM;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return dbatch_one(ctx, d_bz2, len, d_out, cap, out_len, true);
+}
+
+// Host buffer -> host buffer, every stream of the input: upload, one core call into a device output of cap bytes, copy
+// back what was decoded.
+extern "C" int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
+    if (!ctx || !bz2 || !out_len || (cap && !out)) return BZX_E_PARAM;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    *out_len = 0;
+    void *d_z = nullptr, *d_o = nullptr;
+    if (hipMalloc(&d_z, len + 64) != hipSuccess) return BZX_E_NOMEM;
+    if (hipMalloc(&d_o, cap + 64) != hipSuccess) {
+        (void)hipFree(d_z);
+        return BZX_E_NOMEM;
+    }
+    int rc = hipMemcpyAsync(d_z, bz2, len, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? BZX_OK : BZX_E_HIP;
+    if (!rc) rc = dbatch_one(ctx, d_z, len, d_o, cap, out_len, false);
+    if (!rc && *out_len && hipMemcpy(out, d_o, *out_len, hipMemcpyDeviceToHost) != hipSuccess) rc = BZX_E_HIP;
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_z);
+    (void)hipFree(d_o);
+    return rc;
 }

@@ -5,8 +5,9 @@
 // every block CRC and the combined CRC checked.  The reference decodes one block after the other on one thread; here
 // the blocks of a stream are decoded side by side:
 //   scan      every bit offset is tested for the 48-bit block magic / end-of-stream magic (blocks start at arbitrary
-//             bits); the host orders the candidates, a candidate that does not continue the chain of decoded blocks
-//             is a chance match inside compressed data and is dropped
+//             bits): bzx_dc_scan_word (bzx_dc.h) inside the scan kernels of bzx_dbatch.hip and bzx_dstream.hip, which
+//             also order the candidates and walk the chain of blocks; a candidate that does not continue the chain
+//             is a chance match inside compressed data and is skipped (DC_SKIP)
 //   decode    one wave per block: header, symbol map, selectors, code lengths (decompress.rs:98-260), then the
 //             Huffman / MTF / RUNA-RUNB loop (decompress.rs:293-358).  The bit reader and the Huffman tables are
 //             wave-uniform; the 256-entry MTF list lives in four registers per lane and a move-to-front is a few
@@ -16,46 +17,17 @@
 //             per block, 64 blocks per wave (bwt_sort.rs:91-130); the walk also measures the RLE1 expansion and
 //             leaves a checkpoint every 4096 bytes
 //   expand    RLE1 runs are expanded from the checkpoints in parallel (rle1.rs:267-316) at the block's final
-//             offset; block CRCs come from the compressor's CRC kernel (bzx_rle1.hip) over the output
+//             offset; block CRCs with bzx_crc_range (bzx_rle1.h) over the output
 // Integer/byte work, latency-bound (a serial bit stream and a serial pointer chase per block); all blocks of a
-// stream are in flight at once.
+// round are in flight at once.  This file holds the kernels and their launchers; every block is read through its
+// BzxDcSrc and written through its BzxDcDst, so one set of kernels serves the one-shot calls, the batch and the stream.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <new>
 #include "bzx_host.h"
+#include "bzx_rle1.h"
 #include "bzx_wg.h"
 
-#define DC_MAGIC_BLOCK 0x314159265359ull
-#define DC_MAGIC_EOS 0x177245385090ull
-#define DC_ERR_HEADER 0x100u       // BzxBlock.status bits set by the decoder
-#define DC_ERR_DATA 0x200u
 #define DC_CK_SHIFT 12             // a checkpoint every 4096 bytes of the RLE1 image
 #define DC_CK_STRIDE 224           // checkpoints per block slab (900000 / 4096 + 1 = 220)
-
-// ---- scan: candidate block starts ---------------------------------------------------------------------------
-__global__ void bzx_dc_scan_kernel(const uint8_t *__restrict__ z, uint64_t nbytes, uint64_t *__restrict__ found,
-                                   uint32_t *__restrict__ n_found, uint32_t cap)
-{
-    const uint64_t nwords = (nbytes + 3) / 4;
-    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t byte0 = w * 4;
-        uint64_t hi = 0, lo = 0;                            // bytes byte0 .. byte0+15, big-endian
-#pragma unroll
-        for (int i = 0; i < 8; i++) hi = (hi << 8) | (byte0 + i < nbytes ? z[byte0 + i] : 0u);
-#pragma unroll
-        for (int i = 8; i < 16; i++) lo = (lo << 8) | (byte0 + i < nbytes ? z[byte0 + i] : 0u);
-#pragma unroll
-        for (uint32_t s = 0; s < 32; s++) {
-            const uint64_t x = s ? (hi << s) | (lo >> (64 - s)) : hi;
-            const uint64_t v = x >> 16;
-            const uint64_t bit = byte0 * 8 + s;
-            if ((v == DC_MAGIC_BLOCK || v == DC_MAGIC_EOS) && bit >= 32 && bit + 48 <= nbytes * 8) {
-                const uint32_t k = atomicAdd(n_found, 1u);
-                if (k < cap) found[k] = (bit << 1) | (v == DC_MAGIC_EOS ? 1u : 0u);
-            }
-        }
-    }
-}
 
 // ---- decode ---------------------------------------------------------------------------------------------------
 // Wave-uniform bit reader over big-endian 32-bit words: every lane keeps one word of a 64-word window.
@@ -137,13 +109,11 @@ __device__ static void dc_make_tables(uint32_t t, uint32_t alpha)
     d_minlen[t] = minl;
 }
 
-// One wave per block.  Block j starts (its magic) at bit starts[j] of z[0, nbytes), or -- src non-null, the batch --
-// at bit src[j].bit of src[j].z[0, src[j].nbytes).  Outputs: L bytes (B.bwt slab), occ ranks (u32, B.rec_a slab), byte
-// counts (B.freq slab), descriptor: n, crc (stored), orig_ptr, bits = bit after the block's last symbol, status
-// (DC_ERR_* on malformed data).
-__global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uint8_t *__restrict__ z, uint64_t nbytes,
-                                                          const uint64_t *__restrict__ starts,
-                                                          const BzxDcSrc *__restrict__ src, uint32_t max_n)
+// One wave per block.  Block j starts (its magic) at bit src[j].bit of src[j].z[0, src[j].nbytes).  Outputs: L bytes
+// (B.bwt slab), occ ranks (u32, B.rec_a slab), byte counts (B.freq slab), descriptor: n (at most BZX_MAX_N; the host
+// holds it against 100000 * level of the block's stream), crc (stored), orig_ptr, bits = bit after the block's last
+// symbol, status (DC_ERR_* on malformed data).
+__global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const BzxDcSrc *__restrict__ src)
 {
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
     if (b >= B.nblk) return;
@@ -151,16 +121,9 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
     uint8_t *__restrict__ L = B.bwt + (size_t)b * BZX_BLK_STRIDE;
     uint32_t *__restrict__ OCC = reinterpret_cast<uint32_t *>(B.rec_a + (size_t)b * BZX_MAX_N);
     uint8_t *__restrict__ SEL = B.selector + (size_t)b * BZX_SEL_STRIDE;
-    uint64_t start = 0;
-    if (src) {
-        z = src[b].z;
-        nbytes = src[b].nbytes;
-        start = src[b].bit;
-    } else {
-        start = starts[b];
-    }
+    const uint64_t start = src[b].bit;
     DcBits br;
-    br.init(z, nbytes, start + 48);
+    br.init(src[b].z, src[b].nbytes, start + 48);
     uint32_t err = 0;
     const uint32_t crc = br.get(32);
     const uint32_t randomised = br.get(1);
@@ -283,14 +246,14 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
         if (sym <= 1) {                       // RUNA / RUNB
             run += (sym + 1) * run_w;
             run_w <<= 1;
-            if (run > max_n) {
+            if (run > BZX_MAX_N) {
                 err |= DC_ERR_DATA;
                 break;
             }
             continue;
         }
         if (run) {
-            if (n + run > max_n) {
+            if (n + run > BZX_MAX_N) {
                 err |= DC_ERR_DATA;
                 break;
             }
@@ -299,7 +262,7 @@ __global__ __launch_bounds__(64) void bzx_dc_decode_kernel(BzxBatch B, const uin
             run_w = 1;
         }
         if (sym == eob) break;
-        if (n + 1 > max_n) {
+        if (n + 1 > BZX_MAX_N) {
             err |= DC_ERR_DATA;
             break;
         }
@@ -472,15 +435,22 @@ __global__ __launch_bounds__(64) void bzx_dc_expand_kernel(BzxBatch B, const uin
     }
 }
 
-static void bzx_launch_dc_scan(const uint8_t *z, uint64_t nbytes, uint64_t *found, uint32_t *n_found, uint32_t cap,
-                               uint32_t grid, hipStream_t stream)
+// ---- CRC-32/BZIP2 of every block the expansion placed (bzx_crc_range, bzx_rle1.h) -----------------------------------
+__global__ __launch_bounds__(CRC_NT) void bzx_dc_crc_kernel(BzxBatch B, const BzxDcDst *__restrict__ dst,
+                                                            uint32_t *__restrict__ got)
 {
-    hipLaunchKernelGGL(bzx_dc_scan_kernel, dim3(grid), dim3(256), 0, stream, z, nbytes, found, n_found, cap);
+    __shared__ BzxCrcLds lds;
+    const uint32_t my_weight = bzx_crc_setup(lds);
+    for (uint32_t b = blockIdx.x; b < B.nblk; b += gridDim.x) {
+        if (B.blk[b].status || !dst[b].p) continue;          // (uniform over the workgroup)
+        const uint32_t crc = bzx_crc_range(dst[b].p, 0, B.blk[b].pack_word, lds, my_weight);
+        if (threadIdx.x == 0) got[b] = crc;
+    }
 }
-void bzx_launch_dc_decode(const BzxBatch &B, const uint8_t *z, uint64_t nbytes, const uint64_t *starts,
-                          const BzxDcSrc *src, uint32_t max_n, hipStream_t stream)
+
+void bzx_launch_dc_decode(const BzxBatch &B, const BzxDcSrc *src, hipStream_t stream)
 {
-    hipLaunchKernelGGL(bzx_dc_decode_kernel, dim3(B.nblk), dim3(64), 0, stream, B, z, nbytes, starts, src, max_n);
+    hipLaunchKernelGGL(bzx_dc_decode_kernel, dim3(B.nblk), dim3(64), 0, stream, B, src);
 }
 void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream)
 {
@@ -492,257 +462,7 @@ void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const Bzx
 {
     hipLaunchKernelGGL(bzx_dc_expand_kernel, dim3((DC_CK_STRIDE + 63) / 64, B.nblk), dim3(64), 0, stream, B, img_slabs, dst);
 }
-
-// ---- host side (include/bzx.h: bzx_decompress_*) ------------------------------------------------------------------
-#define DC_MAX_FOUND 262144u
-
-// One bzip2 stream at the start of d_bz2[0..len); *consumed = bytes up to and including its footer.
-static int decompress_one(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len, size_t *consumed)
+void bzx_launch_dc_crc(const BzxBatch &B, const BzxDcDst *dst, uint32_t *got, uint32_t n_cu, hipStream_t stream)
 {
-    *consumed = 0;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    *out_len = 0;
-    const uint8_t *z = (const uint8_t *)d_bz2;
-    uint8_t head[4] = {0, 0, 0, 0};
-    if (len < 14) {
-        ctx->err = "shorter than the smallest bzip2 stream";
-        return BZX_E_DATA;
-    }
-    HIP_TRY(ctx, hipMemcpy(head, z, 4, hipMemcpyDeviceToHost));
-    if (head[0] != 'B' || head[1] != 'Z' || head[2] != 'h' || head[3] < '1' || head[3] > '9') {
-        ctx->err = "no BZh1..BZh9 header";
-        return BZX_E_DATA;
-    }
-    const uint32_t max_n = 100000u * (uint32_t)(head[3] - '0');
-    // ---- scan for block / end-of-stream magics at every bit offset
-    void *scratch = nullptr;
-    int rc = bzx_ctx_split_scratch(ctx, (size_t)DC_MAX_FOUND * 8 * 5 + 4096, &scratch);
-    if (rc) return rc;
-    uint64_t *d_found = (uint64_t *)scratch;
-    uint64_t *d_starts = d_found + DC_MAX_FOUND;
-    uint64_t *d_off = d_starts + DC_MAX_FOUND;
-    BzxDcDst *d_dst = (BzxDcDst *)(d_off + DC_MAX_FOUND);
-    uint32_t *d_nfound = (uint32_t *)(d_dst + DC_MAX_FOUND);
-    HIP_TRY(ctx, hipMemsetAsync(d_nfound, 0, 64, ctx->stream));
-    bzx_launch_dc_scan(z, len, d_found, d_nfound, DC_MAX_FOUND, (uint32_t)ctx->n_cu * 8, ctx->stream);
-    uint32_t nfound = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&nfound, d_nfound, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (nfound > DC_MAX_FOUND) {
-        ctx->err = "too many block-magic candidates";
-        return BZX_E_DATA;
-    }
-    std::vector<uint64_t> found, starts;
-    try {
-        found.resize(nfound);
-        if (nfound) HIP_TRY(ctx, hipMemcpy(found.data(), d_found, (size_t)nfound * 8, hipMemcpyDeviceToHost));
-        std::sort(found.begin(), found.end());
-        for (uint64_t f : found)
-            if (!(f & 1u)) starts.push_back(f >> 1);
-    } catch (const std::bad_alloc &) {
-        return BZX_E_NOMEM;
-    }
-    auto is_eos = [&](uint64_t bit) { return std::binary_search(found.begin(), found.end(), (bit << 1) | 1u); };
-    // ---- decode every candidate; keep the chain that starts at bit 32 (a chance match of the magic inside compressed
-    // data does not continue the chain: drop it and decode again without it)
-    uint64_t end_bit = 32;
-    uint32_t nblk = 0;
-    for (int attempt = 0;; attempt++) {
-        nblk = (uint32_t)starts.size();
-        end_bit = 32;
-        if (nblk == 0) break;
-        if ((rc = ensure_blocks(ctx, nblk))) return rc;
-        BzxBatch &B = ctx->B;
-        B.nblk = nblk;
-        B.blk_first = 0;
-        B.blk_step = 1;
-        HIP_TRY(ctx, hipMemcpyAsync(d_starts, starts.data(), (size_t)nblk * 8, hipMemcpyHostToDevice, ctx->stream));
-        bzx_launch_dc_decode(B, z, len, d_starts, nullptr, max_n, ctx->stream);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, (size_t)nblk * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<uint64_t> chain;
-        bool clean = true;
-        uint32_t i = 0;
-        while (i < nblk) {
-            if (starts[i] != end_bit) {             // not where the previous block ended: a chance match
-                clean = false;
-                i++;
-                continue;
-            }
-            if (ctx->h_blk[i].status & BZX_ST_DC_RANDOMISED) {
-                ctx->err = "randomised block (written by bzip2 0.9.0 or older): not supported";
-                return BZX_E_DATA;
-            }
-            if (ctx->h_blk[i].status) {
-                ctx->err = "damaged block in the bzip2 stream";
-                return BZX_E_DATA;
-            }
-            chain.push_back(starts[i]);
-            end_bit = ctx->h_blk[i].bits;
-            i++;
-        }
-        if (clean) break;
-        if (attempt >= 3) {
-            ctx->err = "cannot follow the chain of blocks";
-            return BZX_E_DATA;
-        }
-        starts.swap(chain);
-    }
-    if (!is_eos(end_bit)) {
-        ctx->err = "blocks do not end at an end-of-stream marker";
-        return BZX_E_DATA;
-    }
-    uint8_t foot[16] = {0};
-    {
-        const size_t fb = (size_t)((end_bit + 48) >> 3);
-        const size_t nfb = len - fb < 5 ? len - fb : 5;
-        if ((end_bit + 80 + 7) / 8 > len) {
-            ctx->err = "truncated after the end-of-stream marker";
-            return BZX_E_DATA;
-        }
-        HIP_TRY(ctx, hipMemcpy(foot, z + fb, nfb, hipMemcpyDeviceToHost));
-    }
-    uint64_t fv = 0;
-    for (int i = 0; i < 5; i++) fv = (fv << 8) | foot[i];
-    const uint32_t stream_crc = (uint32_t)((fv << ((end_bit + 48) & 7u)) >> 8);
-    uint64_t total = 0;
-    uint32_t comb = 0;
-    if (nblk) {
-        BzxBatch &B = ctx->B;
-        // ---- inverse BWT, expanded sizes, offsets
-        bzx_launch_dc_ibwt(B, ctx->d_in, ctx->stream);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, (size_t)nblk * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<uint64_t> off;
-        try {
-            off.resize((size_t)nblk + 1);
-        } catch (const std::bad_alloc &) {
-            return BZX_E_NOMEM;
-        }
-        for (uint32_t b = 0; b < nblk; b++) {
-            if (ctx->h_blk[b].status) {
-                ctx->err = "damaged block in the bzip2 stream (inverse BWT)";
-                return BZX_E_DATA;
-            }
-            off[b] = total;
-            total += ctx->h_blk[b].pack_word;
-            comb = ((comb << 1) | (comb >> 31)) ^ ctx->h_blk[b].crc;       // stored CRCs (crc.rs:25-27)
-        }
-        off[nblk] = total;
-        *out_len = (size_t)total;
-        if (total > cap) {
-            ctx->err = "output buffer too small for the decompressed data";
-            return BZX_E_OUTBUF;
-        }
-        std::vector<BzxDcDst> dst(nblk);
-        for (uint32_t b = 0; b < nblk; b++) dst[b] = BzxDcDst{(uint8_t *)d_out + off[b], total - off[b]};
-        HIP_TRY(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)nblk + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_dst, dst.data(), (size_t)nblk * sizeof(BzxDcDst), hipMemcpyHostToDevice, ctx->stream));
-        bzx_launch_dc_expand(B, ctx->d_in, d_dst, ctx->stream);
-        // ---- block CRCs of the output (the compressor's CRC kernel), against the stored ones
-        std::vector<uint32_t> stored(nblk);
-        for (uint32_t b = 0; b < nblk; b++) stored[b] = ctx->h_blk[b].crc;
-        HIP_TRY(ctx, hipMemcpyAsync(d_nfound, &nblk, 4, hipMemcpyHostToDevice, ctx->stream));
-        bzx_launch_block_crcs(ctx, (const uint8_t *)d_out, d_off, d_nfound, B.blk, nblk);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, (size_t)nblk * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipGetLastError());
-        for (uint32_t b = 0; b < nblk; b++) {
-            if (ctx->h_blk[b].crc != stored[b]) {
-                ctx->err = "block CRC mismatch in block " + std::to_string(b);
-                return BZX_E_DATA;
-            }
-        }
-    }
-    if (comb != stream_crc) {
-        ctx->err = "combined CRC mismatch";
-        return BZX_E_DATA;
-    }
-    *out_len = (size_t)total;
-    *consumed = (size_t)((end_bit + 80 + 7) / 8);
-    ctx->stats.nblk = nblk;
-    ctx->stats_batch = false;
-    ctx->stats.raw_bytes = total;
-    return BZX_OK;
-}
-
-// true when another stream header (BZh1..BZh9) starts at d_bz2[at]
-static bool stream_follows(bzx_ctx *ctx, const void *d_bz2, size_t len, size_t at)
-{
-    uint8_t h[4] = {0, 0, 0, 0};
-    if (at + 14 > len) return false;
-    if (hipMemcpy(h, (const uint8_t *)d_bz2 + at, 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    return h[0] == 'B' && h[1] == 'Z' && h[2] == 'h' && h[3] >= '1' && h[3] <= '9';
-}
-
-// Device buffer -> device buffer: ONE stream (the reference's decompress() also stops at the first footer,
-// decompress.rs:81-95).  Bytes behind the footer that are not another stream are ignored, as bzip2 does ("trailing
-// garbage"); a concatenated .bz2 (pbzip2 output, cat a.bz2 b.bz2) is refused here rather than decoded in part --
-// bzx_decompress_buffer decodes every stream of it.
-extern "C" int bzx_decompress_device(bzx_ctx *ctx, const void *d_bz2, size_t len, void *d_out, size_t cap, size_t *out_len)
-{
-    auto api_lock_ = ctx_lock(ctx);
-    BZX_REFUSE_WHILE_STREAMING(ctx);
-    if (!ctx || !d_bz2 || !out_len || (cap && !d_out) || ((uintptr_t)d_out & 15u)) return BZX_E_PARAM;
-    size_t used = 0;
-    const int rc = decompress_one(ctx, d_bz2, len, d_out, cap, out_len, &used);
-    if (rc == BZX_OK && stream_follows(ctx, d_bz2, len, used)) {
-        ctx->err = "another bzip2 stream follows the first (concatenated .bz2): bzx_decompress_buffer decodes all of them";
-        return BZX_E_DATA;
-    }
-    return rc;
-}
-
-extern "C" int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len)
-{
-    auto api_lock_ = ctx_lock(ctx);
-    BZX_REFUSE_WHILE_STREAMING(ctx);
-    if (!ctx || !bz2 || !out_len || (cap && !out)) return BZX_E_PARAM;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void *d_z = nullptr, *d_o = nullptr;
-    if (hipMalloc(&d_z, len + 64) != hipSuccess) return BZX_E_NOMEM;
-    if (hipMalloc(&d_o, cap + 64) != hipSuccess) {
-        (void)hipFree(d_z);
-        return BZX_E_NOMEM;
-    }
-    int rc = hipMemcpyAsync(d_z, bz2, len, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? BZX_OK : BZX_E_HIP;
-    // every stream of a concatenated .bz2, one after the other (each stream starts on a byte boundary)
-    size_t at = 0, total = 0;
-    uint32_t nblk_all = 0;
-    *out_len = 0;
-    void *d_z2 = nullptr;                          // a later stream, moved to an aligned start (the kernels read words)
-    while (!rc) {
-        size_t n = 0, used = 0;
-        const void *src = d_z;
-        if (at) {
-            if (!d_z2 && hipMalloc(&d_z2, len + 64) != hipSuccess) {
-                rc = BZX_E_NOMEM;
-                break;
-            }
-            if (hipMemcpyAsync(d_z2, (const uint8_t *)d_z + at, len - at, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
-                rc = BZX_E_HIP;
-                break;
-            }
-            src = d_z2;
-        }
-        rc = decompress_one(ctx, src, len - at, d_o, cap - total, &n, &used);
-        if (rc == BZX_E_OUTBUF) *out_len = total + n;          // (a lower bound when streams remain)
-        if (rc) break;
-        if (n && hipMemcpy(out + total, d_o, n, hipMemcpyDeviceToHost) != hipSuccess) rc = BZX_E_HIP;
-        total += n;
-        nblk_all += ctx->stats.nblk;
-        at += used;
-        *out_len = total;
-        if (!stream_follows(ctx, d_z, len, at)) break;
-    }
-    if (!rc) {
-        ctx->stats.nblk = nblk_all;
-        ctx->stats_batch = false;
-        ctx->stats.raw_bytes = total;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_z);
-    if (d_z2) (void)hipFree(d_z2);
-    (void)hipFree(d_o);
-    return rc;
+    hipLaunchKernelGGL(bzx_dc_crc_kernel, dim3(B.nblk < n_cu ? B.nblk : n_cu), dim3(CRC_NT), 0, stream, B, dst, got);
 }

@@ -22,6 +22,11 @@
 #define BZX_ST_REDO 2u             // the split kernel handed the block to the general sorter, to be sorted from scratch
 #define BZX_ST_RESUME 4u           // a bucket gave up (deep repeats): the general sorter finishes the leftover groups
 #define BZX_ST_DC_RANDOMISED 0x400u   // decompression: the block has its randomised bit set (not decoded, bzx.h)
+#define DC_ERR_HEADER 0x100u       // decompression: BzxBlock.status bits set by the block decoder on malformed data
+#define DC_ERR_DATA 0x200u
+#define DC_SKIP 0x800u             // ... set by the chain walk: off the chain, or its input is refused (the later kernels skip it)
+#define DC_MAGIC_BLOCK 0x314159265359ull   // the 48 bits in front of every block
+#define DC_MAGIC_EOS 0x177245385090ull     // ... and in front of the stored combined CRC (end of stream)
 // Rank rounds of the bucket sorter (bzx_bsort.hip): round r compares the ranks h and 2h symbols ahead, h = (give-up
 // depth of the block) * 3^r, and leaves the depth at 3h.
 #ifndef RK_ROUNDS

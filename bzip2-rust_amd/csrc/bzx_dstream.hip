@@ -25,7 +25,7 @@
 //                         the round their places in a staging area and cuts after the last block that fits (a block
 //                         expands to at most 46.62 MB: every pass places at least one); blocks that did not fit stay
 //                         decoded in their slabs for the next pass.  Expand (bzx_dc_expand_kernel through BzxDcDst),
-//                         block CRCs (bzx_crc_range), bzx_ds_verdict_kernel compares them with the stored ones and
+//                         block CRCs (bzx_dc_crc_kernel), bzx_ds_verdict_kernel compares them with the stored ones and
 //                         leaves ONE fixed-size record for the host.                          [1 synchronisation]
 //                         The first pass of a round is enqueued behind its decode/chain/inverse BWT without a
 //                         synchronisation in between: a round whose output fits one staging area costs one.
@@ -38,12 +38,8 @@
 #include <algorithm>
 #include <new>
 #include "bzx_host.h"
-#include "bzx_rle1.h"
 #include "bzx_wg.h"
 
-#define DS_MAGIC_BLOCK 0x314159265359ull
-#define DS_MAGIC_EOS 0x177245385090ull
-#define DS_SKIP 0x800u                       // BzxBlock.status: off the chain or behind its stop (later kernels skip it)
 #define DS_BLOCK_BOUND 2400000ull            // bytes: no legal block image is longer (18,002 x 50 x 20 bits + tables)
 #define DS_CARRY_MAX (DS_BLOCK_BOUND + 4096) // gap in front of the accepted bytes: room for the longest carry
 #define DS_STAGE_BYTES ((size_t)48 << 20)    // output staging area: at least one expanded block (46.62 MB)
@@ -51,7 +47,6 @@
 #define DS_DEF_CHUNK ((size_t)128 << 20)
 
 enum { DS_STOP_GO = 0, DS_STOP_NOMAGIC, DS_STOP_WITHHELD, DS_STOP_END, DS_STOP_ERROR };
-enum { DS_ERR_RANDOMISED = 1, DS_ERR_DAMAGED, DS_ERR_TRUNC_EOS, DS_ERR_COMBINED };
 
 struct DsRec {                     // what the host reads of a pass (device -> page-locked host), fixed size
     uint64_t chain_bit;            // chain: where it stands after the round (bit of the whole input)
@@ -62,7 +57,7 @@ struct DsRec {                     // what the host reads of a pass (device -> p
     uint32_t comb;                 // chain: running combined CRC of the open stream
     uint32_t level;                // chain: level of the open stream
     uint32_t stop;                 // chain: DS_STOP_*
-    uint32_t err;                  // chain: DS_ERR_* behind the last chain block (stop == DS_STOP_ERROR)
+    uint32_t err;                  // chain: DcWhy behind the last chain block (stop == DS_STOP_ERROR)
     uint32_t pass_j0;              // layout: first chain block of this pass
     uint32_t placed;               // layout: chain blocks placed so far (this pass included)
     uint32_t lay_err;              // layout: the next chain block failed its inverse BWT
@@ -76,22 +71,11 @@ __global__ __launch_bounds__(256) void bzx_ds_scan_kernel(const uint8_t *__restr
 {
     const uint64_t nwords = (to - from + 3) / 4;
     for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t byte0 = from + w * 4;
-        uint64_t hi = 0, lo = 0;                            // bytes byte0 .. byte0+15, big-endian
-#pragma unroll
-        for (int i = 0; i < 8; i++) hi = (hi << 8) | (byte0 + i < wlen ? z[byte0 + i] : 0u);
-#pragma unroll
-        for (int i = 8; i < 16; i++) lo = (lo << 8) | (byte0 + i < wlen ? z[byte0 + i] : 0u);
-#pragma unroll
-        for (uint32_t s = 0; s < 32; s++) {
-            const uint64_t x = s ? (hi << s) | (lo >> (64 - s)) : hi;
-            const uint64_t v = x >> 16;
-            const uint64_t bit = byte0 * 8 + s;
-            if ((v == DS_MAGIC_BLOCK || v == DS_MAGIC_EOS) && bit < to * 8 && bit + 48 <= wlen * 8) {
-                const uint32_t k = atomicAdd(n_found, 1u);
-                if (k < cap) found[k] = ((base_bit + bit) << 1) | (v == DS_MAGIC_EOS ? 1u : 0u);
-            }
-        }
+        bzx_dc_scan_word(z, wlen, from + w * 4, [&](uint64_t bit, bool eos, uint64_t, uint64_t) {
+            if (bit >= to * 8) return;
+            const uint32_t k = atomicAdd(n_found, 1u);
+            if (k < cap) found[k] = ((base_bit + bit) << 1) | (eos ? 1u : 0u);
+        });
     }
 }
 
@@ -153,18 +137,18 @@ __global__ __launch_bounds__(64) void bzx_ds_chain_kernel(BzxBatch B, const uint
                 }
                 if (st_i & BZX_ST_DC_RANDOMISED) {
                     stop = DS_STOP_ERROR;
-                    err = DS_ERR_RANDOMISED;
+                    err = DC_WHY_RANDOMISED;
                     break;
                 }
                 if (st_i || ran_off || n_i > 100000u * level) {
                     stop = DS_STOP_ERROR;
-                    err = DS_ERR_DAMAGED;
+                    err = DC_WHY_DAMAGED;
                     break;
                 }
                 if (lane == i) mine_on_chain = true;
                 if (lane == 0) chain[nch] = slab_i;
                 nch++;
-                comb = ((comb << 1) | (comb >> 31)) ^ crc_i;              // stored CRCs (crc.rs:25-27)
+                comb = crc_fold(comb, crc_i);                             // stored CRCs
                 at_bit = base_bit + end_i;
             } else {
                 const uint64_t after = (rel + 80 + 7) / 8;                // first byte behind the footer
@@ -174,7 +158,7 @@ __global__ __launch_bounds__(64) void bzx_ds_chain_kernel(BzxBatch B, const uint
                 }
                 if (rel + 80 > wbits) {
                     stop = DS_STOP_ERROR;
-                    err = DS_ERR_TRUNC_EOS;
+                    err = DC_WHY_TRUNC_EOS;
                     break;
                 }
                 const uint64_t fb = (rel + 48) >> 3;
@@ -183,15 +167,14 @@ __global__ __launch_bounds__(64) void bzx_ds_chain_kernel(BzxBatch B, const uint
                 const uint32_t stored = (uint32_t)((fv << ((rel + 48) & 7u)) >> 8);
                 if (stored != comb) {
                     stop = DS_STOP_ERROR;
-                    err = DS_ERR_COMBINED;
+                    err = DC_WHY_COMBINED_CRC;
                     break;
                 }
                 streams++;
                 comb = 0;
-                const uint32_t lv = ds_byte(z, wlen, after + 3);
-                if (after + 14 <= wlen && ds_byte(z, wlen, after) == 'B' && ds_byte(z, wlen, after + 1) == 'Z' &&
-                    ds_byte(z, wlen, after + 2) == 'h' && lv >= '1' && lv <= '9') {
-                    level = lv - '0';
+                const uint32_t next = after + 14 <= wlen ? bzx_bzh_level(z + after) : 0u;
+                if (next) {
+                    level = next;
                     at_bit = base_bit + after * 8 + 32;
                 } else {
                     at_bit = base_bit + after * 8;
@@ -199,7 +182,7 @@ __global__ __launch_bounds__(64) void bzx_ds_chain_kernel(BzxBatch B, const uint
                 }
             }
         }
-        if (isblk && !mine_on_chain) B.blk[slab].status = st | DS_SKIP;
+        if (isblk && !mine_on_chain) B.blk[slab].status = st | DC_SKIP;
         nblk_before += (uint32_t)__popcll(blks);
     }
     if (lane == 0) {
@@ -241,11 +224,7 @@ __global__ __launch_bounds__(64) void bzx_ds_layout_kernel(BzxBatch B, const uin
         const uint32_t b = valid ? chain[j] : 0u;
         const uint64_t size = valid ? B.blk[b].pack_word : 0ull;
         const uint32_t bad = (valid && B.blk[b].status) ? 1u : 0u;
-        uint64_t x = size;                             // inclusive scan of the expanded sizes over the wave
-        for (uint32_t k = 1; k < 64; k <<= 1) {
-            const uint64_t y = __shfl_up(x, k);
-            if (lane >= k) x += y;
-        }
+        const uint64_t x = bzx_wave_incl_sum64(size);  // inclusive scan of the expanded sizes over the wave
         const bool fits = valid && !bad && off + x <= stage_cap;
         const unsigned long long nf = __ballot(valid && !fits);
         const uint32_t cnt = nch - base < 64u ? nch - base : 64u;
@@ -266,19 +245,6 @@ __global__ __launch_bounds__(64) void bzx_ds_layout_kernel(BzxBatch B, const uin
         rec->placed = placed;
         rec->bytes = off;
         rec->lay_err = lay_err;
-    }
-}
-
-// ---- CRC-32/BZIP2 of every block placed by the pass (bzx_crc_range, bzx_rle1.h) -----------------------------------
-__global__ __launch_bounds__(CRC_NT) void bzx_ds_crc_kernel(BzxBatch B, const BzxDcDst *__restrict__ dst,
-                                                            uint32_t *__restrict__ got)
-{
-    __shared__ BzxCrcLds lds;
-    const uint32_t my_weight = bzx_crc_setup(lds);
-    for (uint32_t b = blockIdx.x; b < B.nblk; b += gridDim.x) {
-        if (B.blk[b].status || !dst[b].p) continue;          // (uniform over the workgroup)
-        const uint32_t crc = bzx_crc_range(dst[b].p, 0, B.blk[b].pack_word, lds, my_weight);
-        if (threadIdx.x == 0) got[b] = crc;
     }
 }
 
@@ -510,7 +476,7 @@ static void ds_no_magic(bzx_dstream *s, bool used_up)
         return;
     }
     if (rel + 48 > s->wlen * 8 && !s->wfinal) s->need_more = true;
-    else ds_fail(s, "blocks do not end at an end-of-stream marker");
+    else ds_fail(s, dc_why_text(DC_WHY_NO_EOS));
 }
 
 static void ds_round_complete(bzx_dstream *s)
@@ -534,10 +500,7 @@ static void ds_round_complete(bzx_dstream *s)
         s->finished = true;
         break;
     default:
-        ds_fail(s, r.err == DS_ERR_RANDOMISED  ? "randomised block (written by bzip2 0.9.0 or older): not supported"
-                   : r.err == DS_ERR_TRUNC_EOS ? "truncated after the end-of-stream marker"
-                   : r.err == DS_ERR_COMBINED  ? "combined CRC mismatch"
-                                               : "damaged block in the bzip2 stream");
+        ds_fail(s, dc_why_text(r.err));
     }
 }
 
@@ -575,7 +538,7 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
         (void)hipEventRecord(ctx->ev[5], st);
         if (nb) {
             HIP_TRY(ctx, hipMemcpyAsync(s->d_src, s->h_src, nb * sizeof(BzxDcSrc), hipMemcpyHostToDevice, st));
-            bzx_launch_dc_decode(B, nullptr, 0, nullptr, s->d_src, BZX_MAX_N, st);
+            bzx_launch_dc_decode(B, s->d_src, st);
         }
         hipLaunchKernelGGL(bzx_ds_chain_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8,
                            s->wfinal ? 1u : 0u, s->d_cand, c0, c1, s->chain_bit, s->comb, s->level, s->d_chain, s->d_rec);
@@ -591,8 +554,7 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
         hipLaunchKernelGGL(bzx_ds_layout_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_stage[q],
                            (uint64_t)DS_STAGE_BYTES, s->d_dst, s->d_rec);
         bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
-        hipLaunchKernelGGL(bzx_ds_crc_kernel, dim3(nb < (uint32_t)ctx->n_cu ? nb : (uint32_t)ctx->n_cu), dim3(CRC_NT), 0, st, B,
-                           s->d_dst, s->d_got);
+        bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
         hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_dst, s->d_got, s->d_stage[q],
                            s->d_rec);
     }
@@ -619,11 +581,11 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
     const uint32_t first_blk = s->info.nblk;
     s->info.nblk += r.good;
     if (r.good < r.placed - r.pass_j0) {
-        ds_fail(s, "block CRC mismatch in block " + std::to_string(first_blk + r.good));
+        ds_fail(s, dc_why_text(DC_WHY_BLOCK_CRC, first_blk + r.good));
         return BZX_OK;
     }
     if (r.placed < r.nchain && r.lay_err) {
-        ds_fail(s, "damaged block in the bzip2 stream (inverse BWT)");
+        ds_fail(s, dc_why_text(DC_WHY_IBWT));
         return BZX_OK;
     }
     if (r.placed >= r.nchain) ds_round_complete(s);
@@ -665,11 +627,10 @@ static int ds_promote(bzx_dstream *s)
     if (!s->started) {
         s->started = true;
         if (s->wlen < 14) {
-            ds_fail(s, "shorter than the smallest bzip2 stream");
-        } else if (s->head[0] != 'B' || s->head[1] != 'Z' || s->head[2] != 'h' || s->head[3] < '1' || s->head[3] > '9') {
-            ds_fail(s, "no BZh1..BZh9 header");
+            ds_fail(s, dc_why_text(DC_WHY_SHORT));
+        } else if (!(s->level = bzx_bzh_level(s->head))) {
+            ds_fail(s, dc_why_text(DC_WHY_NO_HEADER));
         } else {
-            s->level = (uint32_t)(s->head[3] - '0');
             s->chain_bit = 32;
             s->comb = 0;
         }

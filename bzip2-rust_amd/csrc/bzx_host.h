@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "../../include/bzx.h"
+#include "bzx_dc.h"
 #include "bzx_device.h"
 
 struct BlockReq {
@@ -78,7 +79,8 @@ struct bzx_ctx {
     void *batch_ws = nullptr;
     size_t batch_ws_bytes = 0;
     hipEvent_t ev_bt[3] = {nullptr, nullptr, nullptr};   // round: before its split part, before emit, after framing
-    bool stats_batch = false;        // the stats describe a batch call: no per-block figures (bzx_get_block_info)
+    bool stats_batch = false;        // the stats describe a batch call or a decompression: no per-block figures
+                                     // (bzx_get_block_info)
 
     // batched decompression (bzx_decompress_batch_*): device tables and pinned host mirrors, grown on demand
     void *dbatch_ws = nullptr;
@@ -140,7 +142,7 @@ void fold_blocks(bzx_stats &st, const BzxBlock *blk, uint32_t first, uint32_t en
 size_t cstream_max_carry(int level);            // longest withheld raw tail of a chunk
 void stream_write_footer(uint8_t *out, uint64_t end, size_t need, uint32_t crc_comb);
 // combined CRC of a stream after one more block (crc.rs:25-27)
-static inline uint32_t crc_fold(uint32_t comb, uint32_t crc) { return ((comb << 1) | (comb >> 31)) ^ crc; }
+__host__ __device__ static inline uint32_t crc_fold(uint32_t comb, uint32_t crc) { return ((comb << 1) | (comb >> 31)) ^ crc; }
 
 // ---- bzx_mdev.hip: shift of a finished chunk to its bit phase
 void bzx_launch_shift_bits(const uint32_t *d_in, uint32_t n_words, uint32_t p, uint32_t *d_out, uint32_t n_cu,
@@ -186,8 +188,8 @@ void bzx_launch_block_crcs(bzx_ctx *ctx, const uint8_t *d_raw, const uint64_t *d
 void bzx_split_scan(hipStream_t st, uint64_t *v, uint64_t n, int is_max, uint64_t *segtot);
 uint64_t bzx_split_scan_words(uint64_t n);
 
-// ---- bzx_decomp.hip: the decoder's kernels (one stream, and the batch of bzx_dbatch.hip)
-void bzx_launch_dc_decode(const BzxBatch &B, const uint8_t *z, uint64_t nbytes, const uint64_t *starts,
-                          const BzxDcSrc *src, uint32_t max_n, hipStream_t stream);
+// ---- bzx_decomp.hip: the decoder's kernels, over any set of blocks (one-shot and batch: bzx_dbatch.hip; bzx_dstream.hip)
+void bzx_launch_dc_decode(const BzxBatch &B, const BzxDcSrc *src, hipStream_t stream);
 void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream);
 void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const BzxDcDst *dst, hipStream_t stream);
+void bzx_launch_dc_crc(const BzxBatch &B, const BzxDcDst *dst, uint32_t *got, uint32_t n_cu, hipStream_t stream);

@@ -168,6 +168,16 @@ __device__ __forceinline__ uint32_t bzx_wave_incl_sum(uint32_t v)
     return v;
 }
 
+// ... of 64-bit values (byte offsets; off the hot path: six shuffles, DPP moves are 32 bits wide).
+__device__ __forceinline__ uint64_t bzx_wave_incl_sum64(uint64_t v)
+{
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint64_t y = __shfl_up(v, d);
+        if (bzx_lane() >= d) v += y;
+    }
+    return v;
+}
+
 // Wave inclusive max scan.
 __device__ __forceinline__ uint32_t bzx_wave_incl_max(uint32_t v)
 {

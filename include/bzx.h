@@ -227,14 +227,24 @@ void bzx_host_free(void *p);
  * Decompression on the device (replaces decompress(), decompress.rs:38-404 minus file I/O; bwt_decode
  * bwt_sort.rs:91-130, rle2_mtf_decode_fast rle2_mtf.rs:191-287, rle1_decode rle1.rs:267-316): one .bz2 stream ->
  * raw bytes; every block CRC and the combined CRC are verified (a mismatch is BZX_E_DATA, unlike the reference, which
- * logs it and continues, decompress.rs:379-386).  The blocks of the stream are decoded side by side.
+ * logs it and continues, decompress.rs:379-386).  The blocks of the input are decoded side by side.
  * _device: d_bz2 / d_out are DEVICE pointers (d_out 16-byte aligned); _buffer: host pointers.
  * _device decodes ONE stream: bytes after its end-of-stream marker are ignored unless they begin another stream
- * ("BZh1".."BZh9"), which is refused with BZX_E_DATA (a concatenated .bz2 is not decoded in part).  _buffer decodes
- * every stream of a concatenated .bz2, one after the other; bytes after the last one that do not begin a stream are
- * ignored.
- * BZX_E_OUTBUF: *out_len = bytes needed by _device; by _buffer, bytes needed by the streams up to and including the
- * one that did not fit -- a lower bound while more streams follow it.
+ * ("BZh1".."BZh9" with at least 14 bytes left), which is refused with BZX_E_DATA "another bzip2 stream follows the
+ * first ..." (a concatenated .bz2 is not decoded in part); a fault of the first stream itself -- damage, a CRC, an
+ * output too small -- is reported in preference.  _buffer decodes every stream of a concatenated .bz2; bytes after
+ * the last one that do not begin a stream are ignored.
+ * Both are bzx_decompress_batch_* with count = 1 (below) and share its rules:
+ *   BZX_E_OUTBUF: *out_len = the exact decoded size of the whole input (all streams of it), nothing is written.
+ *   BZX_E_DATA: *out_len = 0 and out is not written by _buffer, wherever in the input the damage lies (_device may
+ *   have written d_out).  A damaged block CRC is named "block CRC mismatch in block N", N counted over the input.
+ *   No fixed limit on the block-magic candidates of an input (chance matches of the magic in compressed data).
+ *   Memory: the context grows to one block slab (about 28 MB) per block-magic candidate of the whole input, not of
+ *   its longest stream; bzx_dstream_* decodes in bounded device memory.  An allocation that fails is BZX_E_NOMEM and
+ *   the context stays usable.  _buffer holds the input and cap bytes of output on the device for the call and leaves
+ *   no page-locked memory of their size behind.
+ *   bzx_get_stats afterwards: nblk and raw_bytes, summed over the streams; the other fields keep what the last
+ *   compression left.  bzx_get_block_info returns BZX_E_STATE.
  * Accepted streams are those libbz2 1.0.8 accepts -- 2..6 tables, 1..32767 selectors (the first 18002 are used),
  * code lengths 1..20, incomplete prefix codes, RLE1 count bytes 0..255, blocks of up to 100000 * level bytes --
  * with ONE exception: a block whose randomised bit is set (written by bzip2 0.9.0 and older; never by bzip2 >= 0.9.5
@@ -250,7 +260,7 @@ int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t 
  * same bytes and BZX_OK, or BZX_E_DATA -- with its edge rules: an input shorter than 14 bytes or without a BZh1..9
  * header is refused; bytes after a stream that do not begin another stream are ignored; a "BZh<d>" after a stream
  * that does not decode refuses the input; randomised blocks, blocks longer than 100000 * level, selectors outside
- * 1..32767 are refused.  (One difference: there is no fixed limit on the block-magic candidates of an input.)
+ * 1..32767 are refused.
  * Independence: an input's status and bytes do not depend on its neighbours, in the call or in memory; nothing
  * outside [srcs[i], srcs[i] + src_lens[i]) is read.
  * Pointers: d_srcs and d_outs are HOST arrays of count DEVICE pointers.  Inputs may have any alignment; outputs must
@@ -364,7 +374,7 @@ int bzx_get_stats(const bzx_ctx *ctx, bzx_stats *out);
  * call, blocks in stream order (a chunked stream: as many as the context's descriptor table holds, i.e. at least
  * the max_blocks of bzx_ctx_create; BZX_E_PARAM beyond) -- what the reference logs per block at -vvv
  * (src/compression/compress_block.rs:58-63, src/huffman_coding/huffman.rs:176-181).  After a bzx_compress_batch_*
- * call it returns BZX_E_STATE: a batch keeps no per-block figures.
+ * call or any decompression it returns BZX_E_STATE: those keep no per-block figures.
  */
 typedef struct bzx_block_info {
     uint32_t n;               /* RLE1'd bytes in the block */

@@ -1,14 +1,17 @@
-"""Probe (not a test): batched decompression against the one-input decoders, seeded synthetic text at -9.
+"""Probe (not a test): batched decompression, and the one-input calls against the parent commit's; seeded synthetic
+text at -9.
 
-  python tests/gpu_probe_dbatch.py [--reps 3]
+  python tests/gpu_probe_dbatch.py [--reps 3] [--parent-lib PATH/libbzx.so]
 
-Cases: 4096 streams of 64 KiB and 256 streams of 1 MiB (one bzx_decompress_batch_device against a loop of
-bzx_decompress_device over the first 128 / 32 streams, extrapolated to all of them); one file of 64 concatenated
-streams of 256 KiB (count = 1 through bzx_decompress_batch_buffer against bzx_decompress_buffer); one stream of 256 MiB
-(count = 1 against bzx_decompress_device).  The streams are made by the batch compressor.  One context
-(max_blocks = 1024) serves both sides; every shape runs once before it is timed, then the best of --reps; times are
-host clock around calls that end in a device synchronise.  The decoded bytes are checked.  Prints one line per case and
-a JSON line."""
+Cases: 4096 streams of 64 KiB, 256 streams of 1 MiB and one stream of 256 MiB through one
+bzx_decompress_batch_device; one file of 64 concatenated streams of 256 KiB through bzx_decompress_batch_buffer
+(count = 1).  The one-shot calls are the same decoder with count = 1, so on its own the probe only times the batch.
+With --parent-lib (the parent commit built into a second directory) the one-input loops run as well, on that library
+and on this one, alternated with the batch in one process: a loop of bzx_decompress_device over the first 128 / 32 / 1
+streams (extrapolated to all of them), and bzx_decompress_buffer on the concatenated file.  Every library has one
+context of max_blocks = 1024; every shape runs once before it is timed, then the best of --reps; times are host clock
+around calls that end in a device synchronise.  The decoded bytes are checked.  Prints one line per case and a JSON
+line."""
 import argparse
 import ctypes as C
 import json
@@ -26,14 +29,19 @@ from bzx_dbatch_ctypes import DBatchLib  # noqa: E402
 MAX_BLOCKS = 1024
 
 
-def best(fn, reps):
-    fn()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
+def best_of(sides, reps, check):
+    """sides: [(label, fn)].  One checked warm-up each, then reps rounds over all of them in turn; the best times."""
+    for label, fn in sides:
         fn()
-        ts.append(time.perf_counter() - t0)
-    return min(ts)
+        check(label)
+    best = {}
+    for _ in range(reps):
+        for label, fn in sides:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            best[label] = min(best.get(label, dt), dt)
+    return best
 
 
 def compress_all(lib, d_text, count, size):
@@ -47,14 +55,24 @@ def compress_all(lib, d_text, count, size):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--parent-lib", default=None)
     a = ap.parse_args()
     torch.cuda.init()
     oracle = Oracle()
     lib = DBatchLib(max_blocks=MAX_BLOCKS)
-    L = lib.lib
+    parent = DBatchLib(a.parent_lib, max_blocks=MAX_BLOCKS) if a.parent_lib else None
     text = oracle.synthtext(256 << 20, seed=12345)
     d_text = torch.frombuffer(bytearray(text), dtype=torch.uint8).to("cuda")
     results = {}
+
+    def report(name, best, scale=1.0):
+        r = {k + "_ms": v * 1e3 * (scale if k != "batch" else 1.0) for k, v in best.items()}
+        if parent:
+            r["one_shot_over_parent"] = best["one_shot"] / best["parent_one_shot"]
+            r["parent_one_shot_over_batch"] = best["parent_one_shot"] * scale / best["batch"]
+        results[name] = r
+        print(f"{name}: " + ", ".join(f"{k} {v:.2f}" for k, v in r.items()), flush=True)
+
     for name, count, size, loop_n in (("4096x64KiB", 4096, 64 << 10, 128), ("256x1MiB", 256, 1 << 20, 32),
                                       ("1x256MiB", 1, 256 << 20, 1)):
         d_z, offs, olen = compress_all(lib, d_text, count, size)
@@ -67,24 +85,23 @@ def main():
             rc, ol, st = lib.dbatch_device_raw(srcs, olen, outs, caps)
             assert rc == 0, lib.last_error()
 
-        def loop():
-            n = C.c_size_t()
-            for i in range(loop_n):
-                rc = L.bzx_decompress_device(lib.ctx, srcs[i], olen[i], outs[i], caps[i], C.byref(n))
-                assert rc == 0 and n.value == size, lib.last_error()
+        def loop_of(which):
+            def fn():
+                n = C.c_size_t()
+                for i in range(loop_n):
+                    rc = which.lib.bzx_decompress_device(which.ctx, srcs[i], olen[i], outs[i], caps[i], C.byref(n))
+                    assert rc == 0 and n.value == size, which.last_error()
+            return fn
 
-        t_b = best(batch, a.reps)
-        d_out.zero_()
-        batch()
-        assert torch.equal(d_out[:count * size], d_text[:count * size]), name
-        t_l = best(loop, a.reps) * count / loop_n
-        d_out.zero_()
-        loop()
-        assert torch.equal(d_out[:loop_n * size], d_text[:loop_n * size]), name
-        results[name] = dict(batch_ms=t_b * 1e3, loop_ms=t_l * 1e3, loop_extrapolated=loop_n < count,
-                             speedup=t_l / t_b, batch_MBps=count * size / t_b / 1e6)
-        print(f"{name}: batch {t_b * 1e3:.2f} ms, loop {t_l * 1e3:.2f} ms"
-              f"{' (extrapolated from ' + str(loop_n) + ')' if loop_n < count else ''}, {t_l / t_b:.2f}x", flush=True)
+        def check(label):
+            n = (count if label == "batch" else loop_n) * size
+            assert torch.equal(d_out[:n], d_text[:n]), (name, label)
+            d_out.zero_()
+
+        sides = [("batch", batch)] + ([("one_shot", loop_of(lib)), ("parent_one_shot", loop_of(parent))] if parent else [])
+        best = best_of(sides, a.reps, check)
+        report(name, best, count / loop_n)                   # the loops are extrapolated to all streams
+        results[name].update(loop_streams=loop_n, batch_MBps=count * size / best["batch"] / 1e6)
         del d_z, d_out
     # one pbzip2-style file: 64 streams of 256 KiB, concatenated, host buffers on both sides
     size = 256 << 10
@@ -100,20 +117,23 @@ def main():
         rc, ol, st = lib.dbatch_buffer_raw([C.addressof(src)], [len(cat)], [C.addressof(out)], [cap])
         assert rc == 0 and ol == [len(want)], lib.last_error()
 
-    def single():
-        n = C.c_size_t()
-        rc = L.bzx_decompress_buffer(lib.ctx, cat, len(cat), out, cap, C.byref(n))
-        assert rc == 0 and n.value == len(want), lib.last_error()
+    def buffer_of(which):
+        def fn():
+            n = C.c_size_t()
+            rc = which.lib.bzx_decompress_buffer(which.ctx, cat, len(cat), out, cap, C.byref(n))
+            assert rc == 0 and n.value == len(want), which.last_error()
+        return fn
 
-    t_b = best(batch1, a.reps)
-    assert C.string_at(out, len(want)) == want
-    t_s = best(single, a.reps)
-    assert C.string_at(out, len(want)) == want
-    results["1x(64x256KiB concatenated)"] = dict(batch_ms=t_b * 1e3, buffer_ms=t_s * 1e3, speedup=t_s / t_b)
-    print(f"64x256KiB concatenated: batch {t_b * 1e3:.2f} ms, bzx_decompress_buffer {t_s * 1e3:.2f} ms, "
-          f"{t_s / t_b:.2f}x", flush=True)
+    def check1(label):
+        assert C.string_at(out, len(want)) == want, label
+        C.memset(out, 0, cap)
+
+    sides = [("batch", batch1)] + ([("one_shot", buffer_of(lib)), ("parent_one_shot", buffer_of(parent))] if parent else [])
+    report("1x(64x256KiB concatenated)", best_of(sides, a.reps, check1))
     print(json.dumps(results))
     lib.close()
+    if parent:
+        parent.close()
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@ and every case also states which of the two libbz2 must do, so that a writer mis
 
 CPU: the small cases through the fiber emulator (tests/emu).  GPU (-m gpu): every case, at full block sizes."""
 import bz2
+import ctypes as C
 import math
 import os
 import random
@@ -23,7 +24,7 @@ import pytest
 import bz2_writer as W
 from bzx_ctypes import EMU_PATH, ROOT, BzxError, BzxLib
 
-BZX_E_DATA = -7
+BZX_E_OUTBUF, BZX_E_DATA = -4, -7
 
 
 @pytest.fixture(scope="module")
@@ -400,3 +401,61 @@ def test_decode_damage_gpu(bzx, oracle):
     for seed in range(50, 58):
         for label, z, randomised in damaged(oracle, seed):
             judge_damaged(bzx, f"seed {seed}: {label}", z, randomised)
+
+
+# ---- bzx_decompress_device decodes ONE stream: a second one refuses the input, the first one's own faults come first --
+def host_memory(z, cap):
+    """(input pointer, 16-byte aligned output pointer, read(n), keep-alive): the emulator's device memory is host memory."""
+    src, out = C.create_string_buffer(z, len(z)), C.create_string_buffer(cap + 16)
+    p = (C.addressof(out) + 15) // 16 * 16
+    return C.addressof(src), p, lambda n: C.string_at(p, n), (src, out)
+
+
+def torch_memory(z, cap):
+    import torch
+    src = torch.frombuffer(bytearray(z), dtype=torch.uint8).to("cuda")
+    out = torch.zeros(cap + 16, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    return src.data_ptr(), out.data_ptr(), lambda n: out[:n].cpu().numpy().tobytes(), (src, out)
+
+
+def device_one_stream(lib, o, memory):
+    L = lib.lib
+    L.bzx_decompress_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    a, b = W.Block(ptext(o, 900, 300, 51)), W.Block(text(o, 400, 52))
+    za, zb = stream(o, [a], 9), stream(o, [b], 5)
+    assert bz2.decompress(za + zb) == a.raw() + b.raw()
+
+    def run(z, cap=4096):
+        d_z, d_o, read, keep = memory(z, cap)
+        n = C.c_size_t()
+        rc = L.bzx_decompress_device(lib.ctx, d_z, len(z), d_o, cap, C.byref(n))
+        lib._check(rc)
+        return read(n.value)
+
+    assert run(za) == a.raw()
+    assert run(za + b"bytes that begin no stream") == a.raw()
+    with pytest.raises(BzxError) as e:
+        run(za + zb)
+    assert e.value.code == BZX_E_DATA and "another bzip2 stream follows" in str(e.value), str(e.value)
+    # the first stream's own faults take precedence: a damaged stored block CRC, a damaged combined CRC, no room
+    for at, words in ((10, "block CRC mismatch in block 0"), (len(za) - 2, "combined CRC mismatch")):
+        flip = bytearray(za)
+        flip[at] ^= 0x01
+        assert libbz2(bytes(flip)) is None
+        with pytest.raises(BzxError) as e:
+            run(bytes(flip) + zb)
+        assert e.value.code == BZX_E_DATA and words in str(e.value) and "follows" not in str(e.value), str(e.value)
+    with pytest.raises(BzxError) as e:
+        run(za + zb, cap=len(a.raw()) - 1)
+    assert e.value.code == BZX_E_OUTBUF, str(e.value)
+    assert run(za) == a.raw()                                   # the context works afterwards
+
+
+def test_device_one_stream_emu(emu, oracle):
+    device_one_stream(emu, oracle, host_memory)
+
+
+@pytest.mark.gpu
+def test_device_one_stream_gpu(bzx, oracle):
+    device_one_stream(bzx, oracle, torch_memory)
