@@ -139,8 +139,48 @@ void collect_stage_times(bzx_ctx *ctx);
 void fold_blocks(bzx_stats &st, const BzxBlock *blk, uint32_t first, uint32_t end, uint32_t step);
 
 // ---- bzx_cstream.hip: what the chunked stream compressors (one device, several devices) share
-size_t cstream_max_carry(int level);            // longest withheld raw tail of a chunk
-void stream_write_footer(uint8_t *out, uint64_t end, size_t need, uint32_t crc_comb);
+// Buffer sizes for chunks of at most max_chunk bytes (0 = 256 MiB; rounded up to 16 bytes), good for every level:
+// in_cap a chunk + the longest withheld tail, out_cap its output, blk_cap its blocks.
+struct ChunkCaps { size_t max_chunk, in_cap, out_cap; uint32_t blk_cap; };
+ChunkCaps chunk_caps(size_t max_chunk);
+// Chunk of the one-shot calls: chunk_min doubled up to 128 MiB while below len, then one block per compute unit.
+size_t buffer_chunk(size_t len, int n_cu, size_t chunk_min);
+// What one device holds for a chunk pipeline beside its context.  alloc and free run with that device current.
+struct ChunkLane {
+    uint8_t *d_in[2] = {nullptr, nullptr};
+    uint32_t *d_out[2] = {nullptr, nullptr};
+    uint64_t *d_phase = nullptr;                  // [0] bit phase of the next chunk, [1] bits of the last laid-out chunk
+    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
+    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_d2h = nullptr;
+    uint64_t *h_info[2] = {nullptr, nullptr};     // pinned: d_phase after the chunk emitted into d_out[slot]
+    BzxBlock *h_blk[2] = {nullptr, nullptr};      // pinned: descriptors of the chunk's blocks (CRCs)
+    uint32_t *h_w0 = nullptr;                     // pinned: first word of a chunk's output (shared with its predecessor)
+    size_t device_bytes = 0, pinned_bytes = 0;    // what alloc asked for
+    bool alloc(size_t in_cap, size_t out_cap, uint32_t blk_cap);      // false: something failed; free() releases the rest
+    void free();                                  // waits for the two copy streams, then releases everything
+};
+// Where a finished chunk goes: bit phase of its first word, words it touches, byte offset of the first in `out`.
+struct ChunkPlace { uint64_t phase, nwords; size_t off; };
+// The stream as the host accounts for it, chunk by chunk.  What can fail returns a BZX_E_* code and its text in `err`.
+struct ChunkAcct {
+    int level = 9;
+    uint32_t k = 0;                               // chunks fed
+    uint64_t bits = 32;                           // stream bits accounted for so far (header included)
+    uint32_t crc_comb = 0;
+    uint64_t nblk_total = 0;
+    bzx_stats st = {};                            // block figures of the stream so far
+    bool finished = false;
+    int sticky = BZX_OK;                          // the error a feed call returned: later feed calls return it again
+    uint8_t *out = nullptr;
+    size_t cap = 0, need_hint = 0;                // need_hint, after BZX_E_OUTBUF: bytes the output needs at least
+    void reset(int l) { *this = ChunkAcct(); level = l; }      // a new stream on the same object
+    void begin_output(uint8_t *out, size_t cap);  // the caller's buffer of this feed call; chunk 0: the stream header
+    int place_chunk(uint64_t cbits, ChunkPlace *p, std::string &err);
+    void merge_first_word(const ChunkPlace &p, const uint32_t *h_w0);
+    void account_chunk(const BzxBlock *h_blk, uint32_t nblk, uint64_t cbits);
+    // final feed call of len bytes, every chunk accounted for: footer, *produced, and nblk / raw_bytes / out_bits of st
+    int finish(size_t len, size_t *produced, std::string &err);
+};
 // combined CRC of a stream after one more block (crc.rs:25-27)
 __host__ __device__ static inline uint32_t crc_fold(uint32_t comb, uint32_t crc) { return ((comb << 1) | (comb >> 31)) ^ crc; }
 

@@ -2,9 +2,10 @@
 // bzx_mcompress_buffer) and the kernel that shifts a finished chunk to its bit phase.
 //
 // The scheme is that of bzx_cstream.hip, chunk by chunk: split "withheld raw tail + new bytes", compress all blocks but
-// the last, make the chunk outputs bit-contiguous.  There the two things one chunk hands to the next stay on the device
-// (the tail: a device-to-device copy; the bit phase: d_phase, read by bzx_layout_kernel); here chunk k runs on entry
-// k mod ndev, so both go through the host:
+// the last, make the chunk outputs bit-contiguous; the buffer sizes, the per-device resources (ChunkLane) and the host's
+// accounting of the stream (ChunkAcct) are the ones defined there (bzx_host.h).  There the two things one chunk hands
+// to the next stay on the device (the tail: a device-to-device copy; the bit phase: d_phase, read by
+// bzx_layout_kernel); here chunk k runs on entry k mod ndev, so both go through the host:
 //   needs                               from                                   known after
 //   raw bytes of the withheld block     host tail buffer (refilled from the     split of chunk k-1 (it ends in a host
 //                                       caller's bytes)                         synchronisation)
@@ -107,36 +108,20 @@ struct bzx_mctx {
 };
 
 struct MEntry {
-    uint8_t *d_in[2] = {nullptr, nullptr};
-    uint32_t *d_out[2] = {nullptr, nullptr};      // the chunk at bit phase 0
+    ChunkLane L;                                  // d_out: the chunk at bit phase 0; d_phase: zeroed before every chunk
     uint32_t *d_shift = nullptr;                  // ... shifted to its phase in the stream
-    uint64_t *d_phase = nullptr;                  // zeroed before every chunk: [0] phase in / next phase, [1] bits of the chunk
-    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_d2h = nullptr;
-    uint64_t *h_info[2] = {nullptr, nullptr};     // pinned: d_phase of the chunk emitted into d_out[slot]
-    BzxBlock *h_blk[2] = {nullptr, nullptr};      // pinned: its block descriptors
-    uint32_t *h_w0 = nullptr;                     // pinned: first word of a chunk's output (shared with its predecessor)
     uint32_t pend_nblk[2] = {0, 0};
     bool timed = false;                           // the stage events of the context belong to a chunk not yet accounted for
 };
 
 struct bzx_mstream {
     bzx_mctx *m = nullptr;
-    int level = 9;
-    size_t max_chunk = 0, in_cap = 0, out_cap = 0;
-    uint32_t blk_cap = 0;
+    ChunkCaps c = {};                        // (out_cap rounded up to whole vectors of the shift kernel)
+    ChunkAcct a;
     MEntry ent[BZX_MAX_DEVICES];
     uint8_t *h_tail = nullptr;               // pinned: raw bytes of the withheld block
     size_t tail_cap = 0, tail_len = 0;
-    uint32_t k = 0, k_coll = 0;              // chunks fed, chunks collected (in order)
-    uint64_t bits = 32;                      // stream bits accounted for so far (header included)
-    uint32_t crc_comb = 0;
-    uint64_t nblk_total = 0;
-    bzx_stats st = {};
-    bool finished = false;
-    int sticky = BZX_OK;
-    uint8_t *out = nullptr;
-    size_t cap = 0, need_hint = 0;
+    uint32_t k_coll = 0;                     // chunks collected (in order; a.k: chunks fed)
 };
 
 static std::string entry_name(const bzx_mctx *m, uint32_t e)
@@ -225,22 +210,8 @@ static void mstream_free(bzx_mstream *s)
         MEntry &E = s->ent[e];
         (void)hipSetDevice(m->device[e]);
         (void)hipStreamSynchronize(m->ctx[e]->stream);
-        if (E.s_h2d) (void)hipStreamSynchronize(E.s_h2d);
-        if (E.s_d2h) (void)hipStreamSynchronize(E.s_d2h);
-        for (int i = 0; i < 2; i++) {
-            if (E.d_in[i]) (void)hipFree(E.d_in[i]);
-            if (E.d_out[i]) (void)hipFree(E.d_out[i]);
-            if (E.ev_h2d[i]) (void)hipEventDestroy(E.ev_h2d[i]);
-            if (E.ev_done[i]) (void)hipEventDestroy(E.ev_done[i]);
-            if (E.h_info[i]) (void)hipHostFree(E.h_info[i]);
-            if (E.h_blk[i]) (void)hipHostFree(E.h_blk[i]);
-        }
+        E.L.free();
         if (E.d_shift) (void)hipFree(E.d_shift);
-        if (E.d_phase) (void)hipFree(E.d_phase);
-        if (E.ev_d2h) (void)hipEventDestroy(E.ev_d2h);
-        if (E.h_w0) (void)hipHostFree(E.h_w0);
-        if (E.s_h2d) (void)hipStreamDestroy(E.s_h2d);
-        if (E.s_d2h) (void)hipStreamDestroy(E.s_d2h);
     }
     if (s->h_tail) (void)hipHostFree(s->h_tail);
     delete s;
@@ -260,15 +231,9 @@ extern "C" void bzx_mstream_end(bzx_mstream *s)
 static void mstream_reset_counts(bzx_mstream *s, int level)
 {
     bzx_mctx *m = s->m;
-    s->level = level;
-    s->k = s->k_coll = 0;
+    s->a.reset(level);
+    s->k_coll = 0;
     s->tail_len = 0;
-    s->bits = 32;
-    s->crc_comb = 0;
-    s->nblk_total = 0;
-    s->st = {};
-    s->finished = false;
-    s->sticky = BZX_OK;
     m->info.chunks = m->info.shifted = 0;
     m->info.nblk = 0;
     for (uint32_t e = 0; e < m->ndev; e++) {
@@ -282,19 +247,12 @@ static void mstream_reset_counts(bzx_mstream *s, int level)
 
 static int mstream_make(bzx_mctx *m, int level, size_t max_chunk, bzx_mstream **out)
 {
-    if (max_chunk == 0) max_chunk = (size_t)256 << 20;
-    max_chunk = (max_chunk + 15) & ~(size_t)15;
     bzx_mstream *s = new (std::nothrow) bzx_mstream();
     if (!s) return BZX_E_NOMEM;
     s->m = m;
-    s->max_chunk = max_chunk;
-    // sized for every level, as bzx_cstream_begin sizes them (the object kept for bzx_mcompress_buffer changes level)
-    s->tail_cap = cstream_max_carry(9) + 256;
-    s->in_cap = max_chunk + s->tail_cap;
-    s->out_cap = (s->in_cap + s->in_cap / 50 + 65536) & ~(size_t)255;
-    s->out_cap += s->in_cap / 4;
-    s->out_cap = (s->out_cap + 255) & ~(size_t)255;
-    s->blk_cap = (uint32_t)((s->in_cap + s->in_cap / 4) / ((size_t)100000 * 1 - 19) + 4);
+    s->c = chunk_caps(max_chunk);
+    s->c.out_cap = (s->c.out_cap + 255) & ~(size_t)255;      // the shift kernel moves whole 16-byte vectors
+    s->tail_cap = s->c.in_cap - s->c.max_chunk;               // the longest withheld tail + slack
     // Read by every entry's device: asked for as portable explicitly (as bzx_host_alloc does for the callers' buffers).
     // The runtime's header calls the default flag "the same definition" as the portable one, but that is a comment, not
     // a promise, and a machine with one device cannot show the difference.
@@ -303,23 +261,10 @@ static int mstream_make(bzx_mctx *m, int level, size_t max_chunk, bzx_mstream **
     for (uint32_t e = 0; e < m->ndev && ok; e++) {
         MEntry &E = s->ent[e];
         bad = e;
-        ok = hipSetDevice(m->device[e]) == hipSuccess;
-        for (int i = 0; i < 2 && ok; i++) {
-            ok = hipMalloc((void **)&E.d_in[i], s->in_cap) == hipSuccess && hipMalloc((void **)&E.d_out[i], s->out_cap) == hipSuccess &&
-                 hipEventCreateWithFlags(&E.ev_h2d[i], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&E.ev_done[i], hipEventDisableTiming) == hipSuccess &&
-                 hipHostMalloc((void **)&E.h_info[i], 4 * sizeof(uint64_t), 0) == hipSuccess &&
-                 hipHostMalloc((void **)&E.h_blk[i], (size_t)s->blk_cap * sizeof(BzxBlock), 0) == hipSuccess;
-        }
-        ok = ok && hipMalloc((void **)&E.d_shift, s->out_cap) == hipSuccess &&
-             hipMalloc((void **)&E.d_phase, 4 * sizeof(uint64_t)) == hipSuccess &&
-             hipEventCreateWithFlags(&E.ev_d2h, hipEventDisableTiming) == hipSuccess &&
-             hipHostMalloc((void **)&E.h_w0, 16, 0) == hipSuccess &&
-             hipStreamCreateWithFlags(&E.s_h2d, hipStreamNonBlocking) == hipSuccess &&
-             hipStreamCreateWithFlags(&E.s_d2h, hipStreamNonBlocking) == hipSuccess;
-        m->info.dev[e].device_bytes = ok ? 2 * s->in_cap + 3 * s->out_cap + 4 * sizeof(uint64_t) : 0;
-        m->info.dev[e].pinned_bytes = ok ? 2 * (4 * sizeof(uint64_t) + (size_t)s->blk_cap * sizeof(BzxBlock)) + 16 +
-                                           (e == 0 ? s->tail_cap : 0) : 0;        // (the one tail buffer is counted with entry 0)
+        ok = hipSetDevice(m->device[e]) == hipSuccess && E.L.alloc(s->c.in_cap, s->c.out_cap, s->c.blk_cap) &&
+             hipMalloc((void **)&E.d_shift, s->c.out_cap) == hipSuccess;
+        m->info.dev[e].device_bytes = ok ? E.L.device_bytes + s->c.out_cap : 0;
+        m->info.dev[e].pinned_bytes = ok ? E.L.pinned_bytes + (e == 0 ? s->tail_cap : 0) : 0;      // (the one tail buffer is counted with entry 0)
     }
     if (!ok) {
         m->err = entry_name(m, bad) + "bzx_mstream_begin: device or page-locked allocation failed";
@@ -355,10 +300,10 @@ static void entry_times(bzx_mstream *s, uint32_t e)
     bzx_ctx *ctx = m->ctx[e];
     float ms[4] = {0, 0, 0, 0};
     for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]);
-    s->st.ms_bwt += ms[0];
-    s->st.ms_mtf += ms[1];
-    s->st.ms_huffman += ms[2];
-    s->st.ms_emit += ms[3];
+    s->a.st.ms_bwt += ms[0];
+    s->a.st.ms_mtf += ms[1];
+    s->a.st.ms_huffman += ms[2];
+    s->a.st.ms_emit += ms[3];
     m->info.dev[e].ms_device += ms[0] + ms[1] + ms[2] + ms[3];
 }
 
@@ -370,76 +315,63 @@ static int mstream_collect(bzx_mstream *s, uint32_t j)
     bzx_mctx *m = s->m;
     const uint32_t e = j % m->ndev, slot = (j / m->ndev) & 1u;
     MEntry &E = s->ent[e];
+    ChunkLane &L = E.L;
     const uint32_t nblk = E.pend_nblk[slot];
     E.pend_nblk[slot] = 0;
     if (!nblk) return BZX_OK;
     M_TRY(m, e, hipSetDevice(m->device[e]));
-    M_TRY(m, e, hipEventSynchronize(E.ev_done[slot]));
-    const uint64_t p = s->bits & 31u, cbits = E.h_info[slot][1];
-    if (E.h_info[slot][0] != (cbits & 31u)) {
+    M_TRY(m, e, hipEventSynchronize(L.ev_done[slot]));
+    const uint64_t cbits = L.h_info[slot][1];
+    if (L.h_info[slot][0] != (cbits & 31u)) {
         m->err = entry_name(m, e) + "chunk laid out at a bit phase other than 0";
         return BZX_E_STATE;
     }
-    const uint64_t n_in = (cbits + 31) >> 5, nwords = (p + cbits + 31) >> 5;
-    const size_t off = (size_t)(s->bits >> 5) * 4;
-    if (off + nwords * 4 > s->cap) {
-        m->err = "output buffer too small for the compressed stream";
-        s->need_hint = off + (size_t)((p + cbits + 80 + 7) >> 3);
-        return BZX_E_OUTBUF;
-    }
-    if ((uint64_t)shift_vecs((uint32_t)n_in) * 16 > s->out_cap || n_in > 0x7ffffff0u) {
+    ChunkPlace p;
+    int rc = s->a.place_chunk(cbits, &p, m->err);
+    if (rc) return rc;
+    const uint64_t n_in = (cbits + 31) >> 5;
+    if ((uint64_t)shift_vecs((uint32_t)n_in) * 16 > s->c.out_cap || n_in > 0x7ffffff0u) {
         m->err = entry_name(m, e) + "chunk output larger than its device buffer";
         return BZX_E_HIP;
     }
-    const uint32_t *src = E.d_out[slot];
-    M_TRY(m, e, hipStreamWaitEvent(E.s_d2h, E.ev_done[slot], 0));
-    if (p) {
-        bzx_launch_shift_bits(E.d_out[slot], (uint32_t)n_in, (uint32_t)p, E.d_shift, (uint32_t)m->ctx[e]->n_cu, E.s_d2h);
+    const uint32_t *src = L.d_out[slot];
+    M_TRY(m, e, hipStreamWaitEvent(L.s_d2h, L.ev_done[slot], 0));
+    if (p.phase) {
+        bzx_launch_shift_bits(L.d_out[slot], (uint32_t)n_in, (uint32_t)p.phase, E.d_shift, (uint32_t)m->ctx[e]->n_cu, L.s_d2h);
         M_TRY(m, e, hipGetLastError());
         src = E.d_shift;
         m->info.shifted++;
     }
-    M_TRY(m, e, hipMemcpyAsync(E.h_w0, src, 4, hipMemcpyDeviceToHost, E.s_d2h));
-    if (nwords > 1) M_TRY(m, e, hipMemcpyAsync(s->out + off + 4, src + 1, (nwords - 1) * 4, hipMemcpyDeviceToHost, E.s_d2h));
-    M_TRY(m, e, hipEventRecord(E.ev_d2h, E.s_d2h));
-    M_TRY(m, e, hipEventSynchronize(E.ev_d2h));
-    // the first word is shared with the predecessor (or with nothing: then the bytes there are still zero)
-    uint8_t w[4];
-    memcpy(w, E.h_w0, 4);
-    if (p == 0) memcpy(s->out + off, w, 4);
-    else for (int i = 0; i < 4; i++) s->out[off + i] |= w[i];
-    fold_blocks(s->st, E.h_blk[slot], 0, nblk, 1);
-    for (uint32_t b = 0; b < nblk; b++) s->crc_comb = crc_fold(s->crc_comb, E.h_blk[slot][b].crc);
-    s->nblk_total += nblk;
-    s->bits += cbits;
-    m->info.nblk = s->nblk_total;
+    M_TRY(m, e, hipMemcpyAsync(L.h_w0, src, 4, hipMemcpyDeviceToHost, L.s_d2h));
+    if (p.nwords > 1) M_TRY(m, e, hipMemcpyAsync(s->a.out + p.off + 4, src + 1, (p.nwords - 1) * 4, hipMemcpyDeviceToHost, L.s_d2h));
+    M_TRY(m, e, hipEventRecord(L.ev_d2h, L.s_d2h));
+    M_TRY(m, e, hipEventSynchronize(L.ev_d2h));
+    s->a.merge_first_word(p, L.h_w0);
+    s->a.account_chunk(L.h_blk[slot], nblk, cbits);
+    m->info.nblk = s->a.nblk_total;
     return BZX_OK;
 }
 
 static int mstream_feed(bzx_mstream *s, const uint8_t *raw, size_t len, int final, uint8_t *out, size_t cap, size_t *produced)
 {
     bzx_mctx *m = s->m;
-    const uint32_t N = m->ndev, k = s->k, e = k % N, slot = (k / N) & 1u;
+    const uint32_t N = m->ndev, k = s->a.k, e = k % N, slot = (k / N) & 1u;
     MEntry &E = s->ent[e];
+    ChunkLane &L = E.L;
     bzx_ctx *ctx = m->ctx[e];
-    if (k == 0) {
-        memset(out, 0, cap < 64 ? cap : 64);
-        out[0] = 'B'; out[1] = 'Z'; out[2] = 'h'; out[3] = (uint8_t)('0' + s->level);
-    }
-    s->out = out;
-    s->cap = cap;
+    s->a.begin_output(out, cap);
     const size_t total = s->tail_len + len;
-    if (total > s->in_cap) {                     // (cannot happen with the provisioning of begin; never write past d_in)
+    if (total > s->c.in_cap) {                   // (cannot happen with the provisioning of begin; never write past d_in)
         m->err = "withheld bytes + chunk exceed the device input buffer";
         return BZX_E_STATE;
     }
     M_TRY(m, e, hipSetDevice(m->device[e]));
     // the buffers of this slot were last used by chunk k - 2 ndev: collected by now, but the copy stream does not know
-    if (k >= 2 * N) M_TRY(m, e, hipStreamWaitEvent(E.s_h2d, E.ev_done[slot], 0));
-    if (s->tail_len) M_TRY(m, e, hipMemcpyAsync(E.d_in[slot], s->h_tail, s->tail_len, hipMemcpyHostToDevice, E.s_h2d));
-    if (len) M_TRY(m, e, hipMemcpyAsync(E.d_in[slot] + s->tail_len, raw, len, hipMemcpyHostToDevice, E.s_h2d));
-    M_TRY(m, e, hipEventRecord(E.ev_h2d[slot], E.s_h2d));
-    M_TRY(m, e, hipStreamWaitEvent(ctx->stream, E.ev_h2d[slot], 0));
+    if (k >= 2 * N) M_TRY(m, e, hipStreamWaitEvent(L.s_h2d, L.ev_done[slot], 0));
+    if (s->tail_len) M_TRY(m, e, hipMemcpyAsync(L.d_in[slot], s->h_tail, s->tail_len, hipMemcpyHostToDevice, L.s_h2d));
+    if (len) M_TRY(m, e, hipMemcpyAsync(L.d_in[slot] + s->tail_len, raw, len, hipMemcpyHostToDevice, L.s_h2d));
+    M_TRY(m, e, hipEventRecord(L.ev_h2d[slot], L.s_h2d));
+    M_TRY(m, e, hipStreamWaitEvent(ctx->stream, L.ev_h2d[slot], 0));
     uint32_t nblk = 0, use = 0;
     uint64_t last_start = 0;
     int rc = BZX_OK;
@@ -447,9 +379,9 @@ static int mstream_feed(bzx_mstream *s, const uint8_t *raw, size_t len, int fina
         ctx->B.blk_first = 0;
         ctx->B.blk_step = 1;
         // (synchronises the entry's stream: its chunk k - ndev is complete and both copies above have been read)
-        if ((rc = split_on_device(ctx, E.d_in[slot], total, s->level, &nblk, 0, 1, &last_start))) return ctx_failed(m, e, rc);
+        if ((rc = split_on_device(ctx, L.d_in[slot], total, s->a.level, &nblk, 0, 1, &last_start))) return ctx_failed(m, e, rc);
         use = final ? nblk : nblk - 1;
-        if (use > s->blk_cap) {
+        if (use > s->c.blk_cap) {
             m->err = entry_name(m, e) + "more blocks in a chunk than provisioned";
             return BZX_E_HIP;
         }
@@ -475,25 +407,25 @@ static int mstream_feed(bzx_mstream *s, const uint8_t *raw, size_t len, int fina
         s->tail_len = 0;
     }
     if (use) {
-        M_TRY(m, e, hipMemsetAsync(E.d_phase, 0, 4 * sizeof(uint64_t), ctx->stream));
-        if ((rc = run_stages(ctx, use, STG_ALL, -1, E.d_out[slot], s->out_cap, E.d_phase))) return ctx_failed(m, e, rc);
-        M_TRY(m, e, hipMemcpyAsync(E.h_info[slot], E.d_phase, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        M_TRY(m, e, hipMemcpyAsync(E.h_blk[slot], ctx->B.blk, (size_t)use * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
+        M_TRY(m, e, hipMemsetAsync(L.d_phase, 0, 4 * sizeof(uint64_t), ctx->stream));
+        if ((rc = run_stages(ctx, use, STG_ALL, -1, L.d_out[slot], s->c.out_cap, L.d_phase))) return ctx_failed(m, e, rc);
+        M_TRY(m, e, hipMemcpyAsync(L.h_info[slot], L.d_phase, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        M_TRY(m, e, hipMemcpyAsync(L.h_blk[slot], ctx->B.blk, (size_t)use * sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
         E.timed = true;
         m->info.dev[e].chunks++;
         m->info.dev[e].blocks += use;
     }
-    M_TRY(m, e, hipEventRecord(E.ev_done[slot], ctx->stream));
+    M_TRY(m, e, hipEventRecord(L.ev_done[slot], ctx->stream));
     E.pend_nblk[slot] = use;
-    s->k = k + 1;
-    m->info.chunks = s->k;
+    s->a.k = k + 1;
+    m->info.chunks = s->a.k;
     // Chunk k's stages are in the queue; now collect, in order, what is known to be complete: chunk k - ndev, the one
     // the split above waited for.  Its copy-back runs beside the compression of the chunks after it.
     while (s->k_coll + N <= k)
         if ((rc = mstream_collect(s, s->k_coll++))) return rc;
     if (!final) {
-        s->st.raw_bytes += len;
-        *produced = (size_t)(s->bits >> 5) * 4;
+        s->a.st.raw_bytes += len;
+        *produced = (size_t)(s->a.bits >> 5) * 4;
         return BZX_OK;
     }
     while (s->k_coll <= k)
@@ -504,33 +436,21 @@ static int mstream_feed(bzx_mstream *s, const uint8_t *raw, size_t len, int fina
         entry_times(s, i);
         if (m->info.dev[i].ms_device > ms_max) ms_max = m->info.dev[i].ms_device;
     }
-    const uint64_t end = s->bits;
-    const size_t need = (size_t)((end + 80 + 7) >> 3);
-    if (need > cap) {
-        m->err = "output buffer too small for the compressed stream";
-        s->need_hint = need;
-        return BZX_E_OUTBUF;
-    }
-    stream_write_footer(out, end, need, s->crc_comb);
-    *produced = need;
-    s->finished = true;
-    s->st.raw_bytes += len;
-    s->st.nblk = (uint32_t)s->nblk_total;
-    s->st.out_bits = (uint64_t)need * 8;
-    s->st.ms_total = ms_max;
-    m->stats = s->st;
+    if ((rc = s->a.finish(len, produced, m->err))) return rc;
+    s->a.st.ms_total = ms_max;
+    m->stats = s->a.st;
     return BZX_OK;
 }
 
 extern "C" int bzx_mstream_feed(bzx_mstream *s, const uint8_t *raw, size_t len, int final, uint8_t *out, size_t cap,
                                 size_t *produced)
 {
-    if (!s || !s->m || !out || !produced || (len && !raw) || len > s->max_chunk || cap < 16) return BZX_E_PARAM;
+    if (!s || !s->m || !out || !produced || (len && !raw) || len > s->c.max_chunk || cap < 16) return BZX_E_PARAM;
     std::unique_lock<std::recursive_mutex> lock_(s->m->mu);
-    if (s->finished) return BZX_E_STATE;
-    if (s->sticky) return s->sticky;
+    if (s->a.finished) return BZX_E_STATE;
+    if (s->a.sticky) return s->a.sticky;
     const int rc = mstream_feed(s, raw, len, final, out, cap, produced);
-    if (rc) s->sticky = rc;
+    if (rc) s->a.sticky = rc;
     return rc;
 }
 
@@ -544,16 +464,12 @@ extern "C" int bzx_mcompress_buffer(bzx_mctx *m, const uint8_t *raw, size_t len,
         m->err = "a bzx_mstream is open on this bzx_mctx: call bzx_mstream_end first";
         return BZX_E_STATE;
     }
-    size_t chunk = BZX_MBUF_CHUNK_MIN;
-    while (chunk < ((size_t)128 << 20) && chunk < (len + m->ndev - 1) / m->ndev) chunk <<= 1;
-    if (chunk < (len + m->ndev - 1) / m->ndev) {
-        int n_cu = m->ctx[0]->n_cu;
-        for (uint32_t e = 1; e < m->ndev; e++)
-            if (m->ctx[e]->n_cu < n_cu) n_cu = m->ctx[e]->n_cu;
-        chunk = (size_t)(n_cu > 0 ? n_cu : 256) * 900000u;
-    }
+    int n_cu = m->ctx[0]->n_cu;
+    for (uint32_t e = 1; e < m->ndev; e++)
+        if (m->ctx[e]->n_cu < n_cu) n_cu = m->ctx[e]->n_cu;
+    const size_t chunk = buffer_chunk((len + m->ndev - 1) / m->ndev, n_cu, BZX_MBUF_CHUNK_MIN);
     int rc;
-    if (m->cs && m->cs->max_chunk < chunk) bzx_mstream_end(m->cs);      // (clears m->cs)
+    if (m->cs && m->cs->c.max_chunk < chunk) bzx_mstream_end(m->cs);      // (clears m->cs)
     if (!m->cs) {
         if ((rc = mstream_make(m, level, chunk, &m->cs))) return rc;
     } else {
@@ -562,8 +478,8 @@ extern "C" int bzx_mcompress_buffer(bzx_mctx *m, const uint8_t *raw, size_t len,
         for (uint32_t e = 0; e < m->ndev; e++) {
             M_TRY(m, e, hipSetDevice(m->device[e]));
             M_TRY(m, e, hipStreamSynchronize(m->ctx[e]->stream));
-            M_TRY(m, e, hipStreamSynchronize(m->cs->ent[e].s_h2d));
-            M_TRY(m, e, hipStreamSynchronize(m->cs->ent[e].s_d2h));
+            M_TRY(m, e, hipStreamSynchronize(m->cs->ent[e].L.s_h2d));
+            M_TRY(m, e, hipStreamSynchronize(m->cs->ent[e].L.s_d2h));
         }
         mstream_reset_counts(m->cs, level);
     }
@@ -573,7 +489,7 @@ extern "C" int bzx_mcompress_buffer(bzx_mctx *m, const uint8_t *raw, size_t len,
         const size_t n = len - off < chunk ? len - off : chunk;
         const int fin = off + n == len;
         if ((rc = bzx_mstream_feed(s, raw + off, n, fin, out, cap, &produced))) {
-            if (rc == BZX_E_OUTBUF) *out_len = s->need_hint;      // (a lower bound when chunks remain)
+            if (rc == BZX_E_OUTBUF) *out_len = s->a.need_hint;      // (a lower bound when chunks remain)
             return rc;
         }
         off += n;

@@ -212,8 +212,13 @@ int bzx_split_rle1_chunk(bzx_ctx *ctx, const uint8_t *raw, size_t len, int level
  * (bzx_host_alloc, or memory the caller registered with HIP) for truly asynchronous copies.
  *   feed: consumes raw[0..len); `out`/`cap` is the WHOLE output buffer, the same on every call; *produced = bytes
  *   of it that are final so far (a caller may write out[flushed..*produced) to its file after every call).
- *   The call with final != 0 (len may be 0) completes the stream: *produced = length of the .bz2.
- * bzx_compress_buffer is this over a whole buffer.
+ *   The call with final != 0 (len may be 0) completes the stream: *produced = length of the .bz2.  feed after it:
+ *   BZX_E_STATE.  BZX_E_PARAM (a NULL pointer, len > max_chunk, cap < 16) leaves the stream as it was.
+ *   BZX_E_OUTBUF: `out` cannot hold the stream (bzx_compress_buffer: bytes needed so far in *out_len, a lower bound
+ *   while chunks remain).  An error is sticky for the stream object: later feed calls return it again;
+ *   bzx_cstream_end is still required and the bzx_ctx stays usable for the next stream.
+ * bzx_compress_buffer is this over a whole buffer; its stream object is kept in the context and started anew by every
+ * call, also after an error.
  */
 typedef struct bzx_cstream bzx_cstream;
 int bzx_cstream_begin(bzx_ctx *ctx, int level, size_t max_chunk, bzx_cstream **out);
@@ -414,9 +419,8 @@ int bzx_get_block_info(const bzx_ctx *ctx, uint32_t block, bzx_block_info *out);
  *   out that can no longer change (never a word a later chunk still has to touch).  feed returns after the bytes it
  *   was given have left the caller's buffer.  The call with final != 0 (len may be 0) completes the stream:
  *   *produced = length of the .bz2.  feed after it: BZX_E_STATE.
- *   BZX_E_OUTBUF as bzx_cstream_feed / bzx_compress_buffer report it (bzx_mcompress_buffer: bytes needed so far in
- *   *out_len, a lower bound while chunks remain).  An error is sticky for the stream object: later feed calls return
- *   it again; bzx_mstream_end is still required and the bzx_mctx stays usable for the next stream.
+ *   Errors as for bzx_cstream_feed / bzx_compress_buffer, sticky for the stream object likewise; bzx_mstream_end is
+ *   still required and the bzx_mctx stays usable for the next stream.
  * What a chunk needs from its predecessor goes through the host: the raw bytes of the withheld, unfinished block (one
  * page-locked tail buffer, refilled from the caller's bytes after every split) and its bit position (a sum kept by the
  * host).  Every chunk is emitted at bit phase 0 into a device buffer of its entry as soon as its Huffman stage is

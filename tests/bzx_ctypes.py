@@ -166,36 +166,32 @@ class BzxLib:
         self._check(self.lib.bzx_split_rle1(self.ctx, data, len(data), level, slabs, cap, ns, crcs, C.byref(nb)))
         return [(slabs.raw[b * 900000:b * 900000 + ns[b]], crcs[b]) for b in range(nb.value)]
 
+    def cstream(self, level=9, max_chunk=0):
+        return CStream(self, level, max_chunk)
+
     def cstream_compress(self, data: bytes, level=9, chunk=1 << 20, max_chunk=None, pinned=False):
         """bzx_cstream_*: feed `data` in pieces of `chunk` bytes (an int, or a list of piece lengths); returns the .bz2."""
-        L = self.lib
-        L.bzx_cstream_begin.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
-        L.bzx_cstream_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
-                                       C.POINTER(C.c_size_t)]
-        L.bzx_cstream_end.argtypes = [C.c_void_p]
         pieces = chunk if isinstance(chunk, (list, tuple)) else None
-        mc = max_chunk or (max(pieces) if pieces else chunk)
-        s = C.c_void_p()
-        self._check(L.bzx_cstream_begin(self.ctx, level, mc, C.byref(s)))
+        s = self.cstream(level, max_chunk or (max(pieces) if pieces else chunk))
         cap = len(data) + len(data) // 50 + 4096
         out = C.create_string_buffer(cap)
         src = C.create_string_buffer(data, len(data)) if data else C.create_string_buffer(1)
-        produced = C.c_size_t()
         try:
             off, i, last = 0, 0, 0
             while True:
                 n = min(len(data) - off, pieces[i % len(pieces)] if pieces else chunk)
                 fin = off + n >= len(data)
-                self._check(L.bzx_cstream_feed(s, C.addressof(src) + off, n, int(fin), out, cap, C.byref(produced)))
-                assert produced.value >= last
-                last = produced.value
+                rc, produced = s.feed_raw(C.addressof(src) + off, n, fin, C.addressof(out), cap)
+                self._check(rc)
+                assert produced >= last
+                last = produced
                 off += n
                 i += 1
                 if fin:
                     break
         finally:
-            L.bzx_cstream_end(s)
-        return out.raw[:produced.value]
+            s.end()
+        return out.raw[:last]
 
     def split_rle1_chunks(self, data: bytes, level=9, chunk=1 << 16):
         """bzx_split_rle1_chunk over pieces of `chunk` bytes -> list of (block bytes, crc), as split_rle1."""
@@ -241,6 +237,30 @@ class BzxLib:
         st = BzxStats()
         self._check(self.lib.bzx_get_stats(self.ctx, C.byref(st)))
         return st
+
+
+class CStream:
+    """One bzx_cstream on a BzxLib's context: feed_raw(ptr, n, final, out_ptr, cap) -> (rc, produced)."""
+
+    def __init__(self, lib, level, max_chunk):
+        self.L = L = lib.lib
+        L.bzx_cstream_begin.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.bzx_cstream_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]
+        L.bzx_cstream_end.argtypes = [C.c_void_p]
+        L.bzx_cstream_end.restype = None
+        self.h = C.c_void_p()
+        lib._check(L.bzx_cstream_begin(lib.ctx, level, max_chunk, C.byref(self.h)))
+
+    def feed_raw(self, ptr, n, final, out_ptr, cap):
+        made = C.c_size_t(0)
+        rc = self.L.bzx_cstream_feed(self.h, ptr, n, int(final), out_ptr, cap, C.byref(made))
+        return rc, made.value
+
+    def end(self):
+        if self.h:
+            self.L.bzx_cstream_end(self.h)
+            self.h = C.c_void_p()
 
 
 class OracleHuff(C.Structure):

@@ -192,6 +192,56 @@ def test_emu_chunked_stream_and_chunked_split(emu, oracle):
         assert emu.split_rle1_chunks(data, level, chunk) == oracle.split_rle1(data, level), (len(data), chunk)
 
 
+def test_emu_cstream_errors(emu, oracle):
+    """bzx_cstream_feed's refusals, as test_emu_mdev_errors has them for bzx_mstream_feed: a refused argument leaves
+    the stream intact; feed after the final call is BZX_E_STATE; any other error is sticky for the stream object (the
+    device is a chunk ahead of the host's accounting when it is found) and the context stays usable."""
+    import ctypes as C
+    E_PARAM, E_OUTBUF, E_STATE = -2, -4, -6
+    data = oracle.synthtext(120000)
+    want = bz2.compress(data, 1)
+    src = C.create_string_buffer(data, len(data))
+    cap = len(data) + 8192
+    out = C.create_string_buffer(cap)
+    p_src, p_out = C.addressof(src), C.addressof(out)
+    # len > max_chunk; bad pointers; cap below 16
+    s = emu.cstream(1, 64000)
+    try:
+        assert s.feed_raw(p_src, 64001, False, p_out, cap)[0] == E_PARAM
+        assert s.feed_raw(None, 5, False, p_out, cap)[0] == E_PARAM
+        assert s.feed_raw(p_src, 5, False, None, cap)[0] == E_PARAM
+        assert s.feed_raw(p_src, 5, False, p_out, 15)[0] == E_PARAM
+        # (the refused calls left the stream intact) feed after final
+        assert s.feed_raw(p_src, 60000, False, p_out, cap)[0] == 0
+        rc, made = s.feed_raw(p_src + 60000, 60000, True, p_out, cap)
+        assert rc == 0 and out.raw[:made] == want
+        assert s.feed_raw(p_src, 0, True, p_out, cap)[0] == E_STATE
+        assert s.feed_raw(p_src, 10, False, p_out, cap)[0] == E_STATE
+    finally:
+        s.end()
+    # cap too small: BZX_E_OUTBUF, sticky on the stream; the context stays usable
+    small = 2000
+    s = emu.cstream(1, 64000)
+    try:
+        rcs = [s.feed_raw(p_src, 60000, False, p_out, small)[0], s.feed_raw(p_src + 60000, 60000, True, p_out, small)[0]]
+        assert rcs[1] == E_OUTBUF and rcs[0] in (0, E_OUTBUF)
+        assert s.feed_raw(p_src, 0, True, p_out, cap)[0] == E_OUTBUF
+        assert s.feed_raw(p_src, 10, False, p_out, cap)[0] == E_OUTBUF
+        assert "output buffer too small" in emu.lib.bzx_last_error(emu.ctx).decode()
+    finally:
+        s.end()
+    assert emu.compress_buffer(data, 1) == want
+    # the one-shot call reports the bytes needed so far; granted, they suffice (its kept stream object is reset)
+    fn = emu.lib.bzx_compress_buffer
+    ol = C.c_size_t(0)
+    assert fn(emu.ctx, data, len(data), 1, out, small, C.byref(ol)) == E_OUTBUF
+    need = ol.value
+    assert small < need <= len(want) + 4
+    assert fn(emu.ctx, data, len(data), 1, out, need, C.byref(ol)) == 0 and out.raw[:ol.value] == want
+    blk = oracle.synthtext(3000)
+    assert emu.stage_bwt(blk)[:2] == oracle.bwt(blk)
+
+
 def test_emu_decompress(emu, oracle):
     """bzx_decompress_buffer (decompress.rs:38-404): libbz2-made streams come back as the input; damage is reported."""
     from bzx_ctypes import BzxError

@@ -132,6 +132,21 @@ def test_emu_mdev_distribution(emu_runs, oracle):
     assert shifted > 0
 
 
+def test_emu_cstream_equals_mstream_one_entry(emu_runs, emu_path):
+    """bzx_cstream_* and bzx_mstream_* over (0,) share their accounting of the stream: the same bytes and the same
+    nblk, raw_bytes and out_bits for every case."""
+    cases, res = emu_runs
+    lib = BzxLib(emu_path)
+    try:
+        for name, data, level, chunk, _ in cases:
+            r = res[(name, (0,))]
+            assert lib.cstream_compress(data, level, chunk) == r["z"], name
+            st = lib.stats()
+            assert (st.nblk, st.raw_bytes, st.out_bits) == (r["nblk"], r["raw"], r["out_bits"]), name
+    finally:
+        lib.close()
+
+
 SHIFT_SIZES = (0, 1, 3, 4, 5, 255, 256, 257, 4099)
 
 
