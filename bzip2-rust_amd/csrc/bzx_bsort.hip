@@ -707,8 +707,6 @@ __shared__ uint32_t s_bc[8];                 // [2] vote, [5..6] diff
 __shared__ uint32_t s_m[2];                  // lengths of the two lists of tied ranks
 __shared__ uint32_t s_red[SK_NW][4];         // per wave: OR (lo, hi) and AND (lo, hi) of the bucket's records as loaded
 
-template <int WHICH> __device__ __forceinline__ uint64_t *lds_arr() { return WHICH ? s_w : s_x; }
-
 // (lds_order, bzx_uni, bzx_tid_here: bzx_wg.h)
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return bzx_uni(v); }
 __device__ __forceinline__ uint32_t tid_here() { return bzx_tid_here(); }
@@ -749,13 +747,12 @@ __device__ __forceinline__ void wave_rank(uint32_t *wc, uint32_t d, bool valid, 
     lds_order();
 }
 
-// Stable LSD sort (8-bit digits) of A[base .. base+cnt) (A = s_x or s_w) by bits [lo, hi) with the whole workgroup;
+// Stable LSD sort (8-bit digits) of s_w[base .. base+cnt) by bits [lo, hi) with the whole workgroup;
 // digits on which all agree are skipped.  Wave w owns the contiguous chunk [w*rows*64, (w+1)*rows*64), row j = 64
 // consecutive elements.  Starts and ends with workgroup barriers.
-template <int WHICH>
 __device__ __attribute__((noinline)) void wg_radix_sort(uint32_t base, uint32_t cnt, int lo, int hi)
 {
-    uint64_t *A = lds_arr<WHICH>() + base;
+    uint64_t *A = s_w + base;
     const uint32_t tid = threadIdx.x, lane = bzx_lane(), wave = bzx_wave();
     const uint32_t rows = (cnt + SK_NT - 1) / SK_NT, chunk = rows * 64;
     if (tid == 0) {
@@ -1059,6 +1056,169 @@ __device__ __forceinline__ void wave_sort_mark(uint32_t base, uint32_t s, int lo
         if ((diff >> k) & 1u) fset(base + e);
 }
 
+// Rank at which the group of rank p starts (rank 0 starts a group).
+__device__ __forceinline__ uint32_t group_start(uint32_t p)
+{
+    uint32_t wi = p >> 6;
+    uint64_t w = s_f[wi] & (~0ull >> (63u - (p & 63u)));
+    while (!w) w = s_f[--wi];
+    return wi * 64 + 63u - (uint32_t)__builtin_clzll(w);
+}
+
+// The tied ranks of a row of 64: rank p is tied unless a group starts at p and at p + 1.  f: the row's word of group-start
+// flags, nx: the next word (the flag after the row's last rank is its bit 0; ranks from the bucket's size on are all flagged).
+__device__ __forceinline__ uint64_t tied_mask(uint64_t f, uint64_t nx) { return ~(f & ((f >> 1) | (nx << 63))); }
+
+// Compaction of the slots c = j * SK_NT + tid of the workgroup in slot order, keep[j] = bit mask of my wave's row j, in
+// two halves with a barrier of the caller's between them: every wave publishes the kept slots of its rows; then
+// before[j] = kept slots before my row j, and the total is returned.  (Rows from nrow on: nothing kept.)
+__device__ __forceinline__ void slot_counts_publish(const uint64_t *keep, uint32_t nrow)
+{
+    const uint32_t lane = bzx_lane(), wave = bzx_wave();
+#pragma unroll
+    for (uint32_t j = 0; j < BS_E; j++)
+        if (j < nrow && lane == 0) s_cnt[0][j * SK_NW + wave] = (uint32_t)__popcll(keep[j]);
+}
+__device__ __forceinline__ uint32_t slot_counts_sum(uint32_t nrow, uint32_t *before)
+{
+    const uint32_t wave = bzx_wave();
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < BS_E; j++) {
+        before[j] = 0;
+        if (j < nrow) {
+#pragma unroll
+            for (uint32_t w = 0; w < SK_NW; w++) {
+                const uint32_t c = s_cnt[0][j * SK_NW + w];
+                if (w == wave) before[j] = total;
+                total += c;
+            }
+        }
+    }
+    return total;
+}
+
+// ---- The group-ordering step of a round, shared by the refinement rounds of the sort kernel and the rank rounds: it
+// does not care where the round words came from (the next 50 key bits / the ranks h and 2h ahead).  On entry the lane
+// holds up to BS_E entries (bit j of a mask: entry j); rank_of(j) is the rank of entry j, whose round word
+// [key:50 | position:14] the caller stores to s_w between list_big_groups and its barrier.  The four pieces run in this
+// order; the lane id is the caller's (made opaque once per phase, see tid_here).  par: parity of s_rc in use.
+
+// Entries that head their group (hmask) measure it and list it in s_med / s_large when it is above BS_TINY.
+template <typename RankOf>
+__device__ __forceinline__ void list_big_groups(uint32_t hmask, uint32_t par, const RankOf &rank_of)
+{
+#pragma unroll
+    for (uint32_t j = 0; j < BS_E; j++) {
+        if ((hmask >> j) & 1u) {
+            const uint32_t p = rank_of(j);
+            uint32_t wi = p >> 6;
+            uint64_t w = (s_f[wi] >> (p & 63u)) >> 1;               // flags after p
+            uint32_t e;
+            if (w) {
+                e = p + 1u + (uint32_t)__builtin_ctzll(w);
+            } else {
+                do w = s_f[++wi]; while (!w);                       // ends at the sentinel word at the latest
+                e = wi * 64 + (uint32_t)__builtin_ctzll(w);
+            }
+            const uint32_t size = e - p;
+            if (size > BS_MED) s_large[atomicAdd(&s_rc[par][2], 1u)] = p | (size << 16);
+            else if (size > BS_TINY) s_med[atomicAdd(&s_rc[par][1], 1u)] = p | (size << 16);
+        }
+    }
+}
+
+// The listed groups (nmed in s_med, nlarge in s_large; after the barrier that publishes the lists and the round words)
+// are sorted by the top 16 bits of their words only; the sub-groups that leaves are almost always small enough for the
+// counting tier, which compares whole words.  Otherwise: full sort.  Groups of up to BS_MED: one wave each; larger
+// ones: the whole workgroup.  Ends with a barrier.
+__device__ __forceinline__ void sort_listed_groups(uint32_t par, uint32_t nmed, uint32_t nlarge, uint32_t tid, uint32_t lane)
+{
+    for (;;) {
+        uint32_t k = 0;
+        if (lane == 0) k = atomicAdd(&s_rc[par][3], 1u);
+        k = __shfl(k, 0);
+        if (k >= nmed) break;
+        const uint32_t e = s_med[k], gs = e & 0xFFFFu, sz = e >> 16;
+        wave_sort_mark(gs, sz, 48, lane);
+        lds_order();
+        if (__ballot(any_big(gs, sz, lane, 64))) wave_sort_mark(gs, sz, 14, lane);
+    }
+    for (uint32_t k = 0; k < nlarge; k++) {
+        const uint32_t e = s_large[k], gs = e & 0xFFFFu, sz = e >> 16;
+        wg_radix_sort(gs, sz, 48, 64);
+        mark_changes(gs, sz, 48, tid, SK_NT);
+        if (tid == 0) s_bc[2] = 0;
+        __syncthreads();
+        if (any_big(gs, sz, tid, SK_NT)) s_bc[2] = 1;
+        __syncthreads();
+        if (s_bc[2]) {
+            wg_radix_sort(gs, sz, 14, 64);
+            mark_changes(gs, sz, 14, tid, SK_NT);
+        }
+    }
+    __syncthreads();
+}
+
+// Groups of up to BS_TINY ranks: every lane ranks the word at its entry (amask) among its group's.  One entry at a
+// time, four members per step (four LDS reads in flight): an entry costs as many steps as the largest group among the
+// wave's 64 entries needs, and most hold only groups of a few ranks.  dst_[j] = new rank | first-of-sub-group flag << 31
+// (~0: untouched), my[j] = the word; both are the caller's arrays (declared in here they went to scratch
+// memory).  Ends with a barrier: every word has been read.
+template <typename RankOf>
+__device__ __forceinline__ void rank_tiny_groups(uint32_t amask, uint32_t nrow, const RankOf &rank_of, uint32_t (&dst_)[BS_E],
+                                                 uint64_t (&my)[BS_E])
+{
+#pragma unroll
+    for (uint32_t j = 0; j < BS_E; j++) {
+        dst_[j] = 0xFFFFFFFFu;
+        my[j] = 0;
+        uint32_t a_ = 0, sz = 0;
+        if ((amask >> j) & 1u) {
+            const uint32_t p = rank_of(j);
+            uint32_t e_;
+            if (tiny_bounds(p, a_, e_) && e_ - a_ > 1) {
+                sz = e_ - a_;
+                my[j] = s_w[p];
+            }
+        }
+        if (j < nrow) {
+            // r: members below my word (key, then position: a total order); rk: members below my KEY alone -- any word
+            // with a smaller key is below my word with its position bits cleared.  r == rk: nobody with my key
+            // precedes me, I start a (sub)group.
+            uint32_t r = 0, rk = 0;
+            const uint64_t myc = my[j] & ~W_POS_MASK;
+            for (uint32_t i = 0; i < sz; i += 4) {
+                uint64_t wq[4];
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) wq[k] = s_w[a_ + i + k];       // (past the group: read, not counted)
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) {
+                    const bool in = i + k < sz;
+                    r += in && wq[k] < my[j];
+                    rk += in && wq[k] < myc;
+                }
+            }
+            if (sz) dst_[j] = (a_ + r) | (r != rk ? 0u : 0x80000000u);
+        }
+    }
+    __syncthreads();
+}
+
+// The ranked words go to their new ranks, and the first of every sub-group flags its start.  Ends with a barrier.
+__device__ __forceinline__ void place_ranked(const uint32_t (&dst_)[BS_E], const uint64_t (&my)[BS_E])
+{
+#pragma unroll
+    for (uint32_t j = 0; j < BS_E; j++) {
+        if (dst_[j] != 0xFFFFFFFFu) {
+            const uint32_t q = dst_[j] & 0x7FFFFFFFu;
+            s_w[q] = my[j];
+            if ((dst_[j] >> 31) && !fbit(q)) fset(q);      // first of its sub-group
+        }
+    }
+    __syncthreads();
+}
+
 // The list of tied ranks lives in the key halves of s_x, which are dead once the initial sort has set the group-start
 // flags: two lists of 16-bit ranks (one read, one written), entry i in the upper dword of s_x[i].
 #define LIST(which, i) (reinterpret_cast<uint16_t *>(s_x)[4u * (i) + 2u + (which)])
@@ -1115,12 +1275,10 @@ __device__ __forceinline__ bool initial_sort(uint32_t cnt)
     }
     if (tid == 0) s_f[BS_FW] = ~0ull;
     if (__syncthreads_or(bad)) return false;
-    // The list of tied ranks (see list_tied), straight from the flag words: rank p is tied unless a group starts at p
-    // and at p + 1; the flag after a row's last rank is bit 0 of the next flag word (ranks from cnt on are all flagged).
+    // The list of tied ranks (see list_tied), straight from the flag words (tied_mask).
 #pragma unroll
     for (uint32_t j = 0; j < BS_E; j++) {
-        const uint64_t nx = s_f[j * SK_NW + wave + 1];
-        const uint64_t mk = ~(fm[j] & ((fm[j] >> 1) | (nx << 63)));
+        const uint64_t mk = tied_mask(fm[j], s_f[j * SK_NW + wave + 1]);
         if (mk) {
             uint32_t base = 0;
             if (lane == 0) base = atomicAdd(&s_m[0], (uint32_t)__popcll(mk));
@@ -1300,24 +1458,8 @@ __device__ __forceinline__ void bsort_body(const BzxBatch &B)
             uint64_t g[BS_E];
 #pragma unroll
             for (uint32_t j = 0; j < BS_E; j++) g[j] = ((amask >> j) & 1u) ? pk_window_bit(P, xa[j]) : 0ull;
-#pragma unroll
-            for (uint32_t j = 0; j < BS_E; j++) {
-                if ((hmask >> j) & 1u) {                                    // first rank of its group: measure it
-                    const uint32_t p = pq[j] & 0xFFFFu;
-                    uint32_t wi = p >> 6;
-                    uint64_t w = (s_f[wi] >> (p & 63u)) >> 1;               // flags after p
-                    uint32_t e;
-                    if (w) {
-                        e = p + 1u + (uint32_t)__builtin_ctzll(w);
-                    } else {
-                        do w = s_f[++wi]; while (!w);                       // ends at the sentinel word at the latest
-                        e = wi * 64 + (uint32_t)__builtin_ctzll(w);
-                    }
-                    const uint32_t size = e - p;
-                    if (size > BS_MED) s_large[atomicAdd(&s_rc[par][2], 1u)] = p | (size << 16);
-                    else if (size > BS_TINY) s_med[atomicAdd(&s_rc[par][1], 1u)] = p | (size << 16);
-                }
-            }
+            const auto rank_of = [&](uint32_t j) { return pq[j] & 0xFFFFu; };
+            list_big_groups(hmask, par, rank_of);
 #pragma unroll
             for (uint32_t j = 0; j < BS_E; j++)
                 if ((amask >> j) & 1u) s_w[pq[j] & 0xFFFFu] = (g[j] & ~W_POS_MASK) | (uint64_t)(pq[j] >> 16);
@@ -1331,86 +1473,17 @@ __device__ __forceinline__ void bsort_body(const BzxBatch &B)
             if (nmed | nlarge) {
                 DIAG_COUNT(86, nmed);
                 DIAG_COUNT(87, nlarge);
-                // larger groups: sorted by the top 16 bits of their words only; the sub-groups that leaves are almost
-                // always small enough for the counting tier below, which compares whole words.  Otherwise: full sort.
-                for (;;) {
-                    uint32_t k = 0;
-                    if (lane == 0) k = atomicAdd(&s_rc[par][3], 1u);
-                    k = __shfl(k, 0);
-                    if (k >= nmed) break;
-                    const uint32_t e = s_med[k], gs = e & 0xFFFFu, sz = e >> 16;
-                    wave_sort_mark(gs, sz, 48, lane);
-                    lds_order();
-                    if (__ballot(any_big(gs, sz, lane, 64))) wave_sort_mark(gs, sz, 14, lane);
-                }
-                for (uint32_t k = 0; k < nlarge; k++) {
-                    const uint32_t e = s_large[k], gs = e & 0xFFFFu, sz = e >> 16;
-                    wg_radix_sort<1>(gs, sz, 48, 64);
-                    mark_changes(gs, sz, 48, tid, SK_NT);
-                    if (tid == 0) s_bc[2] = 0;
-                    __syncthreads();
-                    if (any_big(gs, sz, tid, SK_NT)) s_bc[2] = 1;
-                    __syncthreads();
-                    if (s_bc[2]) {
-                        wg_radix_sort<1>(gs, sz, 14, 64);
-                        mark_changes(gs, sz, 14, tid, SK_NT);
-                    }
-                }
-                __syncthreads();
+                sort_listed_groups(par, nmed, nlarge, tid, lane);
                 DIAG_STAMP(69);
             }
             tid = tid_here();
             lane = tid & 63u;
             wave = tid >> 6;
-            // groups of up to BS_TINY ranks: every lane ranks the word at its list entry among its group's.  One entry
-            // at a time, four members per step (four LDS reads in flight): an entry costs as many steps as the largest
-            // group among the wave's 64 entries needs, and most hold only groups of a few ranks.
-            uint32_t dst_[BS_E];                                  // new rank | first-of-sub-group flag << 31; ~0: untouched
+            uint32_t dst_[BS_E];
             uint64_t my[BS_E];
-#pragma unroll
-            for (uint32_t j = 0; j < BS_E; j++) {
-                dst_[j] = 0xFFFFFFFFu;
-                my[j] = 0;
-                uint32_t a_ = 0, sz = 0;
-                if ((amask >> j) & 1u) {
-                    const uint32_t p = pq[j] & 0xFFFFu;
-                    uint32_t e_;
-                    if (tiny_bounds(p, a_, e_) && e_ - a_ > 1) {
-                        sz = e_ - a_;
-                        my[j] = s_w[p];
-                    }
-                }
-                if (j < nrow) {
-                    // r: members below my word (key, then position: a total order); rk: members below my KEY alone -- any word
-                    // with a smaller key is below my word with its position bits cleared.  r == rk: nobody with my key
-                    // precedes me, I start a (sub)group.
-                    uint32_t r = 0, rk = 0;
-                    const uint64_t myc = my[j] & ~W_POS_MASK;
-                    for (uint32_t i = 0; i < sz; i += 4) {
-                        uint64_t wq[4];
-#pragma unroll
-                        for (uint32_t k = 0; k < 4; k++) wq[k] = s_w[a_ + i + k];       // (past the group: read, not counted)
-#pragma unroll
-                        for (uint32_t k = 0; k < 4; k++) {
-                            const bool in = i + k < sz;
-                            r += in && wq[k] < my[j];
-                            rk += in && wq[k] < myc;
-                        }
-                    }
-                    if (sz) dst_[j] = (a_ + r) | (r != rk ? 0u : 0x80000000u);
-                }
-            }
-            __syncthreads();
+            rank_tiny_groups(amask, nrow, rank_of, dst_, my);
             DIAG_STAMP(70);
-#pragma unroll
-            for (uint32_t j = 0; j < BS_E; j++) {
-                if (dst_[j] != 0xFFFFFFFFu) {
-                    const uint32_t q = dst_[j] & 0x7FFFFFFFu;
-                    s_w[q] = my[j];
-                    if ((dst_[j] >> 31) && !fbit(q)) fset(q);      // first of its sub-group
-                }
-            }
-            __syncthreads();
+            place_ranked(dst_, my);
             DIAG_STAMP(71);
             list_tied<false>(m, lpar, lpar ^ 1u);                  // the ranks of the list that are still tied
             __syncthreads();
@@ -1440,13 +1513,7 @@ __device__ __forceinline__ void bsort_body(const BzxBatch &B)
                     const uint32_t f0 = fbit(p);
                     sax[p] = (uint64_t)rot | ((uint64_t)f0 << 32);
                     if (isa0) {
-                        uint32_t head = p;
-                        if (!f0) {
-                            uint32_t wi = p >> 6;
-                            uint64_t w = s_f[wi] & (~0ull >> (63u - (p & 63u)));
-                            while (!w) w = s_f[--wi];              // (rank 0 of the bucket starts a group)
-                            head = wi * 64 + 63u - (uint32_t)__builtin_clzll(w);
-                        }
+                        const uint32_t head = f0 ? p : group_start(p);
                         isa0[rot] = start + head;
                         if (f0 && fbit(p + 1)) isa1[rot] = start + head;
                     }
@@ -1462,23 +1529,11 @@ __device__ __forceinline__ void bsort_body(const BzxBatch &B)
                 lane = tid & 63u;
                 wave = tid >> 6;
 #pragma unroll
-                for (uint32_t j = 0; j < BS_E; j++) {
-                    const uint64_t f0 = s_f[j * SK_NW + wave], nx = s_f[j * SK_NW + wave + 1];
-                    mk[j] = ~(f0 & ((f0 >> 1) | (nx << 63)));
-                    if (lane == 0) s_cnt[0][j * SK_NW + wave] = (uint32_t)__popcll(mk[j]);
-                }
+                for (uint32_t j = 0; j < BS_E; j++) mk[j] = tied_mask(s_f[j * SK_NW + wave], s_f[j * SK_NW + wave + 1]);
+                slot_counts_publish(mk, BS_E);
                 __syncthreads();
-                uint32_t total = 0, before[BS_E];
-#pragma unroll
-                for (uint32_t j = 0; j < BS_E; j++) {
-                    before[j] = 0;
-#pragma unroll
-                    for (uint32_t w = 0; w < SK_NW; w++) {
-                        const uint32_t c = s_cnt[0][j * SK_NW + w];
-                        if (w == wave) before[j] = total;
-                        total += c;
-                    }
-                }
+                uint32_t before[BS_E];
+                const uint32_t total = slot_counts_sum(BS_E, before);
 #pragma unroll
                 for (uint32_t j = 0; j < BS_E; j++) {
                     if ((mk[j] >> lane) & 1ull) {
@@ -1549,8 +1604,8 @@ __global__ __launch_bounds__(SK_NT, SK_WAVES_PER_SIMD) void bzx_bfill_kernel(Bzx
 // leftover groups -- all inside one bucket -- are refined by the ranks of the rotations h and 2h symbols ahead (h = the
 // block's smallest give-up depth, times three every round: two gathers per tied rank buy a third fewer visits of it,
 // and the fixed cost of a bucket's round -- list in, barriers, list out -- is what the rounds are made of): the
-// refinement round of the sort kernel with [ISA[(rotation + h) mod n], ISA[(rotation + 2h) mod n]] in place of the next
-// 50 key bits, on the compact list.
+// group-ordering step of the sort kernel's refinement rounds (list_big_groups .. place_ranked) on round words made of
+// [ISA[(rotation + h) mod n], ISA[(rotation + 2h) mod n]] instead of the next 50 key bits, on the compact list.
 //   before      : a bucket that gives up (sort kernel) enters the group-head rank of each of its ranks into rank array
 //                 0, and the ranks that are alone in their group into array 1 too.
 //   round r     : ONE launch.  A bucket loads its list, gathers from rank array r & 1, orders its groups, enters the
@@ -1604,42 +1659,7 @@ __device__ __forceinline__ uint32_t rk_fetch_chunk(const BzxBatch &B, uint32_t n
     return s_fetch[0];
 }
 
-// Exclusive prefix of `v` over the slots c = j * SK_NT + tid of the workgroup in slot order (one bit per slot):
-// keep[j] = bit mask of my wave's row j.  Returns the total; before[j] = kept slots before my row j.  Two barriers.
-__device__ __forceinline__ uint32_t slot_prefix(const uint64_t *keep, uint32_t nrow, uint32_t *before)
-{
-    const uint32_t lane = bzx_lane(), wave = bzx_wave();
-    __syncthreads();
-#pragma unroll
-    for (uint32_t j = 0; j < BS_E; j++)
-        if (j < nrow && lane == 0) s_cnt[0][j * SK_NW + wave] = (uint32_t)__popcll(keep[j]);
-    __syncthreads();
-    uint32_t total = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < BS_E; j++) {
-        before[j] = 0;
-        if (j < nrow) {
-#pragma unroll
-            for (uint32_t w = 0; w < SK_NW; w++) {
-                const uint32_t c = s_cnt[0][j * SK_NW + w];
-                if (w == wave) before[j] = total;
-                total += c;
-            }
-        }
-    }
-    return total;
-}
-
 __shared__ uint32_t s_stall[2 * BS_FW];       // rank rounds: group starts whose group leaves the rounds (one bit per slot)
-
-// Slot at which the group of slot c starts (slot 0 starts a group).
-__device__ __forceinline__ uint32_t group_start(uint32_t c)
-{
-    uint32_t wi = c >> 6;
-    uint64_t w = s_f[wi] & (~0ull >> (63u - (c & 63u)));
-    while (!w) w = s_f[--wi];
-    return wi * 64 + 63u - (uint32_t)__builtin_clzll(w);
-}
 
 // One rank round of a bucket whose list has at most 64 entries, by ONE wave (slot = lane; no workgroup barrier, no
 // flag words: the group starts are a ballot).  Most buckets of real data give up over a handful of pairs, and a
@@ -1881,101 +1901,22 @@ __global__ __launch_bounds__(SK_NT, SK_WAVES_PER_SIMD) void bzx_brank_round_kern
                 if (tid == 0) atomicAdd(&B.blk[b].n_groups, 1u);       // (never closed: the block stays in resume state)
             }
         }
-#pragma unroll
-        for (uint32_t j = 0; j < BS_E; j++) {
-            if ((hmask >> j) & 1u) {
-                const uint32_t c = j * SK_NT + tid;
-                uint32_t wi = c >> 6;
-                uint64_t w = (s_f[wi] >> (c & 63u)) >> 1;
-                uint32_t e;
-                if (w) {
-                    e = c + 1u + (uint32_t)__builtin_ctzll(w);
-                } else {
-                    do w = s_f[++wi]; while (!w);
-                    e = wi * 64 + (uint32_t)__builtin_ctzll(w);
-                }
-                const uint32_t size = e - c;
-                if (size > BS_MED) s_large[atomicAdd(&s_rc[0][2], 1u)] = c | (size << 16);
-                else if (size > BS_TINY) s_med[atomicAdd(&s_rc[0][1], 1u)] = c | (size << 16);
-            }
-        }
+        // ---- the group-ordering step of a round (see list_big_groups): the slot is the rank
+        const auto slot_of = [&](uint32_t j) { return j * SK_NT + tid; };
+        list_big_groups(hmask, 0, slot_of);
 #pragma unroll
         for (uint32_t j = 0; j < BS_E; j++)
             if ((tmask >> j) & 1u) s_w[j * SK_NT + tid] = g[j] | (uint64_t)(j * SK_NT + tid);
         __syncthreads();
         const uint32_t nmed = s_rc[0][1], nlarge = s_rc[0][2];
-        if (nmed | nlarge) {
-            for (;;) {
-                uint32_t k = 0;
-                if (lane == 0) k = atomicAdd(&s_rc[0][3], 1u);
-                k = __shfl(k, 0);
-                if (k >= nmed) break;
-                const uint32_t e = s_med[k], gs = e & 0xFFFFu, sz = e >> 16;
-                wave_sort_mark(gs, sz, 48, lane);
-                lds_order();
-                if (__ballot(any_big(gs, sz, lane, 64))) wave_sort_mark(gs, sz, 14, lane);
-            }
-            for (uint32_t k = 0; k < nlarge; k++) {
-                const uint32_t e = s_large[k], gs = e & 0xFFFFu, sz = e >> 16;
-                wg_radix_sort<1>(gs, sz, 48, 64);
-                mark_changes(gs, sz, 48, tid, SK_NT);
-                if (tid == 0) s_bc[2] = 0;
-                __syncthreads();
-                if (any_big(gs, sz, tid, SK_NT)) s_bc[2] = 1;
-                __syncthreads();
-                if (s_bc[2]) {
-                    wg_radix_sort<1>(gs, sz, 14, 64);
-                    mark_changes(gs, sz, 14, tid, SK_NT);
-                }
-            }
-            __syncthreads();
-        }
+        if (nmed | nlarge) sort_listed_groups(0, nmed, nlarge, tid, lane);
         tid = tid_here();
         lane = tid & 63u;
         wave = tid >> 6;
-        // groups of up to BS_TINY slots: every lane ranks its own word among its group's
         uint32_t dst_[BS_E];
         uint64_t my[BS_E];
-#pragma unroll
-        for (uint32_t j = 0; j < BS_E; j++) {
-            dst_[j] = 0xFFFFFFFFu;
-            my[j] = 0;
-            uint32_t a_ = 0, sz = 0;
-            if ((tmask >> j) & 1u) {
-                const uint32_t c = j * SK_NT + tid;
-                uint32_t e_;
-                if (tiny_bounds(c, a_, e_) && e_ - a_ > 1) {
-                    sz = e_ - a_;
-                    my[j] = s_w[c];
-                }
-            }
-            if (j < nrow) {
-                uint32_t r = 0, rk = 0;                   // (see the sort kernel's counting tier)
-                const uint64_t myc = my[j] & ~W_POS_MASK;
-                for (uint32_t i2 = 0; i2 < sz; i2 += 4) {
-                    uint64_t wq[4];
-#pragma unroll
-                    for (uint32_t k = 0; k < 4; k++) wq[k] = s_w[a_ + i2 + k];          // (past the group: read, not counted)
-#pragma unroll
-                    for (uint32_t k = 0; k < 4; k++) {
-                        const bool in = i2 + k < sz;
-                        r += in && wq[k] < my[j];
-                        rk += in && wq[k] < myc;
-                    }
-                }
-                if (sz) dst_[j] = (a_ + r) | (r != rk ? 0u : 0x80000000u);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t j = 0; j < BS_E; j++) {
-            if (dst_[j] != 0xFFFFFFFFu) {
-                const uint32_t q = dst_[j] & 0x7FFFFFFFu;
-                s_w[q] = my[j];
-                if ((dst_[j] >> 31) && !fbit(q)) fset(q);
-            }
-        }
-        __syncthreads();
+        rank_tiny_groups(tmask, nrow, slot_of, dst_, my);
+        place_ranked(dst_, my);
         // ---- the new state of every slot that was tied: its rotation, its group's head rank into the array being
         // written; a slot that is alone now is settled (last column, general sorter's entry, row of rotation 0)
         const uint8_t *__restrict__ Tx = BZX_BLOCK_PTR(B, B.blk[b]);
@@ -1991,10 +1932,7 @@ __global__ __launch_bounds__(SK_NT, SK_WAVES_PER_SIMD) void bzx_brank_round_kern
             if ((tmask >> j) & 1u) {
                 const uint32_t rot = (uint32_t)s_x[(uint32_t)(s_w[c] & W_POS_MASK)] & 0xFFFFFu;
                 const uint32_t f0 = fbit(c), f1 = fbit(c + 1), pc = LIST(0, c);
-                uint32_t wi = c >> 6;
-                uint64_t w = s_f[wi] & (~0ull >> (63u - (c & 63u)));
-                while (!w) w = s_f[--wi];                          // (slot 0 starts a group)
-                const uint32_t hc = wi * 64 + 63u - (uint32_t)__builtin_clzll(w);
+                const uint32_t hc = group_start(c);
                 if ((smask >> j) & 1u) {                           // leaves the rounds, coarse
                     isa_r[rot] = isa_w[rot] = (start + LIST(0, hc)) | RK_COARSE;
                     sax[pc] = (uint64_t)rot | ((uint64_t)f0 << 32);
@@ -2014,7 +1952,10 @@ __global__ __launch_bounds__(SK_NT, SK_WAVES_PER_SIMD) void bzx_brank_round_kern
             keep[j] = __ballot(kp);
         }
         uint32_t before[BS_E];
-        const uint32_t Tn = slot_prefix(keep, nrow, before);
+        __syncthreads();
+        slot_counts_publish(keep, nrow);
+        __syncthreads();
+        const uint32_t Tn = slot_counts_sum(nrow, before);
 #pragma unroll
         for (uint32_t j = 0; j < BS_E; j++)
             if (j < nrow && ((keep[j] >> lane) & 1ull)) cl[before[j] + (uint32_t)__popcll(keep[j] & ((1ull << lane) - 1ull))] = out[j];
