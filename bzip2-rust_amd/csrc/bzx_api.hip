@@ -197,6 +197,10 @@ extern "C" void bzx_ctx_destroy(bzx_ctx *ctx)
     if (ctx->split_ws) (void)hipFree(ctx->split_ws);
     if (ctx->batch_ws) (void)hipFree(ctx->batch_ws);
     if (ctx->dbatch_ws) (void)hipFree(ctx->dbatch_ws);
+    if (ctx->range_ws) (void)hipFree(ctx->range_ws);
+    if (ctx->range_pin) (void)hipHostFree(ctx->range_pin);
+    for (int i = 0; i < 2; i++)
+        if (ctx->range_io[i]) (void)hipFree(ctx->range_io[i]);
     for (int i = 0; i < 2; i++)
         if (ctx->dbatch_pin[i]) (void)hipHostFree(ctx->dbatch_pin[i]);
     if (ctx->h_blk) (void)hipHostFree(ctx->h_blk);

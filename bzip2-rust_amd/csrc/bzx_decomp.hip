@@ -399,6 +399,230 @@ __global__ __launch_bounds__(64) void bzx_dc_walk_kernel(BzxBatch B, uint8_t *__
     B.blk[b].pack_word = out;                  // expanded length
 }
 
+// ---- the many-lane walk: one WORKGROUP per block (range reads: one to three blocks, nothing to hide the chase behind) --
+// Leaves what bzx_dc_walk_kernel leaves -- IMG[0, n), the checkpoints, pack_word, the status -- for ANY L: the scatter
+// makes T a permutation whatever L is, but one with several cycles when L is no BWT (or the BWT of u^k), and the
+// one-lane walk then goes round the cycle of its start for n steps.
+//   splitters   the walk's start p0 and every position that is a multiple of DW_STRIDE (a test on the position: no
+//               marks).  The segments between splitters partition the cycles that hold one, so all walks together
+//               take at most n steps, and each ends: a splitter's own cycle leads back to it.
+//   phase A     a lane walks from a splitter to the next one it meets and records how many steps that took and which
+//               splitter it met; lanes take splitters from an LDS counter until none is left.  The loop body is ONE
+//               step: a lane that arrives takes its next splitter inside the same loop, so the lanes of a wave do not
+//               wait for the longest segment among them.
+//   phase B     one lane follows the splitters from the start until it is back there (at most n / DW_STRIDE + 2 LDS
+//               reads) and turns the lengths into offsets; c, their sum, is the length of the start's cycle.
+//   phase C     the lanes walk the segments of that cycle again and store their bytes at their offsets; then
+//               IMG[i] = IMG[i mod c] for the rest.
+// The RLE1 checkpoints are a pass of their own over IMG (bzx_dc_ckpt_kernel).
+#define DW_NT 1024
+#define DW_STRIDE 64u
+#define DW_MAX_S ((BZX_MAX_N + DW_STRIDE - 1) / DW_STRIDE + 1)
+#define DW_ON_CHAIN 0x80000000u
+
+__global__ __launch_bounds__(DW_NT) void bzx_dc_wide_walk_kernel(BzxBatch B, uint8_t *__restrict__ img_slabs)
+{
+    __shared__ uint32_t s_len[DW_MAX_S];       // A: steps to the next splitter; B: DW_ON_CHAIN | offset of the segment
+    __shared__ uint16_t s_nxt[DW_MAX_S];       // A: the splitter met
+    __shared__ uint32_t s_fetch[2];            // work counters of phases A and C
+    __shared__ uint32_t s_bad, s_cyc;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    if (B.blk[b].status) return;               // (uniform over the workgroup)
+    const uint32_t n = B.blk[b].n;
+    const uint32_t *__restrict__ W = reinterpret_cast<const uint32_t *>(B.rec_a + (size_t)b * BZX_MAX_N);
+    uint8_t *IMG = img_slabs + (size_t)b * BZX_BLK_STRIDE;
+    const uint32_t orig = B.blk[b].orig_ptr;
+    const uint32_t p0 = orig < n ? W[orig] >> 8 : n;
+    const uint32_t nsplit = (n + DW_STRIDE - 1) / DW_STRIDE + 1;       // splitter 0: p0; 1 + q: position q * DW_STRIDE
+    if (tid == 0) {
+        s_fetch[0] = 0;
+        s_fetch[1] = 0;
+        s_bad = p0 >= n ? 1u : 0u;
+        s_cyc = 0;
+    }
+    __syncthreads();
+    volatile uint32_t *bad = &s_bad;
+    auto pos_of = [&](uint32_t s) { return s ? (s - 1u) * DW_STRIDE : p0; };
+    auto id_of = [&](uint32_t pos) { return pos == p0 ? 0u : 1u + pos / DW_STRIDE; };
+    auto is_split = [&](uint32_t pos) { return pos == p0 || (pos & (DW_STRIDE - 1u)) == 0; };
+    // ---- A
+    {
+        uint32_t s = 0, pos = 0, len = 0;
+        auto next = [&]() {                    // my next splitter; false: none left
+            for (;;) {
+                s = atomicAdd(&s_fetch[0], 1u);
+                if (s >= nsplit || *bad) return false;
+                pos = pos_of(s);
+                len = 0;
+                if (s && pos == p0) {          // the start is a multiple of the stride too: it is splitter 0
+                    s_len[s] = 0;
+                    s_nxt[s] = 0;
+                    continue;
+                }
+                return true;
+            }
+        };
+        bool live = next();
+        while (live) {
+            pos = W[pos] >> 8;
+            len++;
+            if (pos >= n || len > n) {         // no permutation (cannot follow from a decoded block): the block is refused
+                *bad = 1;
+                break;
+            }
+            if (is_split(pos)) {
+                s_len[s] = len;
+                s_nxt[s] = (uint16_t)id_of(pos);
+                live = next();
+            }
+        }
+    }
+    __syncthreads();
+    // ---- B
+    if (tid == 0 && !*bad) {
+        uint32_t s = 0, off = 0, steps = 0;
+        do {
+            const uint32_t len = s_len[s];
+            if ((len & DW_ON_CHAIN) || off + len > n) {
+                *bad = 1;
+                break;
+            }
+            s_len[s] = DW_ON_CHAIN | off;
+            off += len;
+            s = s_nxt[s];
+        } while (s != 0 && ++steps < nsplit);
+        s_cyc = off;
+    }
+    __syncthreads();
+    if (*bad) {
+        if (tid == 0) {
+            B.blk[b].status = DC_ERR_DATA;
+            B.blk[b].pack_word = 0;
+        }
+        return;
+    }
+    // ---- C
+    {
+        uint32_t pos = 0, off = 0;
+        auto next = [&]() {
+            for (;;) {
+                const uint32_t s = atomicAdd(&s_fetch[1], 1u);
+                if (s >= nsplit) return false;
+                const uint32_t v = s_len[s];
+                if (!(v & DW_ON_CHAIN)) continue;          // a splitter of another cycle
+                off = v & ~DW_ON_CHAIN;
+                pos = pos_of(s);
+                return true;
+            }
+        };
+        bool live = next();
+        while (live) {
+            const uint32_t e = W[pos];
+            if (off < n) IMG[off] = (uint8_t)e;
+            off++;
+            pos = e >> 8;
+            if (is_split(pos)) live = next();
+        }
+    }
+    __syncthreads();                           // the cycle's bytes are stored (and visible to this workgroup)
+    const uint32_t c = s_cyc;
+    for (uint32_t i = c + tid; i < n; i += DW_NT) IMG[i] = IMG[i % c];
+}
+
+__device__ __forceinline__ void dc_rle1_step(uint32_t ch, uint32_t &last, uint32_t &cnt, uint32_t &out)
+{
+    if (cnt == 4) {
+        out += ch;
+        cnt = 0;
+        last = 256;
+    } else {
+        cnt = ch == last ? cnt + 1 : 1;
+        last = ch;
+        out++;
+    }
+}
+
+// The RLE1 state machine over IMG[k0, k1), 16 bytes per load where the address allows it.
+__device__ static void dc_rle1_run(const uint8_t *__restrict__ IMG, uint32_t k0, uint32_t k1, uint32_t &last, uint32_t &cnt,
+                                   uint32_t &out)
+{
+    uint32_t k = k0;
+    while (k < k1 && ((uintptr_t)(IMG + k) & 15u)) dc_rle1_step(IMG[k++], last, cnt, out);
+    for (; k + 16 <= k1; k += 16) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(IMG + k);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++) dc_rle1_step((w[i >> 2] >> ((i & 3u) * 8u)) & 255u, last, cnt, out);
+    }
+    while (k < k1) dc_rle1_step(IMG[k++], last, cnt, out);
+}
+
+// One workgroup per block, one lane per 4096-byte segment of the image: the checkpoints, the expanded length and the
+// "ends in four equal bytes" status, from IMG alone.  The RLE1 state at a segment's start depends on the bytes before
+// it, but not on many of them: after three bytes a != b != c the state is (last = c, run = 1) whatever came before
+// (c is no count byte, since a != b; if b was one, a run starts afresh at c; if not, c differs from it).  A lane looks
+// for such a place in the segment before its own and runs the state machine from there.  Where the segment before has
+// none -- stretches of one byte -- the state is carried over from the segment before that, one lane going through the
+// segments in order.
+__global__ __launch_bounds__(256) void bzx_dc_ckpt_kernel(BzxBatch B, const uint8_t *__restrict__ img_slabs)
+{
+    __shared__ uint32_t s_state[256];
+    __shared__ uint32_t s_scan[4];
+    const uint32_t b = blockIdx.x, g = threadIdx.x;
+    if (B.blk[b].status) return;               // (uniform over the workgroup)
+    const uint32_t n = B.blk[b].n;
+    const uint32_t seg_len = 1u << DC_CK_SHIFT;
+    const uint32_t nseg = (n + seg_len - 1) >> DC_CK_SHIFT;            // <= 220
+    const uint8_t *__restrict__ IMG = img_slabs + (size_t)b * BZX_BLK_STRIDE;
+    DcCheck *__restrict__ CK = reinterpret_cast<DcCheck *>(B.gbits + (size_t)b * BZX_SEL_STRIDE);
+    const uint32_t k0 = g << DC_CK_SHIFT;
+    const uint32_t unknown = 0xFFFFFFFFu;
+    uint32_t st = unknown;
+    if (g == 0) st = 256u;
+    else if (g < nseg) {
+        for (uint32_t j = k0; j >= k0 - seg_len + 3; j--) {
+            const uint32_t x = IMG[j - 3], y = IMG[j - 2], z = IMG[j - 1];
+            if (x != y && y != z) {
+                uint32_t last = z, cnt = 1, out = 0;
+                dc_rle1_run(IMG, j, k0, last, cnt, out);
+                st = last | (cnt << 9);
+                break;
+            }
+        }
+    }
+    s_state[g] = st;
+    __syncthreads();
+    if (g == 0) {
+        for (uint32_t q = 1; q < nseg; q++)
+            if (s_state[q] == unknown) {
+                uint32_t last = s_state[q - 1] & 0x1FFu, cnt = s_state[q - 1] >> 9, out = 0;
+                dc_rle1_run(IMG, (q - 1) << DC_CK_SHIFT, q << DC_CK_SHIFT, last, cnt, out);
+                s_state[q] = last | (cnt << 9);
+            }
+    }
+    __syncthreads();
+    uint32_t last = 256, cnt = 0, out = 0;
+    if (g < nseg) {
+        st = s_state[g];
+        last = st & 0x1FFu;
+        cnt = st >> 9;
+        dc_rle1_run(IMG, k0, k0 + seg_len < n ? k0 + seg_len : n, last, cnt, out);
+    }
+    uint32_t total = 0;
+    const uint32_t before = bzx_block_excl_sum<256>(out, s_scan, total);
+    if (g < nseg) {
+        DcCheck c;
+        c.out_pos = before;
+        c.state = st;
+        CK[g] = c;
+    }
+    if (g == nseg - 1) {
+        // four equal bytes end the block: libbz2 reads their count byte past the block's end and refuses the stream
+        if (cnt == 4) B.blk[b].status = DC_ERR_DATA;
+        B.blk[b].pack_word = total;
+    }
+}
+
 // grid (segments, blocks): expands one 4096-byte segment of the RLE1 image from its checkpoint to dst[b].p (at most
 // dst[b].cap bytes from there; a null dst[b].p: the block is not written).
 __global__ __launch_bounds__(64) void bzx_dc_expand_kernel(BzxBatch B, const uint8_t *__restrict__ img_slabs,
@@ -457,6 +681,16 @@ void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t strea
     hipLaunchKernelGGL(bzx_dc_scatter_kernel, dim3(32, B.nblk), dim3(256), 0, stream, B);
     hipLaunchKernelGGL(bzx_dc_pack_kernel, dim3(32, B.nblk), dim3(256), 0, stream, B);
     hipLaunchKernelGGL(bzx_dc_walk_kernel, dim3((B.nblk + 63) / 64), dim3(64), 0, stream, B, img_slabs);
+}
+// The same contract with the many-lane walk: one workgroup per block (range reads: bzx_range.hip).  n_hint: about the
+// length of the longest block; it sizes the grids of the two grid-stride kernels and nothing else.
+void bzx_launch_dc_ibwt_wide(const BzxBatch &B, uint8_t *img_slabs, uint32_t n_hint, hipStream_t stream)
+{
+    const uint32_t tiles = n_hint >= 32 * 256 ? 32u : n_hint / 256 + 1;
+    hipLaunchKernelGGL(bzx_dc_scatter_kernel, dim3(tiles, B.nblk), dim3(256), 0, stream, B);
+    hipLaunchKernelGGL(bzx_dc_pack_kernel, dim3(tiles, B.nblk), dim3(256), 0, stream, B);
+    hipLaunchKernelGGL(bzx_dc_wide_walk_kernel, dim3(B.nblk), dim3(DW_NT), 0, stream, B, img_slabs);
+    hipLaunchKernelGGL(bzx_dc_ckpt_kernel, dim3(B.nblk), dim3(256), 0, stream, B, img_slabs);
 }
 void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const BzxDcDst *dst, hipStream_t stream)
 {

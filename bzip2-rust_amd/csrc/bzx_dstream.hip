@@ -92,7 +92,8 @@ __global__ __launch_bounds__(64) void bzx_ds_chain_kernel(BzxBatch B, const uint
                                                          uint64_t base_bit, uint32_t final,
                                                          const uint64_t *__restrict__ cand, uint32_t c0, uint32_t c1,
                                                          uint64_t chain_bit, uint32_t comb, uint32_t level,
-                                                         uint32_t *__restrict__ chain, DsRec *__restrict__ rec)
+                                                         uint32_t *__restrict__ chain, DsRec *__restrict__ rec,
+                                                         uint32_t *__restrict__ meta)
 {
     const uint32_t lane = threadIdx.x;
     const uint64_t wbits = wlen * 8;
@@ -147,6 +148,7 @@ __global__ __launch_bounds__(64) void bzx_ds_chain_kernel(BzxBatch B, const uint
                 }
                 if (lane == i) mine_on_chain = true;
                 if (lane == 0) chain[nch] = slab_i;
+                if (lane == 0 && meta) meta[nch] = level | (streams << 4);      // (the index: bzx_ds_index_kernel)
                 nch++;
                 comb = crc_fold(comb, crc_i);                             // stored CRCs
                 at_bit = base_bit + end_i;
@@ -277,7 +279,37 @@ __global__ __launch_bounds__(64) void bzx_ds_verdict_kernel(BzxBatch B, const ui
     }
 }
 
+// ---- the index: what an entry needs of the chain blocks a pass placed, next to the pass's record ----------------------
+struct DsIxRec {
+    uint64_t bit;                  // the block's magic, bit of the whole input
+    uint32_t out_len, crc;         // expanded length, stored CRC
+    uint32_t img_bits;             // from the magic to the bit behind the last symbol
+    uint32_t meta;                 // level | streams finished in the round before the block << 4
+};
+
+__global__ __launch_bounds__(64) void bzx_ds_index_kernel(BzxBatch B, const uint32_t *__restrict__ chain,
+                                                         const uint32_t *__restrict__ meta, uint64_t base_bit,
+                                                         const DsRec *__restrict__ rec, DsIxRec *__restrict__ out)
+{
+    const uint32_t j0 = rec->pass_j0, j1 = rec->placed;
+    for (uint32_t j = j0 + threadIdx.x; j < j1; j += 64) {
+        const BzxBlock &d = B.blk[chain[j]];
+        DsIxRec r;
+        r.bit = base_bit + d.out_bit;
+        r.out_len = (uint32_t)d.pack_word;
+        r.crc = d.crc;
+        r.img_bits = (uint32_t)(d.bits - d.out_bit);
+        r.meta = meta[j];
+        out[j - j0] = r;
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
+struct bzx_index {
+    bzx_dstream *s = nullptr;
+    std::vector<bzx_index_entry> entries;
+};
+
 struct DsSlot {                    // an output staging area: the verified bytes of one pass
     uint64_t bytes = 0, off = 0;   // bytes of the pass, bytes of them delivered
     bool arrived = false;          // its copy-back has been awaited
@@ -325,6 +357,10 @@ struct bzx_dstream {
     std::string pend_text, err_text;
     bzx_dstream_info info = {};
     float ms = 0.f;
+    // index mode (bzx_index_*): nothing is copied back or handed out; the placed blocks' figures come with the record
+    bzx_index *ix = nullptr;
+    uint32_t *d_meta = nullptr;
+    DsIxRec *d_ix = nullptr, *h_ix = nullptr;
 };
 
 extern "C" void bzx_dstream_end(bzx_dstream *s)
@@ -356,6 +392,9 @@ extern "C" void bzx_dstream_end(bzx_dstream *s)
     if (s->d_got) (void)hipFree(s->d_got);
     if (s->d_rec) (void)hipFree(s->d_rec);
     if (s->h_rec) (void)hipHostFree(s->h_rec);
+    if (s->d_meta) (void)hipFree(s->d_meta);
+    if (s->d_ix) (void)hipFree(s->d_ix);
+    if (s->h_ix) (void)hipHostFree(s->h_ix);
     if (s->ev_h2d) (void)hipEventDestroy(s->ev_h2d);
     if (s->ev_carry) (void)hipEventDestroy(s->ev_carry);
     if (s->s_h2d) (void)hipStreamDestroy(s->s_h2d);
@@ -364,7 +403,8 @@ extern "C" void bzx_dstream_end(bzx_dstream *s)
     delete s;
 }
 
-extern "C" int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **out)
+// index: the stream of a bzx_index -- one output staging area, none on the host, and the tables of the entries.
+static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bzx_dstream **out)
 {
     if (!ctx || !out) return BZX_E_PARAM;
     *out = nullptr;
@@ -394,9 +434,13 @@ extern "C" int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **o
     };
     bool ok = true;
     for (int i = 0; i < 2 && ok; i++)
-        ok = dmal((void **)&s->d_in[i], s->in_cap) && dmal((void **)&s->d_stage[i], DS_STAGE_BYTES) &&
-             hmal((void **)&s->h_stage[i], DS_STAGE_BYTES) &&
+        ok = dmal((void **)&s->d_in[i], s->in_cap) && (index && i ? true : dmal((void **)&s->d_stage[i], DS_STAGE_BYTES)) &&
+             (index || hmal((void **)&s->h_stage[i], DS_STAGE_BYTES)) &&
              hipEventCreateWithFlags(&s->ev_d2h[i], hipEventDisableTiming) == hipSuccess;
+    if (index)                                               // (zeroed: a pass copies the whole R-entry table back and
+        ok = ok && dmal((void **)&s->d_meta, R * 4) &&       // writes the entries of the blocks it placed only)
+             dmal((void **)&s->d_ix, R * sizeof(DsIxRec)) && hmal((void **)&s->h_ix, R * sizeof(DsIxRec)) &&
+             hipMemset(s->d_ix, 0, R * sizeof(DsIxRec)) == hipSuccess;
     ok = ok && dmal((void **)&s->d_cand, (size_t)s->cap_cand * 8) && hmal((void **)&s->h_cand, (size_t)s->cap_cand * 8) &&
          dmal((void **)&s->d_ncand, 64) && hmal((void **)&s->h_ncand, 64) && dmal((void **)&s->d_src, R * sizeof(BzxDcSrc)) &&
          hmal((void **)&s->h_src, R * sizeof(BzxDcSrc)) && dmal((void **)&s->d_dst, R * sizeof(BzxDcDst)) &&
@@ -417,6 +461,11 @@ extern "C" int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **o
     ctx->ds = s;
     *out = s;
     return BZX_OK;
+}
+
+extern "C" int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **out)
+{
+    return ds_begin(ctx, max_chunk, false, out);
 }
 
 extern "C" int bzx_dstream_get_info(const bzx_dstream *s, bzx_dstream_info *out)
@@ -541,7 +590,8 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
             bzx_launch_dc_decode(B, s->d_src, st);
         }
         hipLaunchKernelGGL(bzx_ds_chain_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8,
-                           s->wfinal ? 1u : 0u, s->d_cand, c0, c1, s->chain_bit, s->comb, s->level, s->d_chain, s->d_rec);
+                           s->wfinal ? 1u : 0u, s->d_cand, c0, c1, s->chain_bit, s->comb, s->level, s->d_chain, s->d_rec,
+                           s->d_meta);
         if (nb) bzx_launch_dc_ibwt(B, ctx->d_in, st);
     } else {
         B.nblk = s->rd_nb;
@@ -557,6 +607,13 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
         bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
         hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_dst, s->d_got, s->d_stage[q],
                            s->d_rec);
+        if (s->ix) {
+            hipLaunchKernelGGL(bzx_ds_index_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_meta, s->wbase * 8, s->d_rec,
+                               s->d_ix);
+            // (the round's share of the table; the pass wrote its first placed - pass_j0 entries, the host reads
+            // r.good <= that many, the rest is what bzx_index_begin zeroed or an earlier pass left)
+            HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, nb * sizeof(DsIxRec), hipMemcpyDeviceToHost, st));
+        }
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(s->h_rec, s->d_rec, sizeof(DsRec), hipMemcpyDeviceToHost, st));
@@ -570,7 +627,22 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
         s->rd = r;
         s->rd_active = true;
     }
-    if (r.good_bytes) {                                      // the verified bytes travel beside the next pass
+    if (s->ix) {                                             // the verified blocks become entries; their bytes stay
+        for (uint32_t j = 0; j < r.good; j++) {
+            const DsIxRec &x = s->h_ix[j];
+            bzx_index_entry e;
+            memset(&e, 0, sizeof(e));
+            e.bit = x.bit;
+            e.out_off = s->info.out_bytes;
+            e.out_len = x.out_len;
+            e.crc = x.crc;
+            e.img_bits = x.img_bits;
+            e.stream = s->info.nstreams + (x.meta >> 4);
+            e.level = (uint8_t)(x.meta & 15u);
+            s->ix->entries.push_back(e);
+            s->info.out_bytes += x.out_len;
+        }
+    } else if (r.good_bytes) {                               // the verified bytes travel beside the next pass
         HIP_TRY(ctx, hipMemcpyAsync(s->h_stage[q], s->d_stage[q], r.good_bytes, hipMemcpyDeviceToHost, s->s_d2h));
         HIP_TRY(ctx, hipEventRecord(s->ev_d2h[q], s->s_d2h));
         s->slot[q].bytes = r.good_bytes;
@@ -748,5 +820,120 @@ extern "C" int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, 
         s->err_rc = rc;
         s->err_text = ctx->err;
     }
+    return rc;
+}
+
+// ---- bzx_index_*: the same machine with nothing handed out ------------------------------------------------------------
+extern "C" void bzx_index_end(bzx_index *ix)
+{
+    if (!ix) return;
+    if (ix->s) {
+        ix->s->ix = nullptr;
+        bzx_dstream_end(ix->s);
+    }
+    delete ix;
+}
+
+extern "C" int bzx_index_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out)
+{
+    if (!ctx || !out) return BZX_E_PARAM;
+    *out = nullptr;
+    bzx_index *ix = new (std::nothrow) bzx_index();
+    if (!ix) return BZX_E_NOMEM;
+    const int rc = ds_begin(ctx, max_chunk, true, &ix->s);
+    if (rc) {
+        delete ix;
+        return rc;
+    }
+    ix->s->ix = ix;
+    *out = ix;
+    return BZX_OK;
+}
+
+extern "C" int bzx_index_feed(bzx_index *ix, const uint8_t *bz2, size_t len, int final, size_t *consumed, int *done)
+{
+    if (!ix || !ix->s || !ix->s->ctx || !consumed || !done || (len && !bz2)) return BZX_E_PARAM;
+    bzx_dstream *s = ix->s;
+    bzx_ctx *ctx = s->ctx;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    *consumed = 0;
+    *done = 0;
+    if (s->err_rc) {
+        ctx->err = s->err_text;
+        return s->err_rc;
+    }
+    if (s->done) {                                           // bytes behind the last stream: counted, not looked at
+        s->info.in_bytes += len;
+        *consumed = len;
+        *done = 1;
+        return BZX_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    bool copied = false;
+    size_t produced = 0;
+    int rc;
+    try {
+        rc = ds_feed(s, bz2, len, final, consumed, nullptr, 0, &produced, done, &copied);
+    } catch (const std::bad_alloc &) {                       // (nothing may unwind across the C ABI)
+        ctx->err = "out of host memory";
+        rc = BZX_E_NOMEM;
+    }
+    if (copied && hipStreamSynchronize(s->s_h2d) != hipSuccess && !rc) {
+        ctx->err = "hipStreamSynchronize(input copy) failed";
+        rc = BZX_E_HIP;
+    }
+    if (rc && !s->err_rc) {
+        s->err_rc = rc;
+        s->err_text = ctx->err;
+    }
+    return rc;
+}
+
+extern "C" int bzx_index_get(const bzx_index *ix, const bzx_index_entry **entries, bzx_index_info *info)
+{
+    if (!ix || !ix->s || !ix->s->ctx || !entries || !info) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(ix->s->ctx->api_mu);
+    *entries = ix->entries.data();
+    memset(info, 0, sizeof(*info));
+    info->in_bytes = ix->s->info.in_bytes;
+    info->out_bytes = ix->s->info.out_bytes;
+    info->nblk = ix->entries.size();
+    info->nstreams = ix->s->info.nstreams;
+    return BZX_OK;
+}
+
+extern "C" int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries,
+                                      uint64_t cap_entries, bzx_index_info *info)
+{
+    if (!ctx || !info || (len && !bz2) || (cap_entries && !entries)) return BZX_E_PARAM;
+    memset(info, 0, sizeof(*info));
+    bzx_index *ix = nullptr;
+    int rc = bzx_index_begin(ctx, std::min<size_t>(std::max<size_t>(len, DS_MIN_CHUNK), (size_t)64 << 20), &ix);
+    if (rc) return rc;
+    size_t pos = 0;
+    int done = 0;
+    while (!rc && !(done && pos == len)) {
+        size_t used = 0;
+        rc = bzx_index_feed(ix, bz2 + pos, len - pos, 1, &used, &done);
+        pos += used;
+        if (!rc && !used && !done) {                         // (a final feed consumes or finishes)
+            ctx->err = "bzx_index_build_buffer: the feed loop made no progress";
+            rc = BZX_E_STATE;
+        }
+    }
+    const bzx_index_entry *e = nullptr;
+    const std::string why = ctx->err;
+    if (bzx_index_get(ix, &e, info) == BZX_OK) {
+        const uint64_t k = std::min<uint64_t>(info->nblk, cap_entries);
+        if (k) memcpy(entries, e, (size_t)k * sizeof(bzx_index_entry));
+        if (!rc && info->nblk > cap_entries) {
+            rc = BZX_E_OUTBUF;
+            bzx_index_end(ix);
+            ctx->err = "bzx_index_build_buffer: more blocks than cap_entries";
+            return rc;
+        }
+    }
+    bzx_index_end(ix);
+    if (rc) ctx->err = why;
     return rc;
 }

@@ -87,6 +87,13 @@ struct bzx_ctx {
     size_t dbatch_ws_bytes = 0;
     void *dbatch_pin[2] = {nullptr, nullptr};   // [0] candidates and round tables, [1] the _buffer form's bounce buffer
     size_t dbatch_pin_bytes[2] = {0, 0};
+
+    // range reads (bzx_decompress_range_*): the two edge staging areas and the round tables, allocated by the first call
+    void *range_ws = nullptr;
+    void *range_pin = nullptr;
+    uint32_t range_slabs = 0;                   // blocks the round tables hold
+    void *range_io[2] = {nullptr, nullptr};     // the _buffer form's span [0] and output [1] on the device, grown on demand
+    size_t range_io_bytes[2] = {0, 0};
 };
 
 #define HIP_TRY(ctx, expr)                                                                       \
@@ -231,5 +238,6 @@ uint64_t bzx_split_scan_words(uint64_t n);
 // ---- bzx_decomp.hip: the decoder's kernels, over any set of blocks (one-shot and batch: bzx_dbatch.hip; bzx_dstream.hip)
 void bzx_launch_dc_decode(const BzxBatch &B, const BzxDcSrc *src, hipStream_t stream);
 void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t stream);
+void bzx_launch_dc_ibwt_wide(const BzxBatch &B, uint8_t *img_slabs, uint32_t n_hint, hipStream_t stream);   // one workgroup per block
 void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const BzxDcDst *dst, hipStream_t stream);
 void bzx_launch_dc_crc(const BzxBatch &B, const BzxDcDst *dst, uint32_t *got, uint32_t n_cu, hipStream_t stream);

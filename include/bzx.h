@@ -350,6 +350,94 @@ int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, 
 void bzx_dstream_end(bzx_dstream *s);
 int bzx_dstream_get_info(const bzx_dstream *s, bzx_dstream_info *out);
 
+/*
+ * Block index and random access: "bytes [off, off + want) of what this .bz2 decodes to" without decoding what lies
+ * before them.  bzip2 blocks are independent and start at any bit; an index entry says where a block starts, what it
+ * decodes to and where that lies in the output.
+ *
+ * bzx_index_*: one entry per VERIFIED block of the input, in input order, over all streams of a concatenated .bz2.
+ * It is the streaming decoder's state machine (scan, chain, rounds, passes; bzx_dstream_* above) with nothing copied
+ * back: every block is decoded, expanded on the device and its CRC compared, and an entry exists only for a block whose
+ * CRC matched.  Same edge rules: concatenated streams are followed, trailing bytes that begin no stream are ignored,
+ * randomised blocks and blocks longer than 100000 x level are refused; an empty stream adds no entry and counts in
+ * nstreams.  A damaged input gives BZX_E_DATA with the texts of bzx_dstream_feed; bzx_index_get then still returns the
+ * entries of the verified prefix.  Device memory as for bzx_dstream_* (one output staging area instead of two, no
+ * page-locked staging); between begin and end the context is busy as with an open bzx_dstream.
+ *   feed: as bzx_dstream_feed without the output; *done = 1 once the last stream has been verified (bytes fed after
+ *   that are counted in in_bytes and ignored).
+ *   get: entries and totals so far; the pointer is valid until the next feed or bzx_index_end.
+ *   bzx_index_build_buffer: begin, a loop over feed, end.  More blocks than cap_entries: BZX_E_OUTBUF with info->nblk =
+ *   entries needed (the first cap_entries are written).  After BZX_E_DATA entries and info describe the verified prefix.
+ *
+ * Stored form (bzx --index writes FILE.bz2.bzxi), little-endian: a 64-byte header -- bytes 0..3 "BZXI", 4..7 version
+ * (1), 8..15 in_bytes, 16..23 out_bytes, 24..31 nblk, 32..35 nstreams, 36..63 zero -- followed by nblk entries of 40
+ * bytes laid out as the struct below.
+ */
+typedef struct {
+    uint64_t bit;        /* bit offset of the block magic from the start of the input */
+    uint64_t out_off;    /* decoded bytes of the whole input before this block */
+    uint32_t out_len;    /* decoded bytes of this block (at most 259/5 x 900,000) */
+    uint32_t crc;        /* stored block CRC */
+    uint32_t img_bits;   /* bits from the magic to the bit after the block's last symbol */
+    uint32_t stream;     /* ordinal of the stream the block belongs to */
+    uint8_t level;       /* 1..9 of that stream */
+    uint8_t reserved[7];
+} bzx_index_entry;       /* 40 bytes, little-endian when stored */
+typedef struct { uint64_t in_bytes, out_bytes; uint64_t nblk; uint32_t nstreams, reserved; } bzx_index_info;
+typedef struct bzx_index bzx_index;
+int bzx_index_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out);
+int bzx_index_feed(bzx_index *ix, const uint8_t *bz2, size_t len, int final, size_t *consumed, int *done);
+int bzx_index_get(const bzx_index *ix, const bzx_index_entry **entries, bzx_index_info *info);
+void bzx_index_end(bzx_index *ix);
+int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries, uint64_t cap_entries,
+                           bzx_index_info *info);
+/*
+ * bzx_index_span (host only, no context): which entries and which input bytes the range [off, off + want) needs:
+ * entries [*first, *first + *count) and input bytes [*byte_lo, *byte_hi) -- from the byte that holds the first block's
+ * magic to the last block's img_bits, rounded up to a byte, + 8 (inside the file: a block is followed by ten bytes of
+ * end-of-stream marker and CRC at least).  The range is clipped at the end of the output; an empty one gives
+ * *count = 0.  BZX_E_PARAM: NULL pointers, or entries that are not in output order.
+ *
+ * bzx_decompress_range_device / _buffer.  The rule: out[0, *got) equals bytes [off, off + want) of what
+ * bzx_decompress_buffer returns for the whole input, clipped at its end (off >= out_bytes or want == 0: *got = 0,
+ * BZX_OK).  bz2[0, len) holds input bytes [base, base + len): the whole file (base 0) or just the span;
+ * BZX_E_PARAM when it does not cover the span.  No magic scan: the covering entries say where the blocks are.
+ * Every touched block is decoded in full, and before a byte leaves its expanded length is held against out_len and its
+ * computed CRC against the CRC stored in the block and against entry.crc.  BZX_E_DATA with "index does not match the
+ * input: ..." (no block magic at `bit`, another stored CRC, another decoded length or block size), the damaged-block
+ * or the "block CRC mismatch in block N" text otherwise (N: the entry's number); *got = 0, and _buffer has not
+ * written out (_device may have written d_out).  Blocks wholly inside the range expand at their final place in d_out,
+ * the at most two edge blocks into device staging areas of 259/5 x 900,000 bytes each, from which the slice is copied;
+ * _buffer uploads the span only and brings back one slice.  A range of more blocks than the context holds slabs runs
+ * in rounds of that many blocks, one host synchronisation each.  Device memory: the span and at most `want` bytes of
+ * output (_buffer: two buffers of 4 MiB at least that the context keeps and grows, so a small read allocates nothing),
+ * the two staging areas (kept by the context from the first call on) and the context's slabs (a context holds 16 at
+ * least from bzx_ctx_create on, about 450 MB, whatever max_blocks said; a range read never adds to them);
+ * nothing depends on the length of the file.  d_bz2 and d_out may have any alignment.  The inverse BWT of these calls
+ * is the many-lane walk (one workgroup per block; bzx_stage_ibwt below), since one to three blocks have nothing to hide
+ * a one-lane pointer chase behind.  bzx_get_stats afterwards: nblk (blocks decoded) and raw_bytes (*got).
+ */
+int bzx_index_span(const bzx_index_entry *e, uint64_t n, uint64_t off, uint64_t want, uint64_t *first, uint64_t *count,
+                   uint64_t *byte_lo, uint64_t *byte_hi);
+int bzx_decompress_range_device(bzx_ctx *ctx, const void *d_bz2, size_t len, uint64_t base, const bzx_index_entry *e,
+                                uint64_t n, uint64_t off, uint64_t want, void *d_out, size_t *got);
+int bzx_decompress_range_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint64_t base, const bzx_index_entry *e,
+                                uint64_t n, uint64_t off, uint64_t want, uint8_t *out, size_t *got);
+/*
+ * The inverse BWT alone, for the parity tests (host pointers): L[0, n) and orig_ptr < n -> the RLE1 image img_out[0, n)
+ * and its expansion raw_out (at most raw_cap bytes are written; *raw_len is the whole expanded length).  wide = 0 runs
+ * the one-lane walk of the one-shot, batch and stream decoders, wide = 1 the many-lane walk of the range reads; both
+ * leave the same image, checkpoints, length and *status (0x200: the image ends in four equal bytes, which libbz2
+ * refuses) for ANY L, a BWT or not.
+ */
+int bzx_stage_ibwt(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t orig_ptr, int wide, uint8_t *img_out,
+                   uint8_t *raw_out, size_t raw_cap, uint64_t *raw_len, uint32_t *status);
+/* For the probes: the kernels of either walk alone (scatter, pack, walk; the checkpoint pass of the many-lane one) over
+ * `copies` copies of that block side by side, under HIP events; *ms_best = the best of `reps` launches.  The context
+ * grows to `copies` slabs. */
+int bzx_stage_ibwt_time(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t orig_ptr, int wide, uint32_t copies,
+                        uint32_t reps, float *ms_best);
+
 /* Per-call telemetry of the last bzx_compress_device/_buffer/_blocks/_batch_* call. */
 typedef struct {
     uint32_t nblk;

@@ -1,0 +1,591 @@
+"""Block index (bzx_index_*), range reads (bzx_decompress_range_*) and the many-lane inverse-BWT walk behind them.
+
+The rules: the index has one entry per verified block and is the same however the input is cut into feed calls; a range
+read returns bytes [off, off + want) of what libbz2 decodes the whole input to (bz2.decompress(z)[off:off + want]),
+from the whole file or from the bytes bzx_index_span names alone; the many-lane walk (bzx_stage_ibwt, wide = 1) leaves
+what the one-lane walk leaves, for any L.
+CPU part (-m "not gpu"): everything through the fiber emulator (tests/emu), small inputs.
+GPU part (-m gpu): the product library on cuda:0, real sizes."""
+import bz2
+import ctypes as C
+import os
+import random
+import subprocess
+
+import pytest
+
+import bz2_writer as W
+from bzx_ctypes import EMU_PATH, ROOT
+from bzx_dstream_ctypes import dstream_decode
+from bzx_range_ctypes import IndexEntry, RangeLib
+
+BZX_OK, BZX_E_PARAM, BZX_E_OUTBUF, BZX_E_STATE, BZX_E_DATA = 0, -2, -4, -6, -7
+BLOCK_MAGIC = bytes.fromhex("314159265359")
+DC_ERR_DATA = 0x200
+
+
+@pytest.fixture(scope="module")
+def emu():
+    csrc = os.path.join(ROOT, "bzip2-rust_amd", "csrc")
+    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(ROOT, "tests", "emu", "hip", "hip_runtime.h")]
+    if not os.path.exists(EMU_PATH) or any(os.path.getmtime(s) > os.path.getmtime(EMU_PATH) for s in srcs):
+        subprocess.check_call(["bash", os.path.join(ROOT, "tests", "emu", "build_emu.sh")])
+    lib = RangeLib(EMU_PATH, max_blocks=16)
+    yield lib
+    lib.close()
+
+
+def text(o, n, seed=1):
+    return o.synthtext(n, seed=0x9E3779B97F4A7C15 + seed)
+
+
+def ptext(o, n, period=700, seed=1):
+    return (text(o, period, seed) * (n // period + 1))[:n]
+
+
+def few(o, n, seed=1, letters=b"acgt"):
+    """n bytes over a few letters, no four equal in a row (an RLE1 image that stands for itself).  The emulator pays for
+    every bit the block decoder reads, and a small alphabet keeps a block's coding tables short."""
+    out = bytearray()
+    for c in text(o, 2 * n + 8, seed):
+        c = letters[c % len(letters)]
+        if len(out) >= 3 and out[-1] == out[-2] == out[-3] == c:
+            continue
+        out.append(c)
+    assert len(out) >= n
+    return bytes(out[:n])
+
+
+def text_class(msg):
+    """What kind of refusal an error text names (as tests/test_dstream.py)."""
+    if "randomised" in msg:
+        return "randomised"
+    if "CRC" in msg:
+        return "crc"
+    return "structure"
+
+
+# ---- 1. the walk ------------------------------------------------------------------------------------------------------
+def py_walk(L, orig):
+    """The contract in a few lines: T from L (a stable counting sort), n steps from T[orig], RLE1 expanded.
+    -> (image, expansion, ends in four equal bytes)"""
+    n = len(L)
+    T = sorted(range(n), key=lambda i: (L[i], i))
+    p, img = T[orig], bytearray()
+    for _ in range(n):
+        img.append(L[p])
+        p = T[p]
+    raw, last, cnt = bytearray(), -1, 0
+    for ch in img:
+        if cnt == 4:
+            raw += bytes([last]) * ch
+            last, cnt = -1, 0
+        else:
+            cnt = cnt + 1 if ch == last else 1
+            last = ch
+            raw.append(ch)
+    return bytes(img), bytes(raw), cnt == 4
+
+
+def walk_cases(o, n, rnd):
+    """(name, L, orig_ptr) at image length n."""
+    out = []
+
+    def bwt(name, img):
+        L, orig = o.bwt(img)
+        out.append((name, L, orig))
+    bwt("text", text(o, n, 60 + n % 7))
+    bwt("one byte", b"z" * n)
+    for unit in (2, 3, 7, 61, 500):
+        if unit < n:
+            bwt(f"u^k, unit {unit}", (text(o, unit, unit) * (n // unit + 1))[:n - n % unit] or b"ab")
+    if n >= 8:
+        bwt("ends in four equal bytes", text(o, n - 4, 3) + b"qqqq")
+        run = (b"abcd" + b"e" * 4 + b"\xff") * (n // 9 + 1)                  # runs of 4 + 255
+        bwt("runs of 4 + 255", run[:n])
+    if n > 9000:
+        # stretches of one byte that cross several 4096-byte segments of the image, between text
+        img = text(o, 700, 5) + b"\0" * 9000 + text(o, 300, 6) + b"\0" * 4 + b"\x07" + b"k" * 8200
+        bwt("long stretches", (img + text(o, n, 7))[:n])
+        out.append(("image with long stretches, as L", (b"\0" * 9001 + b"ab" + b"c" * 8300 + text(o, n, 8))[:n], n // 3))
+    for k in range(4):                                                       # no BWT at all
+        alpha = (2, 5, 256, 3)[k]
+        out.append((f"random L, {alpha} values", bytes(rnd.randrange(alpha) for _ in range(n)), rnd.randrange(n)))
+    return out
+
+
+def check_walk(lib, name, L, orig, slow_reference=True):
+    a = lib.stage_ibwt(L, orig, 0)
+    b = lib.stage_ibwt(L, orig, 1)
+    assert a[2:] == b[2:], (name, len(L), a[2:], b[2:])                      # raw_len, status
+    assert a[0] == b[0] and a[1] == b[1], (name, len(L))                     # img, raw
+    if slow_reference:
+        img, raw, four = py_walk(L, orig)
+        assert b[0] == img and b[2] == len(raw) and b[3] == (DC_ERR_DATA if four else 0), (name, len(L))
+        if not four:
+            assert b[1] == raw, (name, len(L))
+    return b
+
+
+def test_emu_wide_walk_parity(emu, oracle):
+    rnd = random.Random(11)
+    n_random = 0
+    for n in (1, 2, 63, 64, 65, 4095, 4096, 4097, 20011):
+        for name, L, orig in walk_cases(oracle, n, rnd):
+            check_walk(emu, name, L, orig)
+            n_random += name.startswith("random")
+    # more random L with random orig_ptr: at least 50 in all
+    for k in range(30):
+        n = rnd.choice((5, 100, 1000, 3000, 6000))
+        alpha = rnd.choice((1, 2, 3, 16, 256))
+        check_walk(emu, "random", bytes(rnd.randrange(alpha) for _ in range(n)), rnd.randrange(n))
+        n_random += 1
+    assert n_random >= 50
+    st = check_walk(emu, "four", *oracle.bwt(b"xyz" + b"q" * 4))
+    assert st[3] == DC_ERR_DATA
+    # arguments
+    assert emu.lib.bzx_stage_ibwt(emu.ctx, b"ab", 2, 2, 1, C.create_string_buffer(2), None, 0, C.byref(C.c_uint64()),
+                                  C.byref(C.c_uint32())) == BZX_E_PARAM       # orig_ptr >= n
+
+
+# ---- 2. the index -----------------------------------------------------------------------------------------------------
+def index_inputs(o):
+    """(name, .bz2, [(bit of the block magic, decoded length, stored crc, stream, level)], streams)"""
+    out = []
+
+    def written(blocks, level):
+        f = {}
+        z = W.write_stream(o, blocks, level, fields=f)
+        return z, [(s, len(b.raw()), o.crc32(b.raw())) for (s, _), b in zip(f.get("magic", []), blocks)]
+
+    def found(z, parts):
+        """Streams of bz2.compress: one block each (or none), whose magic follows the header."""
+        exp, at = [], 0
+        for k, (raw, level) in enumerate(parts):
+            zz = bz2.compress(raw, level)
+            if raw:
+                assert zz[4:10] == BLOCK_MAGIC
+                exp.append((at * 8 + 32, len(raw), int.from_bytes(zz[10:14], "big"), k, level))
+            at += len(zz)
+        return exp
+    z, b = written([W.Block(few(o, 60, 4)), W.Block(few(o, 45, 5, b"xyz")), W.Block(few(o, 50, 6))], 1)
+    out.append(("multi-block BZh1", z, [x + (0, 1) for x in b], 1))
+    parts = [(few(o, 80, 7), 2), (b"", 9), (few(o, 40, 8, b"01") + b"2" * 30, 7)]
+    z = b"".join(bz2.compress(r, l) for r, l in parts)
+    out.append(("three streams, the middle one empty", z, found(z, parts), 3))
+    parts = [(few(o, 85, 9, b"lmnop"), 9)]
+    z = bz2.compress(*parts[0])
+    out.append(("trailing bytes with a stray magic", z + b"xy" + BLOCK_MAGIC + b"..BZh" + b"trailing bytes, no stream",
+                found(z, parts), 1))
+    z, b = written([W.Block(few(o, 48, 10)), W.Block(b"Q"), W.Block(few(o, 40, 11, b"uvw"))], 9)
+    out.append(("a one-byte block", z, [x + (0, 9) for x in b], 1))
+    return out
+
+
+def magic_at(z, bit):
+    v = int.from_bytes(z[bit // 8:bit // 8 + 7], "big")
+    return (v >> (8 - bit % 8)) & ((1 << 48) - 1) == int.from_bytes(BLOCK_MAGIC, "big")
+
+
+_built = {}
+
+
+def build(lib, z):
+    """bzx_index_build_buffer -> (entries, nblk, info), checked to be BZX_OK."""
+    key = (id(lib), bytes(z))
+    if key not in _built:
+        rc, entries, info = lib.index_build(z)
+        assert rc == 0, lib.last_error()
+        _built[key] = (entries, info.nblk, info)
+    return _built[key]
+
+
+def test_emu_index(emu, oracle):
+    for name, z, expect, nstreams in index_inputs(oracle):
+        want = bz2.decompress(z)
+        entries, n, info = build(emu, z)
+        keys = [entries[i].key() for i in range(n)]
+        assert (info.in_bytes, info.out_bytes, info.nblk, info.nstreams) == (len(z), len(want), len(expect), nstreams), name
+        off = 0
+        for (bit, out_off, out_len, crc, img_bits, stream, level), e in zip(keys, expect):
+            assert (bit, out_len, crc, stream, level) == e, (name, keys, expect)
+            assert magic_at(z, bit) and out_off == off
+            assert int.from_bytes(z[(bit + 48) // 8:(bit + 48) // 8 + 5], "big") >> (8 - (bit + 48) % 8) & 0xFFFFFFFF == crc
+            nxt = bit + img_bits                     # the next block's magic or the end-of-stream marker
+            v = int.from_bytes(z[nxt // 8:nxt // 8 + 7], "big") >> (8 - nxt % 8) & ((1 << 48) - 1)
+            assert v in (0x314159265359, 0x177245385090), name
+            off += out_len
+        # any cutting, several chunk sizes: the same index
+        for feeds in (1, 7, 4096, 0):
+            for max_chunk in ((16, 64, 1 << 16) if feeds == 7 else (64,) if feeds == 1 else (256, 0)):
+                rc, got, inf, _ = emu.index_feed(z, feeds, max_chunk)
+                assert rc == 0 and got == keys, (name, feeds, max_chunk, emu.last_error())
+                assert (inf.in_bytes, inf.out_bytes, inf.nblk, inf.nstreams) == (len(z), len(want), n, nstreams)
+    # too few entries: the number needed
+    name, z, expect, _ = index_inputs(oracle)[0]
+    rc, entries, info = emu.index_build(z, cap=1)
+    assert rc == BZX_E_OUTBUF and info.nblk == len(expect)
+    # an empty stream alone
+    rc, entries, info = emu.index_build(bz2.compress(b""))
+    assert rc == 0 and (info.nblk, info.nstreams, info.out_bytes) == (0, 1, 0)
+
+
+def test_emu_index_damaged(emu, oracle):
+    b = [W.Block(few(oracle, 70, 21)), W.Block(few(oracle, 60, 22, b"klmno")), W.Block(few(oracle, 50, 23))]
+    f = {}
+    z = W.write_stream(oracle, b, 1, fields=f)
+    good, n, _ = build(emu, z)
+    keys = [good[i].key() for i in range(n)]
+    flip = bytearray(z)
+    bit = f["payload"][1][0] + (f["payload"][1][1] - f["payload"][1][0]) // 2       # payload of the second block
+    flip[bit >> 3] ^= 0x80 >> (bit & 7)
+    cases = [("a payload bit of block 2 flipped", bytes(flip), 1, None),
+             ("truncated in block 3", z[:f["payload"][2][0] // 8 + 3], 2, "structure"),
+             ("a randomised block", W.write_stream(oracle, [b[0], W.Block(few(oracle, 40, 31), randomised=1)], 9), 1,
+              "randomised")]
+    for name, bad, verified, cls in cases:
+        # the same verdict and text class as bzx_dstream_feed's
+        rc1, _, _ = dstream_decode(emu, bad, 0, 1 << 20)
+        cls1 = text_class(emu.last_error())
+        for feeds, max_chunk in ((0, 0), (7, 64)):
+            rc, got, info, why = emu.index_feed(bad, feeds, max_chunk)
+            assert rc == rc1 == BZX_E_DATA and text_class(why) == cls1, (name, rc, why)
+            assert cls is None or cls1 == cls
+            assert len(got) == info.nblk == verified, (name, got)
+            if "randomised" not in name:
+                assert got == keys[:verified]
+            assert info.out_bytes == sum(k[2] for k in got)
+        rc, entries, info = emu.index_build(bad)
+        assert rc == BZX_E_DATA and info.nblk == verified and text_class(emu.last_error()) == cls1
+    # the context is as good as new
+    assert build(emu, bz2.compress(b"after the damage", 3))[1] == 1
+
+
+# ---- 3. range reads -----------------------------------------------------------------------------------------------------
+def range_plan(entries, n, total, rnd, count=200):
+    """Every range that starts or ends within 2 bytes of a block border, and `count` seeded random ones."""
+    borders = sorted({0, total} | {entries[i].out_off for i in range(n)})
+    plan = set()
+    for bd in borders:
+        for d in range(-2, 3):
+            p = bd + d
+            if p < 0:
+                continue
+            for w in (1, 3):
+                plan.add((p, w))                                     # starts there
+                if p - w >= 0:
+                    plan.add((p - w, w))                             # ends there
+            other = rnd.choice(borders)
+            lo, hi = min(p, other), max(p, other)
+            plan.add((lo, hi - lo))
+    plan |= {(0, 0), (5, 0), (total, 7), (total + 3, 7), (total - 1, 1), (total - 1, 100), (0, total), (0, total + 9)}
+    if n >= 2:                                                       # from the last bytes of one block / stream into the next
+        plan.add((entries[1].out_off - 3, 7))
+        plan.add((entries[n - 1].out_off - 1, 2))
+    out = sorted(plan)
+    for _ in range(count):
+        off = rnd.randrange(0, total + 2)
+        out.append((off, rnd.choice((1, 2, 9, 40, 100, total))))
+    return out
+
+
+def check_ranges(lib, z, want, entries, n, plan, rnd, how="alternate"):
+    """Every range of the plan through _buffer.  how: "both" = with the whole file and with the span alone, "span" = with
+    the span alone (base = byte_lo), "alternate" = one or the other by turns."""
+    assert how in ("both", "span", "alternate")
+    for k, (off, w) in enumerate(plan):
+        exp = want[off:off + w]
+        rc, first, count, lo, hi = lib.span(entries, n, off, w)
+        assert rc == 0 and (count == 0) == (not exp)
+        modes = {"both": ("file", "span"), "span": ("span",), "alternate": (("file", "span")[k % 2],)}[how]
+        for mode in modes:
+            if mode == "file" or not count:
+                rc, got, _, _ = lib.range_buffer(z, 0, entries, n, off, w)
+            else:
+                assert 0 <= lo < hi <= len(z)
+                rc, got, _, _ = lib.range_buffer(z[lo:hi], lo, entries, n, off, w)
+            assert rc == 0 and got == exp, (off, w, mode, rc, lib.last_error())
+
+
+def test_emu_range(emu, oracle):
+    rnd = random.Random(23)
+    for name, z, expect, _ in index_inputs(oracle):
+        want = bz2.decompress(z)
+        entries, n, info = build(emu, z)
+        plan = range_plan(entries, n, len(want), rnd)
+        assert len(plan) >= 200 + 5 * (n + 1)
+        check_ranges(emu, z, want, entries, n, plan, rnd, how="both")
+        st = emu.stats()
+        assert st.raw_bytes <= len(want)
+    # a range over two streams, asked for in so many words
+    name, z, expect, _ = index_inputs(oracle)[1]
+    entries, n, _ = build(emu, z)
+    assert n == 2 and entries[0].stream == 0 and entries[1].stream == 2
+    want = bz2.decompress(z)
+    rc, got, _, _ = emu.range_buffer(z, 0, entries, n, 70, 30)
+    assert rc == 0 and got == want[70:100] and entries[1].out_off == 80 and len(want) == 150
+
+
+def test_emu_range_rounds(emu, oracle):
+    """More blocks than the context holds slabs: rounds of 16."""
+    blocks = [W.Block(few(oracle, 12 + k % 5, 100 + k % 4, b"ab")) for k in range(37)]
+    z = W.write_stream(oracle, blocks, 9)
+    want = bz2.decompress(z)
+    entries, n, _ = build(emu, z)
+    assert n == 37
+    for off, w in ((0, len(want)), (7, len(want) - 12), (entries[2].out_off, entries[36].out_off - entries[2].out_off)):
+        rc, got, _, _ = emu.range_buffer(z, 0, entries, n, off, w)
+        assert rc == 0 and got == want[off:off + w], emu.last_error()
+        assert emu.stats().nblk == emu.span(entries, n, off, w)[2] > 32 and emu.stats().raw_bytes == len(got)
+
+
+def stale(entries, n, k, **change):
+    e = (IndexEntry * n)(*[entries[i] for i in range(n)])
+    for name, v in change.items():
+        setattr(e[k], name, v)
+    return e
+
+
+def test_emu_range_refusals(emu, oracle):
+    b = [W.Block(few(oracle, 70, 21)), W.Block(few(oracle, 60, 22, b"klmno")), W.Block(few(oracle, 50, 23))]
+    f = {}
+    z = W.write_stream(oracle, b, 1, fields=f)
+    want = bz2.decompress(z)
+    entries, n, _ = build(emu, z)
+    off, w = entries[1].out_off + 5, 20                                     # inside block 2
+    rc, first, count, lo, hi = emu.span(entries, n, off, w)
+    assert (rc, first, count) == (0, 1, 1)
+    assert lo == entries[1].bit // 8 and hi == (entries[1].bit + entries[1].img_bits + 7) // 8 + 8
+    # a span one byte too short, at either end
+    for zz, base in ((z[lo:hi - 1], lo), (z[lo + 1:hi], lo + 1), (z[:hi - 1], 0)):
+        rc, got, room, g = emu.range_buffer(zz, base, entries, n, off, w)
+        assert rc == BZX_E_PARAM and g == 0 and room == b"\xa5" * w, (rc, emu.last_error())
+    rc, got, _, _ = emu.range_buffer(z[lo:hi], lo, entries, n, off, w)
+    assert rc == 0 and got == want[off:off + w]
+    # a stale index
+    for name, e in (("bit", stale(entries, n, 1, bit=entries[1].bit + 1)), ("crc", stale(entries, n, 1, crc=entries[1].crc ^ 4)),
+                    ("out_len", stale(entries, n, 1, out_len=entries[1].out_len - 1)),
+                    ("out_len of the last block", stale(entries, n, 2, out_len=entries[2].out_len + 1))):
+        o2, w2 = (entries[2].out_off + 1, 9) if "last" in name else (off, w)
+        rc, got, room, g = emu.range_buffer(z, 0, e, n, o2, w2)
+        assert rc == BZX_E_DATA and g == 0 and room == b"\xa5" * w2, (name, rc, emu.last_error())
+        assert "index does not match the input" in emu.last_error(), (name, emu.last_error())
+    # a payload bit flipped inside the touched block; inside an untouched one
+    for blk, ok in ((1, False), (2, True), (0, True)):
+        bit = f["payload"][blk][0] + (f["payload"][blk][1] - f["payload"][blk][0]) // 2
+        bad = bytearray(z)
+        bad[bit >> 3] ^= 0x80 >> (bit & 7)
+        rc, got, room, g = emu.range_buffer(bytes(bad), 0, entries, n, off, w)
+        if ok:
+            assert rc == 0 and got == want[off:off + w], blk
+        else:
+            assert rc == BZX_E_DATA and g == 0 and room == b"\xa5" * w
+            msg = emu.last_error()
+            assert "index does not match the input" in msg or "block CRC mismatch in block 1" in msg or "damaged block" in msg
+    # a context with an open stream
+    s = emu.dstream(64)
+    try:
+        rc, got, room, g = emu.range_buffer(z, 0, entries, n, off, w)
+        assert rc == BZX_E_STATE and g == 0 and "bzx_dstream" in emu.last_error()
+        h = C.c_void_p()
+        assert emu.lib.bzx_index_begin(emu.ctx, 0, C.byref(h)) == BZX_E_STATE and not h.value
+        with pytest.raises(Exception):
+            emu.stage_ibwt(b"abc", 0, 1)
+    finally:
+        s.end()
+    # ... and with an open index
+    h = C.c_void_p()
+    assert emu.lib.bzx_index_begin(emu.ctx, 0, C.byref(h)) == 0
+    try:
+        assert emu.range_buffer(z, 0, entries, n, off, w)[0] == BZX_E_STATE
+        assert emu.decompress_one(z)[0] == BZX_E_STATE
+    finally:
+        emu.lib.bzx_index_end(h)
+    rc, got, _, _ = emu.range_buffer(z, 0, entries, n, off, w)
+    assert rc == 0 and got == want[off:off + w]
+    # NULL arguments
+    L = emu.lib
+    g = C.c_size_t()
+    assert L.bzx_decompress_range_buffer(None, z, len(z), 0, entries, n, 0, 5, C.create_string_buffer(5), C.byref(g)) == BZX_E_PARAM
+    assert L.bzx_decompress_range_buffer(emu.ctx, z, len(z), 0, entries, n, 0, 5, None, C.byref(g)) == BZX_E_PARAM
+    assert L.bzx_decompress_range_buffer(emu.ctx, z, len(z), 0, entries, n, 0, 5, C.create_string_buffer(5), None) == BZX_E_PARAM
+    assert L.bzx_index_span(entries, n, 0, 5, None, None, None, None) == BZX_E_PARAM
+    assert L.bzx_index_begin(None, 0, C.byref(h)) == BZX_E_PARAM and L.bzx_index_begin(emu.ctx, 0, None) == BZX_E_PARAM
+    L.bzx_index_end(None)
+
+
+# ---- GPU --------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def gpu16():
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.init()
+    lib = RangeLib(max_blocks=16)
+    yield lib
+    lib.close()
+
+
+@pytest.fixture(scope="module")
+def maker():
+    """A context of its own for making the inputs (compression grows a context's slabs)."""
+    lib = RangeLib(max_blocks=16)
+    yield lib
+    lib.close()
+
+
+@pytest.mark.gpu
+def test_gpu_wide_walk_parity(gpu16, oracle):
+    rnd = random.Random(31)
+    for n in (899_981, 900_000):
+        unit = text(oracle, 30_011, 71)
+        imgs = [("text", text(oracle, n, 70)), ("random bytes", oracle.randbytes(n)), ("zeros", bytes(n)),
+                ("u^k, unit 30,011", (unit * (n // len(unit)))), ("ends in four equal bytes", text(oracle, n - 4, 72) + b"qqqq")]
+        for name, img in imgs:
+            L, orig = gpu16.stage_bwt(img)[:2]
+            a = check_walk(gpu16, name, L, orig, slow_reference=False)
+            assert a[0] == img, name                                        # the inverse of the forward transform
+            assert a[3] == (DC_ERR_DATA if "four" in name else 0)
+        # no BWT at all
+        for alpha in (2, 256):
+            L = bytes(rnd.getrandbits(8) % alpha for _ in range(n))
+            check_walk(gpu16, f"random L, {alpha} values", L, rnd.randrange(n), slow_reference=False)
+    for n in (1, 2, 63, 64, 65, 4095, 4096, 4097, 20011):                   # the small shapes of the CPU part
+        for name, L, orig in walk_cases(oracle, n, rnd):
+            check_walk(gpu16, name, L, orig, slow_reference=n < 5000)
+
+
+def gpu_range_plan(entries, n, total, rnd, count=300):
+    """300 seeded random ranges of 1 B to 8 MiB and the border cases."""
+    plan = []
+    borders = sorted({0, total} | {entries[i].out_off for i in rnd.sample(range(n), min(n, 6))})
+    for bd in borders:
+        for d in (-2, -1, 0, 1, 2):
+            if 0 <= bd + d:
+                plan.append((bd + d, rnd.choice((1, 5, 70_000))))
+                if bd + d >= 3:
+                    plan.append((bd + d - 3, 3))
+    plan += [(0, 0), (total, 5), (total + 1, 5), (total - 1, 9)]
+    for k in range(count):
+        w = 1 << rnd.randrange(0, 24)
+        w = min(8 << 20, rnd.randrange(w, 2 * w))
+        plan.append((rnd.randrange(0, total), w))
+    return plan
+
+
+def device_ranges(lib, z, want, entries, n, plan):
+    """Through bzx_decompress_range_device: the whole file on the device, outputs at odd addresses."""
+    import torch
+    d_z = torch.frombuffer(bytearray(z), dtype=torch.uint8).cuda()
+    d_o = torch.empty((8 << 20) + 64, dtype=torch.uint8, device="cuda")
+    for k, (off, w) in enumerate(plan):
+        exp = want[off:off + w]
+        d_o.fill_(0xA5)
+        rc, got = lib.range_device_raw(d_z.data_ptr(), len(z), 0, entries, n, off, w, d_o.data_ptr() + (k % 3))
+        assert rc == 0 and got == len(exp), (off, w, rc, lib.last_error())
+        torch.cuda.synchronize()
+        back = d_o[k % 3:k % 3 + len(exp) + 1].cpu().numpy().tobytes()
+        assert back[:len(exp)] == exp and back[len(exp):] == b"\xa5", (off, w)
+
+
+def gpu_input(lib, maker, z, want, rnd, nblk_min, nstreams):
+    rc, entries, info = lib.index_build(z, cap=max(4096, len(z) // 2000))
+    assert rc == 0, lib.last_error()
+    n = info.nblk
+    assert (info.in_bytes, info.out_bytes, info.nstreams) == (len(z), len(want), nstreams) and n >= nblk_min
+    assert entries[n - 1].out_off + entries[n - 1].out_len == len(want)
+    plan = gpu_range_plan(entries, n, len(want), rnd)
+    check_ranges(lib, z, want, entries, n, plan, rnd, how="span")
+    device_ranges(lib, z, want, entries, n, plan)
+    return entries, n
+
+
+@pytest.mark.gpu
+def test_gpu_range_text(gpu16, maker, oracle):
+    rnd = random.Random(41)
+    raw = text(oracle, 64 << 20, 81)
+    for level in (9, 1):
+        z = maker.compress_buffer(raw, level)
+        assert bz2.decompress(z) == raw
+        s = gpu16.dstream(1 << 20)
+        slabs = s.info().slabs
+        s.end()
+        assert slabs == 16
+        entries, n = gpu_input(gpu16, maker, z, raw, rnd, len(raw) // (100000 * level), 1)
+        s = gpu16.dstream(1 << 20)                               # index build and range reads left the slabs alone
+        assert s.info().slabs == 16
+        s.end()
+        for i in range(n):
+            assert entries[i].level == level and entries[i].stream == 0
+    # more blocks than slabs, on a context created with max_blocks = 4 (it holds 16): the rounds
+    small = RangeLib(max_blocks=4)
+    try:
+        off, w = entries[3].out_off + 17, 40 * 99_000
+        rc, got, _, _ = small.range_buffer(z, 0, entries, n, off, w)
+        assert rc == 0 and got == raw[off:off + w], small.last_error()
+        assert small.stats().nblk > 16
+    finally:
+        small.close()
+
+
+@pytest.mark.gpu
+def test_gpu_range_concatenated_and_zeros(gpu16, maker, oracle):
+    rnd = random.Random(43)
+    parts = [text(oracle, 256 << 10, 90 + k) for k in range(64)]
+    z = b"".join(bz2.compress(p, 1 + k % 9) for k, p in enumerate(parts))
+    raw = b"".join(parts)
+    entries, n = gpu_input(gpu16, maker, z, raw, rnd, 64, 64)
+    assert sorted({entries[i].stream for i in range(n)}) == list(range(64))
+    # 256 MiB of zeros: a few hundred bytes of .bz2, blocks of about 45 MB each
+    total = 256 << 20
+    z = maker.compress_buffer(bytes(total), 9)
+    assert len(z) < 1000
+    rc, entries, info = gpu16.index_build(z)
+    assert rc == 0 and (info.out_bytes, info.nstreams) == (total, 1) and 5 <= info.nblk <= 8
+    n = info.nblk
+    plan = gpu_range_plan(entries, n, total, rnd)
+    for k, (off, w) in enumerate(plan):
+        rc, first, count, lo, hi = gpu16.span(entries, n, off, w)
+        exp = max(0, min(total, off + w) - off)
+        rc, got, _, _ = gpu16.range_buffer(z[lo:hi], lo, entries, n, off, w) if count else gpu16.range_buffer(z, 0, entries, n, off, w)
+        assert rc == 0 and got == bytes(exp), (off, w, rc, gpu16.last_error())
+    import torch
+    d_z = torch.frombuffer(bytearray(z), dtype=torch.uint8).cuda()
+    d_o = torch.empty((8 << 20) + 64, dtype=torch.uint8, device="cuda")
+    for off, w in plan:
+        exp = max(0, min(total, off + w) - off)
+        d_o.fill_(0xA5)
+        rc, got = gpu16.range_device_raw(d_z.data_ptr(), len(z), 0, entries, n, off, w, d_o.data_ptr())
+        assert rc == 0 and got == exp, gpu16.last_error()
+        torch.cuda.synchronize()
+        assert int(d_o[:exp].max()) == 0 if exp else True
+        assert int(d_o[exp]) == 0xA5
+
+
+@pytest.mark.gpu
+def test_gpu_range_refusals_and_small_shapes(gpu16, maker, oracle):
+    rnd = random.Random(47)
+    for name, z, expect, nstreams in index_inputs(oracle):
+        want = bz2.decompress(z)
+        rc, entries, info = gpu16.index_build(z)
+        assert rc == 0 and info.nblk == len(expect) and info.nstreams == nstreams
+        assert [entries[i].key()[0] for i in range(info.nblk)] == [e[0] for e in expect]
+        for feeds, max_chunk in ((1, 64), (7, 16), (0, 0)):
+            rc, got, inf, _ = gpu16.index_feed(z, feeds, max_chunk)
+            assert rc == 0 and got == [entries[i].key() for i in range(info.nblk)]
+        check_ranges(gpu16, z, want, entries, info.nblk, range_plan(entries, info.nblk, len(want), rnd, 60), rnd)
+    raw = text(oracle, 3 << 20, 95)
+    z = maker.compress_buffer(raw, 1)
+    rc, entries, info = gpu16.index_build(z)
+    n = info.nblk
+    assert rc == 0 and n >= 30
+    off, w = entries[10].out_off + 1000, 5000
+    bad = bytearray(z)
+    bad[(entries[10].bit + entries[10].img_bits // 2) // 8] ^= 0x10
+    rc, got, room, g = gpu16.range_buffer(bytes(bad), 0, entries, n, off, w)
+    assert rc == BZX_E_DATA and g == 0 and room == b"\xa5" * w
+    rc, got, _, _ = gpu16.range_buffer(bytes(bad), 0, entries, n, entries[11].out_off, w)        # the damage is elsewhere
+    assert rc == 0 and got == raw[entries[11].out_off:entries[11].out_off + w]
+    rc, got, room, g = gpu16.range_buffer(z, 0, stale(entries, n, 10, crc=1), n, off, w)
+    assert rc == BZX_E_DATA and g == 0 and "index does not match" in gpu16.last_error()
+    rc, info2 = gpu16.index_build(bytes(bad))[::2]
+    assert rc == BZX_E_DATA and info2.nblk == 10

@@ -9,12 +9,17 @@
 // bzx_decompress_batch_buffer (a file it does not accept is decoded again on its own, for the one-file path's message).
 // --devices LIST (HIP ordinals, comma-separated, repeats allowed): the chunked compression path deals its chunks over
 // these devices through bzx_mstream_feed, one process, host-side assembly; the bytes are the same.
+// --index FILE.bz2 ... writes FILE.bz2.bzxi, the block index of bzx_index_* (layout: include/bzx.h); -dc --range OFF:LEN
+// FILE.bz2 reads that index and only the bytes of the file that bzx_index_span names, and writes decoded bytes
+// [OFF, OFF + LEN) to standard output through bzx_decompress_range_buffer.  Without an index that matches the file it
+// refuses: there is no silent full decode behind --range.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <algorithm>
 #include <new>
 #include <string>
 #include <vector>
@@ -29,6 +34,8 @@ struct Opts {
     bool quiet = false;
     std::vector<std::string> files;
     std::vector<int> devices;          // --devices: entries of a bzx_mctx for the chunked compression path
+    bool index = false, range = false; // --index; --range OFF:LEN
+    uint64_t range_off = 0, range_len = 0;
 };
 
 static void help()
@@ -41,6 +48,8 @@ static void help()
          "  -q --quiet        no warnings               -v --verbose      statistics (-vv more)\n"
          "  -s --small        accepted, ignored         -h --help  -V --version  -L --license\n"
          "  --devices LIST    compress one stream on several devices: ordinals, comma-separated, repeats allowed\n"
+         "  --index           write FILE.bzxi, the block index of every FILE (a .bz2), for --range\n"
+         "  --range OFF:LEN   with -dc: decoded bytes [OFF, OFF + LEN) of FILE to standard output, through FILE.bzxi\n"
          "With no file, or when a file is -, reads standard input and writes standard output.");
 }
 
@@ -189,6 +198,173 @@ static int do_unzip(const Opts &o, bzx_ctx *ctx, FILE *in, const std::vector<uin
     bzx_dstream_end(ds);
     if (ibuf) bzx_host_free(ibuf);
     free(obuf);
+    return ret;
+}
+
+// ---- --index / --range ---------------------------------------------------------------------------------------------
+static void put_le(uint8_t *p, uint64_t v, int n)
+{
+    for (int i = 0; i < n; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+static uint64_t get_le(const uint8_t *p, int n)
+{
+    uint64_t v = 0;
+    for (int i = 0; i < n; i++) v |= (uint64_t)p[i] << (8 * i);
+    return v;
+}
+static const size_t BZXI_HEADER = 64, BZXI_ENTRY = 40;
+
+// FILE.bz2 -> FILE.bz2.bzxi through bzx_index_feed, 64 MiB chunks in page-locked memory as -d reads them.
+static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    const char *name = f.c_str();
+    FILE *in = fopen(name, "rb");
+    if (!in) {
+        if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", name, strerror(errno));
+        return 1;
+    }
+    const size_t CH = (size_t)64 << 20;
+    bzx_index *ix = nullptr;
+    int rc = bzx_index_begin(ctx, CH, &ix);
+    if (rc) {
+        fclose(in);
+        return fail(o, "cannot start", name, ctx, rc);
+    }
+    uint8_t *ibuf = (uint8_t *)bzx_host_alloc(CH);
+    int ret = ibuf ? 0 : fail(o, "out of memory", name, nullptr, BZX_E_NOMEM), done = 0;
+    size_t have = 0, off = 0;
+    bool eof = false;
+    while (!ret && !(done && eof && off == have)) {
+        if (off == have && !eof) {
+            have = fread(ibuf, 1, CH, in);
+            off = 0;
+            if (have < CH) {
+                if (ferror(in)) {
+                    ret = fail(o, strerror(errno), name, nullptr, BZX_OK);
+                    break;
+                }
+                eof = true;
+            }
+        }
+        size_t used = 0;
+        rc = bzx_index_feed(ix, ibuf + off, have - off, eof ? 1 : 0, &used, &done);
+        if (rc) {
+            ret = fail(o, "indexing failed", name, ctx, rc);
+            break;
+        }
+        off += used;
+    }
+    fclose(in);
+    const bzx_index_entry *e = nullptr;
+    bzx_index_info info;
+    if (!ret && (rc = bzx_index_get(ix, &e, &info))) ret = fail(o, "indexing failed", name, ctx, rc);
+    if (!ret) {
+        const std::string oname = f + ".bzxi";
+        FILE *out = fopen(oname.c_str(), "wb");
+        uint8_t head[BZXI_HEADER] = {'B', 'Z', 'X', 'I'}, rec[BZXI_ENTRY];
+        put_le(head + 4, 1, 4);
+        put_le(head + 8, info.in_bytes, 8);
+        put_le(head + 16, info.out_bytes, 8);
+        put_le(head + 24, info.nblk, 8);
+        put_le(head + 32, info.nstreams, 4);
+        bool ok = out && fwrite(head, 1, sizeof head, out) == sizeof head;
+        for (uint64_t k = 0; ok && k < info.nblk; k++) {
+            memset(rec, 0, sizeof rec);
+            put_le(rec, e[k].bit, 8);
+            put_le(rec + 8, e[k].out_off, 8);
+            put_le(rec + 16, e[k].out_len, 4);
+            put_le(rec + 20, e[k].crc, 4);
+            put_le(rec + 24, e[k].img_bits, 4);
+            put_le(rec + 28, e[k].stream, 4);
+            rec[32] = e[k].level;
+            ok = fwrite(rec, 1, sizeof rec, out) == sizeof rec;
+        }
+        if (out && fclose(out) != 0) ok = false;
+        if (!ok) {
+            if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
+            unlink(oname.c_str());
+            ret = 1;
+        } else if (o.verbose) {
+            fprintf(stderr, "  %s: %llu blocks in %u streams, %llu -> %llu bytes\n", oname.c_str(), (unsigned long long)info.nblk,
+                    info.nstreams, (unsigned long long)info.in_bytes, (unsigned long long)info.out_bytes);
+        }
+    }
+    bzx_index_end(ix);
+    if (ibuf) bzx_host_free(ibuf);
+    return ret;
+}
+
+static int range_refuse(const Opts &o, const std::string &f, const char *why)
+{
+    if (!o.quiet) fprintf(stderr, "bzx: %s: --range: %s\n", f.c_str(), why);
+    return 1;
+}
+
+// Decoded bytes [off, off + len) of FILE.bz2 to standard output, from FILE.bz2.bzxi and the span of the file alone.
+static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    const std::string iname = f + ".bzxi";
+    FILE *xf = fopen(iname.c_str(), "rb");
+    if (!xf) return range_refuse(o, f, ("no index " + iname + " (write it with bzx --index " + f + ")").c_str());
+    std::vector<uint8_t> x;
+    const bool xok = read_all(xf, x);
+    fclose(xf);
+    if (!xok || x.size() < BZXI_HEADER || memcmp(x.data(), "BZXI", 4) != 0 || get_le(x.data() + 4, 4) != 1)
+        return range_refuse(o, f, ("not a bzx index of version 1: " + iname).c_str());
+    const uint64_t in_bytes = get_le(x.data() + 8, 8), out_bytes = get_le(x.data() + 16, 8), nblk = get_le(x.data() + 24, 8);
+    if ((x.size() - BZXI_HEADER) / BZXI_ENTRY != nblk || (x.size() - BZXI_HEADER) % BZXI_ENTRY)
+        return range_refuse(o, f, ("truncated index " + iname).c_str());
+    FILE *in = fopen(f.c_str(), "rb");
+    struct stat sb;
+    if (!in || fstat(fileno(in), &sb) != 0) {
+        if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", f.c_str(), strerror(errno));
+        if (in) fclose(in);
+        return 1;
+    }
+    int ret = 0;
+    std::vector<bzx_index_entry> e;
+    std::vector<uint8_t> span, out;
+    uint64_t first = 0, count = 0, lo = 0, hi = 0;
+    size_t got = 0;
+    try {
+        e.resize(nblk);
+        for (uint64_t k = 0; k < nblk; k++) {
+            const uint8_t *r = x.data() + BZXI_HEADER + k * BZXI_ENTRY;
+            memset(&e[k], 0, sizeof(e[k]));
+            e[k].bit = get_le(r, 8);
+            e[k].out_off = get_le(r + 8, 8);
+            e[k].out_len = (uint32_t)get_le(r + 16, 4);
+            e[k].crc = (uint32_t)get_le(r + 20, 4);
+            e[k].img_bits = (uint32_t)get_le(r + 24, 4);
+            e[k].stream = (uint32_t)get_le(r + 28, 4);
+            e[k].level = r[32];
+        }
+        const uint64_t total = nblk ? e[nblk - 1].out_off + e[nblk - 1].out_len : 0;
+        if ((uint64_t)sb.st_size != in_bytes || total != out_bytes) {
+            ret = range_refuse(o, f, "the index does not match the file (another size): write it again with bzx --index");
+        } else if (bzx_index_span(e.data(), nblk, o.range_off, o.range_len, &first, &count, &lo, &hi)) {
+            ret = range_refuse(o, f, "the index does not match the file (entries out of order)");
+        } else if (count) {
+            if (hi > (uint64_t)sb.st_size) hi = (uint64_t)sb.st_size;
+            span.resize((size_t)(hi - lo));
+            out.resize((size_t)std::min<uint64_t>(o.range_len, out_bytes - o.range_off));
+            if (fseeko(in, (off_t)lo, SEEK_SET) != 0 || fread(span.data(), 1, span.size(), in) != span.size()) {
+                ret = fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK);
+            } else {
+                const int rc = bzx_decompress_range_buffer(ctx, span.data(), span.size(), lo, e.data(), nblk, o.range_off,
+                                                           o.range_len, out.data(), &got);
+                if (rc) ret = fail(o, "range read failed", f.c_str(), ctx, rc);
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        ret = fail(o, "out of memory", f.c_str(), nullptr, BZX_E_NOMEM);
+    }
+    fclose(in);
+    if (!ret && got && fwrite(out.data(), 1, got, stdout) != got) ret = fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK);
+    if (!ret && fflush(stdout) != 0) ret = 1;
+    if (!ret && o.verbose) fprintf(stderr, "  %s: bytes [%llu, %llu) from %llu blocks, %zu bytes of the file read\n", f.c_str(),
+                                   (unsigned long long)o.range_off, (unsigned long long)(o.range_off + got),
+                                   (unsigned long long)count, span.size());
     return ret;
 }
 
@@ -342,6 +518,20 @@ int main(int argc, char **argv)
             else if (a == "--small") {}
             else if (a == "--fast") o.level = 1;
             else if (a == "--best") o.level = 9;
+            else if (a == "--index") o.index = true;
+            else if (a == "--range" || a.rfind("--range=", 0) == 0) {
+                const std::string v = a == "--range" ? (i + 1 < argc ? argv[++i] : "") : a.substr(8);
+                const size_t c = v.find(':');
+                const std::string x = v.substr(0, c), y = c == std::string::npos ? "" : v.substr(c + 1);
+                if (x.empty() || y.empty() || x.size() > 19 || y.size() > 19 || x.find_first_not_of("0123456789") != std::string::npos ||
+                    y.find_first_not_of("0123456789") != std::string::npos) {
+                    fprintf(stderr, "bzx: --range takes OFF:LEN in bytes, e.g. 41000000000:65536 (got \"%s\")\n", v.c_str());
+                    return 1;
+                }
+                o.range = true;
+                o.range_off = strtoull(x.c_str(), nullptr, 10);
+                o.range_len = strtoull(y.c_str(), nullptr, 10);
+            }
             else if (a == "--devices" || a.rfind("--devices=", 0) == 0) {
                 std::string list = a == "--devices" ? (i + 1 < argc ? argv[++i] : "") : a.substr(10);
                 o.devices.clear();
@@ -379,6 +569,26 @@ int main(int argc, char **argv)
                 else { fprintf(stderr, "bzx: unexpected flag -%c\n", c); return 1; }
             }
         }
+    }
+    if (o.index || o.range) {
+        if (o.index && o.range) { fprintf(stderr, "bzx: --index and --range do not go together\n"); return 1; }
+        if (o.range && (o.mode != UNZIP || !o.to_stdout)) { fprintf(stderr, "bzx: --range goes with -dc\n"); return 1; }
+        if (o.files.empty() || (o.range && o.files.size() != 1)) {
+            fprintf(stderr, o.range ? "bzx: --range takes one file\n" : "bzx: --index takes files\n");
+            return 1;
+        }
+        for (const std::string &f : o.files)
+            if (f == "-") { fprintf(stderr, "bzx: --index and --range need a file that can be read again, not standard input\n"); return 1; }
+        bzx_ctx *ctx = nullptr;
+        const int rc = bzx_ctx_create(0, o.index ? UNZIP_SLABS : 0, &ctx);
+        if (rc) {
+            fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
+            return 2;
+        }
+        int ret = 0;
+        for (const std::string &f : o.files) ret |= o.index ? do_index(o, ctx, f) : do_range(o, ctx, f);
+        bzx_ctx_destroy(ctx);
+        return ret;
     }
     if (o.files.empty()) o.files.push_back("-");
     // two or more named files, without -v: the small regular ones go through the batched entry points
