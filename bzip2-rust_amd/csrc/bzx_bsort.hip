@@ -695,15 +695,15 @@ __global__ __launch_bounds__(BS_NT) void bzx_bsplit_deep_kernel(BzxBatch B)
 static_assert(BS_C % SK_NT == 0 && BS_E >= 1 && BS_E <= 8, "bucket capacity");
 
 __shared__ uint64_t s_x[BS_C];               // records, in rank order after the initial sort (never moved again)
-__shared__ uint64_t s_w[BS_C + 4];           // rank p: [current 50 key bits | index into s_x of the record ranked p:14] (+ read slack)
-__shared__ uint32_t s_cnt[SK_NW][SK_ND];     // per-wave digit counters
+__shared__ __attribute__((aligned(16))) uint64_t s_w[BS_C + 4];   // rank p: [current 50 key bits | index into s_x of the record ranked p:14] (+ read slack)
+__shared__ __attribute__((aligned(16))) uint32_t s_cnt[SK_NW][SK_ND];     // per-wave digit counters (read four at a time)
 __shared__ uint32_t s_dbase[SK_ND];
 __shared__ uint32_t s_part[4];
 __shared__ uint64_t s_f[BS_FW + 1];          // bit p: a group starts at rank p (all set from cnt on)
 __shared__ uint32_t s_med[BS_C / BS_TINY + 1];     // groups of 65..512: first rank | size << 16
 __shared__ uint32_t s_large[BS_C / BS_MED + 1];    // larger groups
 __shared__ uint32_t s_rc[2][4];              // per round (parity): [0] any rank tied, [1] #med, [2] #large, [3] med fetch
-__shared__ uint32_t s_bc[8];                 // [2] vote, [5..6] diff
+__shared__ uint32_t s_bc[8];                 // [2] vote, [3] result of the one-wave rounds, [5..6] diff
 __shared__ uint32_t s_m[2];                  // lengths of the two lists of tied ranks
 __shared__ uint32_t s_red[SK_NW][4];         // per wave: OR (lo, hi) and AND (lo, hi) of the bucket's records as loaded
 
@@ -851,7 +851,7 @@ __device__ __attribute__((noinline)) void wg_radix_sort(uint32_t base, uint32_t 
 __device__ __attribute__((noinline)) void wg_radix_sort_opt(uint32_t cnt, int lo, int hi)
 {
     uint64_t *A = s_x;
-    const uint32_t tid = threadIdx.x, lane = bzx_lane(), wave = bzx_wave();
+    const uint32_t lane = bzx_lane(), wave = bzx_wave();
     const uint32_t rows = (cnt + SK_NT - 1) / SK_NT, chunk = rows * 64;
     __syncthreads();                            // publishes s_x and the waves' OR / AND of their records (s_red)
     uint64_t diff;
@@ -867,6 +867,7 @@ __device__ __attribute__((noinline)) void wg_radix_sort_opt(uint32_t cnt, int lo
         diff = ((uint64_t)(o1 & ~a1) << 32) | (o0 & ~a0);        // bits on which the records differ
     }
     uint32_t *wc = s_cnt[wave];
+    uint32_t *wb = reinterpret_cast<uint32_t *>(s_w) + wave * SK_ND;      // my wave's digit starts (s_w is idle until the passes are done)
     for (int shift = lo; shift < hi; shift += SK_DB) {
         if (((diff >> shift) & (uint64_t)(SK_ND - 1)) == 0) continue;
 #pragma unroll
@@ -887,36 +888,43 @@ __device__ __attribute__((noinline)) void wg_radix_sort_opt(uint32_t cnt, int lo
         }
         __syncthreads();
         {
-            // exclusive start of every (digit, wave): one digit per thread, over waves first, then over digits; the
-            // digit's start is folded into the per-wave counters
-            static_assert(SK_ND <= SK_NT, "one digit per thread");
-            if (tid < SK_ND) {
-                uint32_t t[SK_NW], sum = 0;
+            // exclusive start of every (digit, wave), by every wave for itself: a lane takes four consecutive digits,
+            // sums them over the waves, and a scan over the wave gives the digits' starts; the wave keeps the starts
+            // of ITS records in its slice of s_w.  Nobody else reads that slice, so the scatter follows without a
+            // barrier.  (The counters are read by all waves until the barrier that ends the pass: a wave zeroes its
+            // own only after it.)
+            static_assert(SK_ND == 4 * 64, "four digits per lane");
+            uint32_t mine[4], tot[4], sum = 0;
 #pragma unroll
-                for (int w = 0; w < SK_NW; w++) {
-                    t[w] = s_cnt[w][tid];
-                    sum += t[w];
-                }
-                const uint32_t incl = bzx_wave_incl_sum(sum);
-                uint32_t run = incl - sum;
+            for (uint32_t i = 0; i < 4; i++) mine[i] = tot[i] = 0;
 #pragma unroll
-                for (int w = 0; w < SK_NW; w++) {
-                    s_cnt[w][tid] = run;
-                    run += t[w];
+            for (uint32_t w = 0; w < SK_NW; w++) {
+                const uint4 c = *reinterpret_cast<const uint4 *>(&s_cnt[w][4 * lane]);
+                const uint32_t cc[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+                for (uint32_t i = 0; i < 4; i++) {
+                    if (w < wave) mine[i] += cc[i];              // records of the waves before mine with this digit
+                    tot[i] += cc[i];
                 }
-                if (lane == 63) s_part[wave] = incl;
             }
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) sum += tot[i];
+            uint32_t run = bzx_wave_incl_sum(sum) - sum;
+            uint4 o;
+            o.x = run + mine[0];
+            run += tot[0];
+            o.y = run + mine[1];
+            run += tot[1];
+            o.z = run + mine[2];
+            run += tot[2];
+            o.w = run + mine[3];
+            *reinterpret_cast<uint4 *>(&wb[4 * lane]) = o;
         }
-        __syncthreads();
-        const uint32_t p1 = s_part[0], p2 = p1 + s_part[1], p3 = p2 + s_part[2];
+        lds_order();
 #pragma unroll
         for (uint32_t j = 0; j < BS_E; j++) {
             const uint32_t e = wave * chunk + j * 64 + lane;
-            if (j < rows && e < cnt) {
-                const uint32_t d = (uint32_t)(v[j] >> shift) & (SK_ND - 1);
-                const uint32_t q = d >> 6;                   // wave of the thread that scanned digit d
-                A[wc[d] + (q == 0 ? 0u : q == 1 ? p1 : q == 2 ? p2 : p3) + old[j]] = v[j];
-            }
+            if (j < rows && e < cnt) A[wb[(uint32_t)(v[j] >> shift) & (SK_ND - 1)] + old[j]] = v[j];
         }
         __syncthreads();
     }
@@ -1289,6 +1297,62 @@ __device__ __forceinline__ bool initial_sort(uint32_t cnt)
     return true;
 }
 
+// The refinement rounds of a bucket from the round on that starts with at most 64 tied ranks (on text: every round after
+// round 0), by ONE wave, entry = lane, all 64 lanes together: the same steps as a round of the workgroup -- gather,
+// counting tier, write-back, filtering of the list -- ordered by lds_order() alone, where the workgroup spends four
+// barriers on two or three entries.  All members of a tied group are on the list, so no group exceeds BS_TINY and
+// the tiers above the counting tier cannot be needed.  Runs until the list is empty or the bucket gives up
+// under the workgroup's own condition.  Returns the depth reached, with bit 31 set when the bucket gave up.  (Not inlined,
+// and nothing passed by reference: either raised the scratch use of the sort kernel.)
+__device__ __attribute__((noinline)) uint32_t wave_rounds(const uint8_t *__restrict__ P, uint32_t bits, uint32_t nbits, uint32_t m,
+                                                          uint32_t lpar, uint32_t round, uint32_t dcur)
+{
+    const uint32_t lane = bzx_lane();
+    for (;; round++) {
+        if (m == 0) return dcur;
+        if (!(round < BS_ROUNDS && dcur < nbits)) return dcur | 0x80000000u;
+        const bool has = lane < m;
+        uint32_t p = 0, gs = 0, ge = 0;
+        uint64_t my = 0;
+        if (has) {
+            p = LIST(lpar, lane);
+            const uint32_t pos = (uint32_t)(s_w[p] & W_POS_MASK);
+            uint32_t x = REC_IDX(s_x[pos]) * bits + dcur;
+            if (x >= nbits) x -= nbits;
+            my = (pk_window_bit(P, x) & ~W_POS_MASK) | pos;
+            tiny_bounds(p, gs, ge);
+        }
+        lds_order();
+        if (has) s_w[p] = my;
+        lds_order();
+        // r: members below my word (key, then position); rk: members below my key alone (see rank_tiny_groups)
+        uint32_t r = 0, rk = 0;
+        const uint64_t myc = my & ~W_POS_MASK;
+        const uint32_t sz = ge - gs;
+        for (uint32_t i = 0; __ballot(i < sz); i++) {
+            if (i < sz) {
+                const uint64_t o = s_w[gs + i];
+                r += o < my;
+                rk += o < myc;
+            }
+        }
+        lds_order();
+        if (has) {
+            const uint32_t q = gs + r;
+            s_w[q] = my;
+            if (r == rk && !fbit(q)) fset(q);              // first of its sub-group
+        }
+        lds_order();
+        const bool t = has && !(fbit(p) && fbit(p + 1));   // still tied
+        const uint64_t mk = __ballot(t);
+        if (t) LIST(lpar ^ 1u, (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))) = (uint16_t)p;
+        lds_order();
+        m = (uint32_t)__popcll(mk);
+        lpar ^= 1u;
+        dcur += 50;
+    }
+}
+
 #ifndef SK_WAVES_PER_SIMD
 #define SK_WAVES_PER_SIMD 4             // 128 VGPRs: no spills (at 80 the round loop spills ~40 registers to scratch)
 #endif
@@ -1386,7 +1450,8 @@ __device__ __forceinline__ void bsort_body(const BzxBatch &B)
             st_cur = uni(st_nx);
             continue;
         }
-        if (tid == 0) s_rc[0][0] = s_rc[0][1] = s_rc[0][2] = s_rc[0][3] = s_m[0] = s_m[1] = 0;
+        if (tid < 4) s_rc[0][tid] = 0;            // (one dword per lane: as vectors of zeros by lane 0 they were kept in scratch)
+        if (tid < 2) s_m[tid] = 0;
         DIAG_STAMP(65);
         if (!initial_sort(cnt)) {                               // (its first barrier also publishes s_x)
             // the optimistic passes did not deliver a sorted bucket (see wg_radix_sort_opt): the whole block goes to
@@ -1421,6 +1486,20 @@ __device__ __forceinline__ void bsort_body(const BzxBatch &B)
             const uint32_t par = round & 1u;
             const uint32_t m = uni(s_m[lpar]);                       // tied ranks
             if (m == 0) break;
+            if (m <= 64) {
+                // a short list: wave 0 runs this round and all that follow, the others wait for it once
+                DIAG_COUNT(89, 1);
+                if (wave == 0) {
+                    dcur = wave_rounds(P, bits, nbits, m, lpar, round, dcur);
+                    if (lane == 0) s_bc[3] = dcur;
+                }
+                __syncthreads();
+                dcur = uni(s_bc[3]);
+                fail = dcur >> 31;
+                dcur &= 0x7FFFFFFFu;
+                DIAG_STAMP(70);
+                break;
+            }
             if (!(round < BS_ROUNDS && dcur < nbits)) {                // deep repeats / identical rotations: rank rounds
                 DIAG_COUNT(round >= BS_ROUNDS ? 84 : 85, 1);
                 fail = true;
@@ -1563,15 +1642,23 @@ __device__ __forceinline__ void bsort_body(const BzxBatch &B)
             uint8_t *__restrict__ L = B.bwt + BZX_SLAB(B, b) * BZX_BLK_STRIDE + start;
             const uint32_t p0 = tid * OUT_E;
             if (p0 < cnt) {
-                uint64_t w8[OUT_E];
+                // A lane visits its eight ranks in rotated order, starting at rank (tid / 4) % 8 of its eight.  Most ranks
+                // were never tied and still hold their own position (s_w[p] = p), so both reads below stride 64 bytes
+                // from lane to lane: taken in the same order by every lane, the 4-byte reads of 32 lanes hit 2 of the
+                // 32 banks (16-way) and wide reads of s_w 4 of 64.  Rotated, four consecutive lanes read the same slot,
+                // 16 dwords apart, and the next four lanes one slot (2 dwords) further: 32 lanes fall on 16 different
+                // banks, two lanes each.
+                const uint32_t rot = tid >> 2;
+                uint32_t pos[OUT_E];
 #pragma unroll
-                for (uint32_t k = 0; k < OUT_E; k++) w8[k] = s_w[p0 + k];
+                for (uint32_t k = 0; k < OUT_E; k++) pos[k] = (uint32_t)(s_w[p0 + ((k + rot) & (OUT_E - 1))] & W_POS_MASK);
                 uint64_t bytes = 0;
 #pragma unroll
                 for (uint32_t k = 0; k < OUT_E; k++) {
-                    const uint32_t r = reinterpret_cast<const uint32_t *>(s_x)[2u * (uint32_t)(w8[k] & W_POS_MASK)];   // (low half of the record)
-                    bytes |= (uint64_t)REC_PREV(r) << (8 * k);
-                    if (p0 + k < cnt && REC_IDX(r) == 0) B.blk[b].orig_ptr = start + p0 + k;
+                    const uint32_t kk = (k + rot) & (OUT_E - 1);
+                    const uint32_t r = reinterpret_cast<const uint32_t *>(s_x)[2u * pos[k]];   // (low half of the record)
+                    bytes |= (uint64_t)REC_PREV(r) << (8 * kk);
+                    if (p0 + kk < cnt && REC_IDX(r) == 0) B.blk[b].orig_ptr = start + p0 + kk;
                 }
                 if (p0 + OUT_E <= cnt) {
                     __builtin_memcpy(L + p0, &bytes, 8);
