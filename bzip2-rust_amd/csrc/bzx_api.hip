@@ -199,6 +199,7 @@ extern "C" void bzx_ctx_destroy(bzx_ctx *ctx)
     if (ctx->dbatch_ws) (void)hipFree(ctx->dbatch_ws);
     if (ctx->range_ws) (void)hipFree(ctx->range_ws);
     if (ctx->range_pin) (void)hipHostFree(ctx->range_pin);
+    if (ctx->range_sl) (void)hipFree(ctx->range_sl);
     for (int i = 0; i < 2; i++)
         if (ctx->range_io[i]) (void)hipFree(ctx->range_io[i]);
     for (int i = 0; i < 2; i++)

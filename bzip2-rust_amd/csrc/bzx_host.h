@@ -94,6 +94,8 @@ struct bzx_ctx {
     uint32_t range_slabs = 0;                   // blocks the round tables hold
     void *range_io[2] = {nullptr, nullptr};     // the _buffer form's span [0] and output [1] on the device, grown on demand
     size_t range_io_bytes[2] = {0, 0};
+    void *range_sl = nullptr;                   // bzx_decompress_ranges_*: the gather kernel's slice table, grown on demand
+    size_t range_sl_cap = 0;                    // ... entries it holds
 };
 
 #define HIP_TRY(ctx, expr)                                                                       \

@@ -424,6 +424,59 @@ int bzx_decompress_range_device(bzx_ctx *ctx, const void *d_bz2, size_t len, uin
 int bzx_decompress_range_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint64_t base, const bzx_index_entry *e,
                                 uint64_t n, uint64_t off, uint64_t want, uint8_t *out, size_t *got);
 /*
+ * Many ranges in one call.  bzx_decompress_ranges_device / _buffer.  The rule: given room, range i leaves
+ * out[out_offs[i], out_offs[i] + gots[i]) equal to what bzx_decompress_range_buffer(..., offs[i], wants[i], ...) returns
+ * for that range alone, and status[i] is that call's BZX_OK or BZX_E_DATA.  The ranges may come in any order, overlap,
+ * repeat, be empty or lie beyond the end (gots[i] = 0, BZX_OK).  The output is packed: out_offs[i] is the running sum of
+ * the clipped lengths, computed from the index before any device work, and *need is that sum; *need > cap: BZX_E_OUTBUF,
+ * nothing is touched.  Every distinct touched block is decoded ONCE however many ranges want bytes of it.
+ *   The input comes in pieces: pieces[j].p holds input bytes [base, base + len), ascending and disjoint; one piece
+ *   {p, 0, file length} is the whole file.  Every touched block's bytes [bit / 8, (bit + img_bits + 7) / 8 + 8) must lie
+ *   inside ONE piece.  bzx_index_spans (host only, no context) names the pieces a list of ranges needs: the union of these
+ *   intervals over the touched blocks, overlapping or adjacent ones merged, gaps left as gaps (a caller may merge further:
+ *   a superset is always accepted); more than cap_pieces: BZX_E_OUTBUF with *npieces = pieces needed.
+ *   Independence, as in bzx_decompress_batch_*: a range's bytes and status depend on the blocks it touches and on nothing
+ *   else.  A damaged block, or an entry that does not match, fails exactly the ranges that touch it: BZX_E_DATA, gots[i] =
+ *   0; _buffer does not write that range's slot of out (it copies back maximal runs of consecutive good ranges: one copy
+ *   when all are good), _device may have written it.  The call returns BZX_OK when every status is, otherwise status[k] of
+ *   the lowest failing k, and bzx_last_error reads "range k: " and the single call's text.  Only verified bytes leave: the
+ *   checks of the single call, by the same code.
+ *   Errors of the whole call are returned and set into every status[i]: BZX_E_PARAM (NULL arrays with count > 0; pieces
+ *   not ascending and disjoint; a touched block not inside one piece -- the text names the range and the bytes; entries
+ *   not in output order), BZX_E_OUTBUF, BZX_E_NOMEM, BZX_E_HIP, BZX_E_STATE (an open bzx_dstream or bzx_index).  count = 0:
+ *   BZX_OK.  After any error the context stays usable.
+ *   Memory: a block that one range alone touches and wholly contains expands at its final place in d_out; every other
+ *   block expands into a staging pool -- the two staging areas of the single call used as one region of about 93 MB, at
+ *   256-byte aligned offsets -- from which ONE launch per round of bzx_rg_gather_kernel puts the slices of the verified
+ *   blocks in place.  A round takes blocks in ascending order until it holds as many as the context has slabs or the next
+ *   pool block does not fit.  Nothing but small tables grows (the block tables, a slice table of 24 bytes per 64 KiB of
+ *   slice).  _buffer uploads the pieces that hold a touched block, and nothing else, into the span buffer the context
+ *   keeps, and decodes into its kept output buffer of *need bytes.  d_out and the piece pointers may have any alignment.
+ *   Host synchronisations: one per round and one at the end; none per range, block or slice.
+ *   bzx_get_stats afterwards: nblk = DISTINCT blocks decoded, raw_bytes = the sum of gots.
+ */
+typedef struct { const void *p; uint64_t base; uint64_t len; } bzx_piece;   /* input bytes [base, base + len) at p */
+int bzx_index_spans(const bzx_index_entry *e, uint64_t n, uint32_t count, const uint64_t *offs, const uint64_t *wants,
+                    uint64_t *bases, uint64_t *lens, uint32_t cap_pieces, uint32_t *npieces);
+int bzx_decompress_ranges_device(bzx_ctx *ctx, const bzx_piece *pieces, uint32_t npieces, const bzx_index_entry *e,
+                                 uint64_t n, uint32_t count, const uint64_t *offs, const uint64_t *wants, void *d_out,
+                                 size_t cap, size_t *out_offs, size_t *gots, int *status, size_t *need);
+int bzx_decompress_ranges_buffer(bzx_ctx *ctx, const bzx_piece *pieces, uint32_t npieces, const bzx_index_entry *e,
+                                 uint64_t n, uint32_t count, const uint64_t *offs, const uint64_t *wants, uint8_t *out,
+                                 size_t cap, size_t *out_offs, size_t *gots, int *status, size_t *need);
+/*
+ * The gather kernel alone, for the parity tests (host pointers): slice i copies src[src_offs[i], + lens[i]) to
+ * out[dst_offs[i], + lens[i]) on the device, through the same cutting into 64 KiB table entries and the same kernel as
+ * the range reads.  The device copy of `out` starts from the caller's bytes, so what lies outside the slices comes back
+ * unchanged.  BZX_E_PARAM when a slice leaves either buffer.  _time: the same under HIP events, *ms_best = the best of
+ * `reps` launches (for the probe).
+ */
+int bzx_stage_gather(bzx_ctx *ctx, const uint8_t *src, size_t src_len, uint32_t nslices, const uint64_t *src_offs,
+                     const uint64_t *dst_offs, const uint64_t *lens, uint8_t *out, size_t out_len);
+int bzx_stage_gather_time(bzx_ctx *ctx, const uint8_t *src, size_t src_len, uint32_t nslices, const uint64_t *src_offs,
+                          const uint64_t *dst_offs, const uint64_t *lens, uint8_t *out, size_t out_len, uint32_t reps,
+                          float *ms_best);
+/*
  * The inverse BWT alone, for the parity tests (host pointers): L[0, n) and orig_ptr < n -> the RLE1 image img_out[0, n)
  * and its expansion raw_out (at most raw_cap bytes are written; *raw_len is the whole expanded length).  wide = 0 runs
  * the one-lane walk of the one-shot, batch and stream decoders, wide = 1 the many-lane walk of the range reads; both

@@ -12,7 +12,9 @@
 // --index FILE.bz2 ... writes FILE.bz2.bzxi, the block index of bzx_index_* (layout: include/bzx.h); -dc --range OFF:LEN
 // FILE.bz2 reads that index and only the bytes of the file that bzx_index_span names, and writes decoded bytes
 // [OFF, OFF + LEN) to standard output through bzx_decompress_range_buffer.  Without an index that matches the file it
-// refuses: there is no silent full decode behind --range.
+// refuses: there is no silent full decode behind --range.  -dc --ranges LIST FILE.bz2 does the same for a list of OFF:LEN
+// lines in one bzx_decompress_ranges_buffer call: it reads the byte intervals of the file that bzx_index_spans names and
+// writes the ranges in list order, back to back; when any range fails, nothing is written.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,6 +38,7 @@ struct Opts {
     std::vector<int> devices;          // --devices: entries of a bzx_mctx for the chunked compression path
     bool index = false, range = false; // --index; --range OFF:LEN
     uint64_t range_off = 0, range_len = 0;
+    std::string ranges;                // --ranges LIST
 };
 
 static void help()
@@ -50,6 +53,7 @@ static void help()
          "  --devices LIST    compress one stream on several devices: ordinals, comma-separated, repeats allowed\n"
          "  --index           write FILE.bzxi, the block index of every FILE (a .bz2), for --range\n"
          "  --range OFF:LEN   with -dc: decoded bytes [OFF, OFF + LEN) of FILE to standard output, through FILE.bzxi\n"
+         "  --ranges LIST     with -dc: the same for every OFF:LEN line of the text file LIST, in one call, back to back\n"
          "With no file, or when a file is -, reads standard input and writes standard output.");
 }
 
@@ -300,8 +304,10 @@ static int range_refuse(const Opts &o, const std::string &f, const char *why)
     return 1;
 }
 
-// Decoded bytes [off, off + len) of FILE.bz2 to standard output, from FILE.bz2.bzxi and the span of the file alone.
-static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
+// FILE.bz2.bzxi and FILE.bz2, with the refusals of --range and --ranges: no index, not an index, an index of another size.
+// -> 0 and the entries, the open file and its size; 1 after a message.
+static int load_index(const Opts &o, const std::string &f, std::vector<bzx_index_entry> &e, uint64_t *out_bytes, FILE **in,
+                      uint64_t *file_size)
 {
     const std::string iname = f + ".bzxi";
     FILE *xf = fopen(iname.c_str(), "rb");
@@ -311,21 +317,20 @@ static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
     fclose(xf);
     if (!xok || x.size() < BZXI_HEADER || memcmp(x.data(), "BZXI", 4) != 0 || get_le(x.data() + 4, 4) != 1)
         return range_refuse(o, f, ("not a bzx index of version 1: " + iname).c_str());
-    const uint64_t in_bytes = get_le(x.data() + 8, 8), out_bytes = get_le(x.data() + 16, 8), nblk = get_le(x.data() + 24, 8);
+    const uint64_t in_bytes = get_le(x.data() + 8, 8), nblk = get_le(x.data() + 24, 8);
+    *out_bytes = get_le(x.data() + 16, 8);
     if ((x.size() - BZXI_HEADER) / BZXI_ENTRY != nblk || (x.size() - BZXI_HEADER) % BZXI_ENTRY)
         return range_refuse(o, f, ("truncated index " + iname).c_str());
-    FILE *in = fopen(f.c_str(), "rb");
+    *in = fopen(f.c_str(), "rb");
     struct stat sb;
-    if (!in || fstat(fileno(in), &sb) != 0) {
+    if (!*in || fstat(fileno(*in), &sb) != 0) {
         if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", f.c_str(), strerror(errno));
-        if (in) fclose(in);
+        if (*in) fclose(*in);
+        *in = nullptr;
         return 1;
     }
+    *file_size = (uint64_t)sb.st_size;
     int ret = 0;
-    std::vector<bzx_index_entry> e;
-    std::vector<uint8_t> span, out;
-    uint64_t first = 0, count = 0, lo = 0, hi = 0;
-    size_t got = 0;
     try {
         e.resize(nblk);
         for (uint64_t k = 0; k < nblk; k++) {
@@ -340,12 +345,35 @@ static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
             e[k].level = r[32];
         }
         const uint64_t total = nblk ? e[nblk - 1].out_off + e[nblk - 1].out_len : 0;
-        if ((uint64_t)sb.st_size != in_bytes || total != out_bytes) {
+        if (*file_size != in_bytes || total != *out_bytes)
             ret = range_refuse(o, f, "the index does not match the file (another size): write it again with bzx --index");
-        } else if (bzx_index_span(e.data(), nblk, o.range_off, o.range_len, &first, &count, &lo, &hi)) {
+    } catch (const std::bad_alloc &) {
+        ret = fail(o, "out of memory", f.c_str(), nullptr, BZX_E_NOMEM);
+    }
+    if (ret) {
+        fclose(*in);
+        *in = nullptr;
+    }
+    return ret;
+}
+
+// Decoded bytes [off, off + len) of FILE.bz2 to standard output, from FILE.bz2.bzxi and the span of the file alone.
+static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    std::vector<bzx_index_entry> e;
+    uint64_t out_bytes = 0, file_size = 0;
+    FILE *in = nullptr;
+    if (load_index(o, f, e, &out_bytes, &in, &file_size)) return 1;
+    const uint64_t nblk = e.size();
+    int ret = 0;
+    std::vector<uint8_t> span, out;
+    uint64_t first = 0, count = 0, lo = 0, hi = 0;
+    size_t got = 0;
+    try {
+        if (bzx_index_span(e.data(), nblk, o.range_off, o.range_len, &first, &count, &lo, &hi)) {
             ret = range_refuse(o, f, "the index does not match the file (entries out of order)");
         } else if (count) {
-            if (hi > (uint64_t)sb.st_size) hi = (uint64_t)sb.st_size;
+            if (hi > file_size) hi = file_size;
             span.resize((size_t)(hi - lo));
             out.resize((size_t)std::min<uint64_t>(o.range_len, out_bytes - o.range_off));
             if (fseeko(in, (off_t)lo, SEEK_SET) != 0 || fread(span.data(), 1, span.size(), in) != span.size()) {
@@ -365,6 +393,114 @@ static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
     if (!ret && o.verbose) fprintf(stderr, "  %s: bytes [%llu, %llu) from %llu blocks, %zu bytes of the file read\n", f.c_str(),
                                    (unsigned long long)o.range_off, (unsigned long long)(o.range_off + got),
                                    (unsigned long long)count, span.size());
+    return ret;
+}
+
+// LIST: OFF:LEN lines; blank lines and # comments are skipped.  -> 0, or 1 after a message that names the line.
+static int read_ranges(const Opts &o, std::vector<uint64_t> &offs, std::vector<uint64_t> &wants)
+{
+    FILE *lf = fopen(o.ranges.c_str(), "r");
+    if (!lf) {
+        fprintf(stderr, "bzx: %s: %s\n", o.ranges.c_str(), strerror(errno));
+        return 1;
+    }
+    std::vector<uint8_t> raw;
+    const bool ok = read_all(lf, raw);
+    fclose(lf);
+    if (!ok) {
+        fprintf(stderr, "bzx: %s: %s\n", o.ranges.c_str(), strerror(errno));
+        return 1;
+    }
+    const std::string all(raw.begin(), raw.end());
+    size_t line = 0;
+    for (size_t p = 0; p < all.size();) {
+        const size_t q = all.find('\n', p) == std::string::npos ? all.size() : all.find('\n', p);
+        std::string t = all.substr(p, q - p);
+        p = q + 1;
+        line++;
+        if (t.find('#') != std::string::npos) t.erase(t.find('#'));
+        const size_t a = t.find_first_not_of(" \t\r"), z = t.find_last_not_of(" \t\r");
+        if (a == std::string::npos) continue;
+        t = t.substr(a, z - a + 1);
+        const size_t c = t.find(':');
+        const std::string x = t.substr(0, c), y = c == std::string::npos ? "" : t.substr(c + 1);
+        if (x.empty() || y.empty() || x.size() > 19 || y.size() > 19 || x.find_first_not_of("0123456789") != std::string::npos ||
+            y.find_first_not_of("0123456789") != std::string::npos) {
+            fprintf(stderr, "bzx: %s: line %zu: not OFF:LEN in bytes (got \"%s\")\n", o.ranges.c_str(), line, t.c_str());
+            return 1;
+        }
+        offs.push_back(strtoull(x.c_str(), nullptr, 10));
+        wants.push_back(strtoull(y.c_str(), nullptr, 10));
+    }
+    return 0;
+}
+
+// The ranges of LIST to standard output, in list order, back to back: one bzx_decompress_ranges_buffer call over the byte
+// intervals of the file that bzx_index_spans names.
+static int do_ranges(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    std::vector<uint64_t> offs, wants;
+    try {
+        if (read_ranges(o, offs, wants)) return 1;
+    } catch (const std::bad_alloc &) {
+        return fail(o, "out of memory", f.c_str(), nullptr, BZX_E_NOMEM);
+    }
+    std::vector<bzx_index_entry> e;
+    uint64_t out_bytes = 0, file_size = 0;
+    FILE *in = nullptr;
+    if (load_index(o, f, e, &out_bytes, &in, &file_size)) return 1;
+    const uint64_t nblk = e.size();
+    const uint32_t count = (uint32_t)offs.size();
+    int ret = 0;
+    size_t need = 0, read_bytes = 0;
+    uint32_t np = 0;
+    std::vector<uint8_t> out;
+    try {
+        if (offs.size() > 0xFFFFFFFFull) {
+            ret = range_refuse(o, f, "too many ranges in the list");
+        } else if (bzx_index_spans(e.data(), nblk, count, offs.data(), wants.data(), nullptr, nullptr, 0, &np) == BZX_E_PARAM) {
+            ret = range_refuse(o, f, "the index does not match the file (entries out of order)");
+        } else if (count) {
+            std::vector<uint64_t> bases(np), lens(np);
+            std::vector<std::vector<uint8_t>> held(np);
+            std::vector<bzx_piece> pieces(np);
+            std::vector<size_t> out_offs(count), gots(count);
+            std::vector<int> status(count);
+            if (np && bzx_index_spans(e.data(), nblk, count, offs.data(), wants.data(), bases.data(), lens.data(), np, &np))
+                ret = fail(o, "out of memory", f.c_str(), nullptr, BZX_E_NOMEM);
+            for (uint32_t j = 0; !ret && j < np; j++) {
+                if (bases[j] + lens[j] > file_size) {
+                    ret = range_refuse(o, f, "the index does not match the file (a block ends behind it)");
+                    break;
+                }
+                held[j].resize((size_t)lens[j]);
+                if (fseeko(in, (off_t)bases[j], SEEK_SET) != 0 || fread(held[j].data(), 1, held[j].size(), in) != held[j].size())
+                    ret = fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK);
+                pieces[j] = bzx_piece{held[j].data(), bases[j], lens[j]};
+                read_bytes += held[j].size();
+            }
+            for (uint32_t i = 0; i < count; i++)
+                need += offs[i] < out_bytes ? (size_t)std::min<uint64_t>(wants[i], out_bytes - offs[i]) : 0;
+            if (!ret) {
+                out.resize(need ? need : 1);
+                const int rc = bzx_decompress_ranges_buffer(ctx, pieces.data(), np, e.data(), nblk, count, offs.data(), wants.data(),
+                                                            out.data(), need, out_offs.data(), gots.data(), status.data(), &need);
+                if (rc) ret = fail(o, "range read failed", f.c_str(), ctx, rc);
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        ret = fail(o, "out of memory", f.c_str(), nullptr, BZX_E_NOMEM);
+    }
+    fclose(in);
+    if (!ret && need && fwrite(out.data(), 1, need, stdout) != need) ret = fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK);
+    if (!ret && fflush(stdout) != 0) ret = 1;
+    if (!ret && o.verbose) {
+        bzx_stats st;
+        memset(&st, 0, sizeof st);
+        if (count) bzx_get_stats(ctx, &st);
+        fprintf(stderr, "  %s: %u ranges, %zu bytes from %u distinct blocks, %u pieces (%zu bytes) of the file read\n", f.c_str(), count,
+                need, st.nblk, np, read_bytes);
+    }
     return ret;
 }
 
@@ -532,6 +668,10 @@ int main(int argc, char **argv)
                 o.range_off = strtoull(x.c_str(), nullptr, 10);
                 o.range_len = strtoull(y.c_str(), nullptr, 10);
             }
+            else if (a == "--ranges" || a.rfind("--ranges=", 0) == 0) {
+                o.ranges = a == "--ranges" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
+                if (o.ranges.empty()) { fprintf(stderr, "bzx: --ranges takes a file of OFF:LEN lines\n"); return 1; }
+            }
             else if (a == "--devices" || a.rfind("--devices=", 0) == 0) {
                 std::string list = a == "--devices" ? (i + 1 < argc ? argv[++i] : "") : a.substr(10);
                 o.devices.clear();
@@ -569,6 +709,20 @@ int main(int argc, char **argv)
                 else { fprintf(stderr, "bzx: unexpected flag -%c\n", c); return 1; }
             }
         }
+    }
+    if (!o.ranges.empty()) {
+        if (o.index || o.range) { fprintf(stderr, "bzx: --ranges does not go with --index or --range\n"); return 1; }
+        if (o.mode != UNZIP || !o.to_stdout) { fprintf(stderr, "bzx: --ranges goes with -dc\n"); return 1; }
+        if (o.files.size() != 1 || o.files[0] == "-") { fprintf(stderr, "bzx: --ranges takes one file, not standard input\n"); return 1; }
+        bzx_ctx *ctx = nullptr;
+        const int rc = bzx_ctx_create(0, 0, &ctx);
+        if (rc) {
+            fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
+            return 2;
+        }
+        const int ret = do_ranges(o, ctx, o.files[0]);
+        bzx_ctx_destroy(ctx);
+        return ret;
     }
     if (o.index || o.range) {
         if (o.index && o.range) { fprintf(stderr, "bzx: --index and --range do not go together\n"); return 1; }
