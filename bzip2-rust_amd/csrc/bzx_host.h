@@ -88,13 +88,13 @@ struct bzx_ctx {
     void *dbatch_pin[2] = {nullptr, nullptr};   // [0] candidates and round tables, [1] the _buffer form's bounce buffer
     size_t dbatch_pin_bytes[2] = {0, 0};
 
-    // range reads (bzx_decompress_range_*): the two edge staging areas and the round tables, allocated by the first call
+    // range reads (bzx_decompress_range_*, _ranges_*): the staging pool and the round tables, allocated by the first call
     void *range_ws = nullptr;
     void *range_pin = nullptr;
     uint32_t range_slabs = 0;                   // blocks the round tables hold
     void *range_io[2] = {nullptr, nullptr};     // the _buffer form's span [0] and output [1] on the device, grown on demand
     size_t range_io_bytes[2] = {0, 0};
-    void *range_sl = nullptr;                   // bzx_decompress_ranges_*: the gather kernel's slice table, grown on demand
+    void *range_sl = nullptr;                   // the gather kernel's slice table, grown on demand
     size_t range_sl_cap = 0;                    // ... entries it holds
 };
 
@@ -116,13 +116,15 @@ static inline std::unique_lock<std::recursive_mutex> ctx_lock(bzx_ctx *ctx)
 
 // Between bzx_dstream_begin and bzx_dstream_end the slabs hold the stream's decoded blocks: every other compute entry
 // point of the context is refused (after its lock is taken; the stream stays intact).
-#define BZX_REFUSE_WHILE_STREAMING(ctx)                                                                              \
-    do {                                                                                                             \
-        if ((ctx) && (ctx)->ds) {                                                                                    \
-            (ctx)->err = "the context is busy with an open bzx_dstream (its block slabs hold the stream's decoded "  \
-                         "blocks): call bzx_dstream_end first";                                                      \
-            return BZX_E_STATE;                                                                                      \
-        }                                                                                                            \
+static inline int refuse_streaming(bzx_ctx *ctx)
+{
+    ctx->err = "the context is busy with an open bzx_dstream (its block slabs hold the stream's decoded blocks): call "
+               "bzx_dstream_end first";
+    return BZX_E_STATE;
+}
+#define BZX_REFUSE_WHILE_STREAMING(ctx)                          \
+    do {                                                         \
+        if ((ctx) && (ctx)->ds) return refuse_streaming(ctx);    \
     } while (0)
 
 static inline int level_ok(int level) { return level >= 1 && level <= 9; }

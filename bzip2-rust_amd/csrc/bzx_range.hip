@@ -10,11 +10,12 @@
 //                 to hide a one-lane pointer chase behind
 //   check         bzx_rg_check_kernel: is the block magic where the entry says, and is the expanded length the
 //                 entry's?  A block that fails is neither expanded nor summed (its destination is sized by the entry)
-//   expand, CRC   blocks wholly inside the range at their final place in the output, the at most two edge blocks of
-//                 the range into staging areas of their own
-//   [sync]        descriptors, CRCs and flags; the host holds every block against its entry, then the slices of the
-//                 edge blocks are copied from their staging areas
+//   expand, CRC   a block that one range alone touches and wholly contains at its final place in the output, every
+//                 other block (the at most two edge blocks of a range; a block that several ranges share) into the pool
+//   [sync]        descriptors, CRCs and flags; the host holds every block against its entry, then one launch of the
+//                 gather kernel moves the wanted slices of the verified pool blocks
 // One host synchronisation per round; nothing leaves through _buffer before every block of the range has passed.
+// One core (ranges_plan, ranges_exec, ranges_call) serves every entry point: the single call is count = 1 over one piece.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include "bzx_host.h"
 
 #define RG_EDGE_BYTES ((size_t)(BZX_MAX_N / 5 * 259 + 16))      // an expanded block: 259/5 x 900,000, rounded up
+#define RG_POOL_BYTES (2 * rg_al(RG_EDGE_BYTES))                // the pool: room for the two edge blocks of one range
 #define RG_NO_MAGIC 1u
 #define RG_LENGTH 2u
 
@@ -43,6 +45,13 @@ __global__ __launch_bounds__(64) void bzx_rg_check_kernel(BzxBatch B, const BzxD
 
 static uint64_t rg_total(const bzx_index_entry *e, uint64_t n) { return n ? e[n - 1].out_off + e[n - 1].out_len : 0; }
 
+// The input bytes a block needs: from the byte that holds its magic to its last bit, rounded up to a byte, + 8.
+static void rg_block_bytes(const bzx_index_entry &x, uint64_t *lo, uint64_t *hi)
+{
+    *lo = x.bit / 8;
+    *hi = (x.bit + x.img_bits + 7) / 8 + 8;
+}
+
 extern "C" int bzx_index_span(const bzx_index_entry *e, uint64_t n, uint64_t off, uint64_t want, uint64_t *first,
                               uint64_t *count, uint64_t *byte_lo, uint64_t *byte_hi)
 {
@@ -61,18 +70,19 @@ extern "C" int bzx_index_span(const bzx_index_entry *e, uint64_t n, uint64_t off
     if (a >= z || a->out_off > off) return BZX_E_PARAM;          // (entries that are not in output order)
     *first = (uint64_t)(a - e);
     *count = (uint64_t)(z - a);
-    *byte_lo = a->bit / 8;
-    *byte_hi = (z[-1].bit + z[-1].img_bits + 7) / 8 + 8;
+    uint64_t other;
+    rg_block_bytes(*a, byte_lo, &other);
+    rg_block_bytes(z[-1], &other, byte_hi);
     return BZX_OK;
 }
 
 // Round tables: device [src R][dst R][want_len R][got R][flag R], pinned [got R][flag R]; behind them on the device the
-// two edge staging areas.
+// pool.
 struct RgTables {
     BzxDcSrc *d_src;
     BzxDcDst *d_dst;
     uint32_t *d_len, *d_got, *d_flag, *h_got, *h_flag;
-    uint8_t *edge[2];
+    uint8_t *pool;
 };
 
 static size_t rg_al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -84,7 +94,7 @@ static int rg_tables(bzx_ctx *ctx, uint32_t R, RgTables *t)
         if (ctx->range_pin) (void)hipHostFree(ctx->range_pin);
         ctx->range_ws = ctx->range_pin = nullptr;
         ctx->range_slabs = 0;
-        const size_t dev = rg_al(R * sizeof(BzxDcSrc)) + rg_al(R * sizeof(BzxDcDst)) + 3 * rg_al((size_t)R * 4) + 2 * rg_al(RG_EDGE_BYTES);
+        const size_t dev = rg_al(R * sizeof(BzxDcSrc)) + rg_al(R * sizeof(BzxDcDst)) + 3 * rg_al((size_t)R * 4) + RG_POOL_BYTES;
         if (hipMalloc(&ctx->range_ws, dev) != hipSuccess || hipHostMalloc(&ctx->range_pin, 2 * rg_al((size_t)R * 4), 0) != hipSuccess) {
             if (ctx->range_ws) (void)hipFree(ctx->range_ws);
             ctx->range_ws = nullptr;
@@ -105,8 +115,7 @@ static int rg_tables(bzx_ctx *ctx, uint32_t R, RgTables *t)
     q += rg_al((size_t)R * 4);
     t->d_flag = (uint32_t *)q;
     q += rg_al((size_t)R * 4);
-    t->edge[0] = q;
-    t->edge[1] = q + rg_al(RG_EDGE_BYTES);
+    t->pool = q;
     t->h_got = (uint32_t *)ctx->range_pin;
     t->h_flag = (uint32_t *)((uint8_t *)ctx->range_pin + rg_al((size_t)R * 4));
     return BZX_OK;
@@ -181,60 +190,6 @@ static int rg_round(bzx_ctx *ctx, const RgTables &t, uint32_t nb, const BzxDcSrc
     return BZX_OK;
 }
 
-// Entries e[first, first + count) cover output bytes [lo, hi); d_z[0, zlen) holds input bytes [zbase, zbase + zlen).
-// d_out receives [lo, hi).
-static int range_run(bzx_ctx *ctx, const uint8_t *d_z, size_t zlen, uint64_t zbase, const bzx_index_entry *e, uint64_t first,
-                     uint64_t count, uint64_t lo, uint64_t hi, uint8_t *d_out)
-{
-    hipStream_t st = ctx->stream;
-    int rc = ensure_blocks(ctx, 1);              // (a context holds 16 slabs at least from bzx_ctx_create on: nothing grows)
-    if (rc) return rc;
-    const uint32_t R = ctx->cap_slabs;
-    RgTables t;
-    if ((rc = rg_tables(ctx, R, &t))) return rc;
-    std::vector<BzxDcSrc> src(R);
-    std::vector<BzxDcDst> dst(R);
-    std::vector<uint32_t> len(R);
-    struct Edge { uint64_t k; uint32_t area; };
-    uint32_t areas = 0;
-    for (uint64_t k0 = first; k0 < first + count; k0 += R) {
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(R, first + count - k0);
-        std::vector<Edge> edges;
-        uint32_t n_hint = 0;                                 // an image is at most 5/4 of what it expands to
-        for (uint32_t j = 0; j < nb; j++) {
-            const bzx_index_entry &x = e[k0 + j];
-            n_hint = std::max<uint32_t>(n_hint, (uint32_t)std::min<uint64_t>(BZX_MAX_N, (uint64_t)x.out_len * 5 / 4 + 8));
-            src[j] = BzxDcSrc{d_z, zlen, x.bit - zbase * 8};
-            len[j] = x.out_len;
-            if (x.out_len > RG_EDGE_BYTES - 16) return rg_refuse(ctx, "index does not match the input: an entry's out_len exceeds a block");
-            if (x.out_off >= lo && x.out_off + x.out_len <= hi) {
-                dst[j] = BzxDcDst{d_out + (x.out_off - lo), x.out_len};
-            } else {                                         // an edge of the range: at most two in all
-                if (areas >= 2) {
-                    ctx->err = "range read: more than two edge blocks";
-                    return BZX_E_STATE;
-                }
-                edges.push_back(Edge{k0 + j, areas});
-                dst[j] = BzxDcDst{t.edge[areas++], x.out_len};
-            }
-        }
-        if ((rc = rg_round(ctx, t, nb, src.data(), dst.data(), len.data(), n_hint))) return rc;
-        for (uint32_t j = 0; j < nb; j++)
-            if ((rc = rg_verdict(ctx, e[k0 + j], k0 + j, ctx->h_blk[j], t.h_flag[j], t.h_got[j]))) return rc;
-        for (const Edge &g : edges) {                        // verified: the slices of the edge blocks
-            const bzx_index_entry &x = e[g.k];
-            const uint64_t a = std::max<uint64_t>(x.out_off, lo), z = std::min<uint64_t>(x.out_off + x.out_len, hi);
-            HIP_TRY(ctx, hipMemcpyAsync(d_out + (a - lo), t.edge[g.area] + (a - x.out_off), z - a, hipMemcpyDeviceToDevice, st));
-        }
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    memset(&ctx->stats, 0, sizeof(ctx->stats));
-    ctx->stats_batch = true;
-    ctx->stats.nblk = (uint32_t)count;
-    ctx->stats.raw_bytes = hi - lo;
-    return BZX_OK;
-}
-
 // The touched entries tile [their first byte, their last byte): out_off is the running sum of out_len.
 static int rg_tiles(bzx_ctx *ctx, const bzx_index_entry *e, uint64_t first, uint64_t count, uint64_t hi)
 {
@@ -249,99 +204,14 @@ static int rg_tiles(bzx_ctx *ctx, const bzx_index_entry *e, uint64_t first, uint
     return BZX_OK;
 }
 
-// Argument checks and the span of both forms.  *count == 0: nothing to do.
-static int range_args(bzx_ctx *ctx, size_t len, uint64_t base, const bzx_index_entry *e, uint64_t n, uint64_t off, uint64_t want,
-                      uint64_t *first, uint64_t *count, uint64_t *lo, uint64_t *hi)
-{
-    uint64_t byte_lo = 0, byte_hi = 0;
-    if (bzx_index_span(e, n, off, want, first, count, &byte_lo, &byte_hi)) {
-        ctx->err = "range read: the index entries are not in order";
-        return BZX_E_PARAM;
-    }
-    if (!*count) return BZX_OK;
-    if (base > byte_lo || base + len < byte_hi) {
-        ctx->err = "range read: the input bytes given do not cover bytes [" + std::to_string(byte_lo) + ", " +
-                   std::to_string(byte_hi) + ") of the file (bzx_index_span)";
-        return BZX_E_PARAM;
-    }
-    *lo = off;
-    *hi = std::min<uint64_t>(rg_total(e, n), off + std::min<uint64_t>(want, ~0ull - off));
-    return rg_tiles(ctx, e, *first, *count, *hi);
-}
-
-extern "C" int bzx_decompress_range_device(bzx_ctx *ctx, const void *d_bz2, size_t len, uint64_t base, const bzx_index_entry *e,
-                                           uint64_t n, uint64_t off, uint64_t want, void *d_out, size_t *got)
-{
-    auto api_lock_ = ctx_lock(ctx);
-    if (got) *got = 0;
-    BZX_REFUSE_WHILE_STREAMING(ctx);
-    if (!ctx || !got || (n && !e)) return BZX_E_PARAM;
-    uint64_t first = 0, count = 0, lo = 0, hi = 0;
-    int rc = range_args(ctx, len, base, e, n, off, want, &first, &count, &lo, &hi);
-    if (rc || !count) return rc;
-    if (!d_bz2 || !d_out) return BZX_E_PARAM;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    try {
-        rc = range_run(ctx, (const uint8_t *)d_bz2, len, base, e, first, count, lo, hi, (uint8_t *)d_out);
-    } catch (const std::bad_alloc &) {                       // (nothing may unwind across the C ABI)
-        ctx->err = "out of host memory";
-        rc = BZX_E_NOMEM;
-    }
-    if (rc) (void)hipStreamSynchronize(ctx->stream);         // nothing of a failed call is left in flight
-    else *got = (size_t)(hi - lo);
-    return rc;
-}
-
-extern "C" int bzx_decompress_range_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint64_t base, const bzx_index_entry *e,
-                                           uint64_t n, uint64_t off, uint64_t want, uint8_t *out, size_t *got)
-{
-    auto api_lock_ = ctx_lock(ctx);
-    if (got) *got = 0;
-    BZX_REFUSE_WHILE_STREAMING(ctx);
-    if (!ctx || !got || (n && !e)) return BZX_E_PARAM;
-    uint64_t first = 0, count = 0, lo = 0, hi = 0;
-    int rc = range_args(ctx, len, base, e, n, off, want, &first, &count, &lo, &hi);
-    if (rc || !count) return rc;
-    if (!bz2 || !out) return BZX_E_PARAM;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the span alone travels to the device, one slice comes back
-    const uint64_t byte_lo = e[first].bit / 8;
-    const uint64_t byte_hi = (e[first + count - 1].bit + e[first + count - 1].img_bits + 7) / 8 + 8;
-    // (two device buffers the context keeps and grows: no allocation, and no hipFree with its device-wide wait, on the
-    // path of a small read)
-    void *d_z = nullptr, *d_o = nullptr;
-    if ((rc = rg_io(ctx, 0, (size_t)(byte_hi - byte_lo) + 64, &d_z)) || (rc = rg_io(ctx, 1, (size_t)(hi - lo) + 64, &d_o))) return rc;
-    rc = hipMemcpyAsync(d_z, bz2 + (byte_lo - base), (size_t)(byte_hi - byte_lo), hipMemcpyHostToDevice, ctx->stream) == hipSuccess
-             ? BZX_OK
-             : BZX_E_HIP;
-    try {
-        if (!rc)
-            rc = range_run(ctx, (const uint8_t *)d_z, (size_t)(byte_hi - byte_lo), byte_lo, e, first, count, lo, hi, (uint8_t *)d_o);
-    } catch (const std::bad_alloc &) {                       // (nothing may unwind across the C ABI)
-        ctx->err = "out of host memory";
-        rc = BZX_E_NOMEM;
-    }
-    if (!rc && hipMemcpyAsync(out, d_o, (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-        ctx->err = "hipMemcpyAsync(range output) failed";
-        rc = BZX_E_HIP;
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) {
-        ctx->err = "hipStreamSynchronize(range output) failed";
-        rc = BZX_E_HIP;
-    }
-    if (!rc) *got = (size_t)(hi - lo);
-    return rc;
-}
-
-// ---- many ranges in one call (bzx_index_spans, bzx_decompress_ranges_*, bzx_stage_gather) -------------------------------
+// ---- the core: any number of ranges in one call (bzx_index_spans, bzx_decompress_range_*, _ranges_*, bzx_stage_gather) ----
 // The host plans the whole call from the index: every range is clipped and given its place in the packed output, the
 // distinct touched blocks are listed in ascending order with the slices the ranges want of them, and rounds of at most R
 // blocks go through rg_round.  A block that one range alone touches and wholly contains expands at its final place; every
-// other block expands into the pool (the two edge areas of range_ws as one region, 256-byte aligned offsets), and after the
+// other block expands into the pool (behind the round tables in range_ws, 256-byte aligned offsets), and after the
 // round's verdicts ONE launch of the gather kernel moves the slices of its verified pool blocks.
 #define RG_PIECE ((uint64_t)64 << 10)          // bytes one workgroup of the gather kernel moves at most
 #define RG_NT 256
-#define RG_POOL_BYTES (2 * rg_al(RG_EDGE_BYTES))
 
 struct RgSlice {
     const uint8_t *src;
@@ -411,12 +281,6 @@ static int rg_gather(bzx_ctx *ctx, const std::vector<RgSlice> &v)
                            (const RgSlice *)ctx->range_sl + at);
     HIP_TRY(ctx, hipGetLastError());
     return BZX_OK;
-}
-
-static void rg_block_bytes(const bzx_index_entry &x, uint64_t *lo, uint64_t *hi)
-{
-    *lo = x.bit / 8;
-    *hi = (x.bit + x.img_bits + 7) / 8 + 8;
 }
 
 extern "C" int bzx_index_spans(const bzx_index_entry *e, uint64_t n, uint32_t count, const uint64_t *offs, const uint64_t *wants,
@@ -583,7 +447,7 @@ static int ranges_exec(bzx_ctx *ctx, RgPlan &P, const bzx_piece *pc, const uint8
     const uint32_t R = ctx->cap_slabs;
     RgTables t;
     if ((rc = rg_tables(ctx, R, &t))) return rc;
-    uint8_t *pool = t.edge[0];
+    uint8_t *pool = t.pool;
     std::vector<BzxDcSrc> src(R);
     std::vector<BzxDcDst> dst(R);
     std::vector<uint32_t> len(R);
@@ -626,15 +490,18 @@ static int ranges_exec(bzx_ctx *ctx, RgPlan &P, const bzx_piece *pc, const uint8
         }
         if ((rc = rg_gather(ctx, sl))) return rc;
         i += nb;
+        // every range has failed: nothing is left to deliver, statuses and texts are final
+        if (std::find(P.bad.begin(), P.bad.end(), 0) == P.bad.end()) break;
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return BZX_OK;
 }
 
-// Both forms.  host: pieces[].p and out are host pointers.
+// Both forms.  host: pieces[].p and out are host pointers.  BZX_E_DATA: the statuses are set range by range, *fail_k is
+// the lowest failed range and ctx->err the text of its failure as it stands (the batched entry names the range in front).
 static int ranges_call(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const bzx_index_entry *e, uint64_t n, uint32_t count,
                        const uint64_t *offs, const uint64_t *wants, uint8_t *out, size_t cap, size_t *out_offs, size_t *gots,
-                       int *status, size_t *need, bool host)
+                       int *status, size_t *need, bool host, uint64_t *fail_k)
 {
     RgPlan P;
     int rc = ranges_plan(ctx, pc, npc, e, n, count, offs, wants, cap, out_offs, gots, need, P);
@@ -692,10 +559,27 @@ static int ranges_call(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const bz
     ctx->stats.nblk = (uint32_t)P.blk.size();
     ctx->stats.raw_bytes = raw;
     if (P.fail_k != ~0ull) {
-        ctx->err = "range " + std::to_string(P.fail_k) + ": " + P.fail_text;
+        ctx->err = P.fail_text;
+        *fail_k = P.fail_k;
         return BZX_E_DATA;
     }
     return BZX_OK;
+}
+
+// ... with nothing unwinding across the C ABI and nothing of a failed call left in flight.
+static int ranges_core(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const bzx_index_entry *e, uint64_t n, uint32_t count,
+                       const uint64_t *offs, const uint64_t *wants, void *out, size_t cap, size_t *out_offs, size_t *gots,
+                       int *status, size_t *need, bool host, uint64_t *fail_k)
+{
+    int rc;
+    try {
+        rc = ranges_call(ctx, pc, npc, e, n, count, offs, wants, (uint8_t *)out, cap, out_offs, gots, status, need, host, fail_k);
+    } catch (const std::bad_alloc &) {
+        ctx->err = "out of host memory";
+        rc = BZX_E_NOMEM;
+    }
+    if (rc && rc != BZX_E_DATA) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
 }
 
 static int ranges_entry(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const bzx_index_entry *e, uint64_t n, uint32_t count,
@@ -709,23 +593,17 @@ static int ranges_entry(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const b
     if (!ctx) {
         rc = BZX_E_PARAM;
     } else if (ctx->ds) {
-        ctx->err = "the context is busy with an open bzx_dstream (its block slabs hold the stream's decoded blocks): call "
-                   "bzx_dstream_end first";
-        rc = BZX_E_STATE;
+        rc = refuse_streaming(ctx);
     } else if (count == 0) {
         return BZX_OK;
     } else if (!offs || !wants || !out_offs || !gots || !status || !need || (n && !e) || (npc && !pc)) {
         ctx->err = "range read: a NULL array";
         rc = BZX_E_PARAM;
     } else {
-        try {
-            rc = ranges_call(ctx, pc, npc, e, n, count, offs, wants, (uint8_t *)out, cap, out_offs, gots, status, need, host);
-            whole = rc != BZX_OK && rc != BZX_E_DATA;        // (BZX_E_DATA: the statuses are set, range by range)
-        } catch (const std::bad_alloc &) {                   // (nothing may unwind across the C ABI)
-            ctx->err = "out of host memory";
-            rc = BZX_E_NOMEM;
-        }
-        if (rc && whole) (void)hipStreamSynchronize(ctx->stream);      // nothing of a failed call is left in flight
+        uint64_t fail_k = 0;
+        rc = ranges_core(ctx, pc, npc, e, n, count, offs, wants, out, cap, out_offs, gots, status, need, host, &fail_k);
+        whole = rc != BZX_OK && rc != BZX_E_DATA;            // (BZX_E_DATA: the statuses are set, range by range)
+        if (rc == BZX_E_DATA) ctx->err = "range " + std::to_string(fail_k) + ": " + ctx->err;
     }
     if (rc && whole) {
         for (uint32_t i = 0; i < count; i++) {
@@ -748,6 +626,58 @@ extern "C" int bzx_decompress_ranges_buffer(bzx_ctx *ctx, const bzx_piece *piece
                                             size_t cap, size_t *out_offs, size_t *gots, int *status, size_t *need)
 {
     return ranges_entry(ctx, pieces, npieces, e, n, count, offs, wants, out, cap, out_offs, gots, status, need, true);
+}
+
+// The single call, both forms: count = 1 of the core over one piece.  host: bz2 and out are host pointers, and the span
+// alone is the piece (it alone is uploaded, one slice comes back).  A touched entry whose bytes leave the piece (a corrupt
+// index: the first and the last one lie inside the span by construction) would read zeros there: it is refused here with
+// the text of a missing magic, before the core runs -- so if a lower-numbered block fails too, for another reason, this
+// entry's text is the one reported.
+static int range_entry(bzx_ctx *ctx, const void *bz2, size_t len, uint64_t base, const bzx_index_entry *e, uint64_t n, uint64_t off,
+                       uint64_t want, void *out, size_t *got, bool host)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    if (got) *got = 0;
+    BZX_REFUSE_WHILE_STREAMING(ctx);
+    if (!ctx || !got || (n && !e)) return BZX_E_PARAM;
+    uint64_t first = 0, count = 0, byte_lo = 0, byte_hi = 0;
+    if (bzx_index_span(e, n, off, want, &first, &count, &byte_lo, &byte_hi)) {
+        ctx->err = "range read: the index entries are not in order";
+        return BZX_E_PARAM;
+    }
+    if (!count) return BZX_OK;
+    if (base > byte_lo || base + len < byte_hi) {
+        ctx->err = "range read: the input bytes given do not cover bytes [" + std::to_string(byte_lo) + ", " +
+                   std::to_string(byte_hi) + ") of the file (bzx_index_span)";
+        return BZX_E_PARAM;
+    }
+    if (!bz2 || !out) return BZX_E_PARAM;
+    const bzx_piece pc = host ? bzx_piece{(const uint8_t *)bz2 + (byte_lo - base), byte_lo, byte_hi - byte_lo} : bzx_piece{bz2, base, len};
+    for (uint64_t k = first; k < first + count; k++) {
+        uint64_t lo, hi;
+        rg_block_bytes(e[k], &lo, &hi);
+        if (lo < pc.base || hi > pc.base + pc.len)
+            return rg_refuse(ctx, "index does not match the input: no block magic at bit " + std::to_string(e[k].bit) + " (block " +
+                                      std::to_string(k) + ")");
+    }
+    size_t out_off = 0, need = 0;
+    int status = 0;
+    uint64_t fail_k = 0;
+    const int rc = ranges_core(ctx, &pc, 1, e, n, 1, &off, &want, out, ~(size_t)0, &out_off, got, &status, &need, host, &fail_k);
+    if (rc) *got = 0;
+    return rc;
+}
+
+extern "C" int bzx_decompress_range_device(bzx_ctx *ctx, const void *d_bz2, size_t len, uint64_t base, const bzx_index_entry *e,
+                                           uint64_t n, uint64_t off, uint64_t want, void *d_out, size_t *got)
+{
+    return range_entry(ctx, d_bz2, len, base, e, n, off, want, d_out, got, false);
+}
+
+extern "C" int bzx_decompress_range_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint64_t base, const bzx_index_entry *e,
+                                           uint64_t n, uint64_t off, uint64_t want, uint8_t *out, size_t *got)
+{
+    return range_entry(ctx, bz2, len, base, e, n, off, want, out, got, true);
 }
 
 // ---- the gather kernel alone, for the parity tests and the probe ----------------------------------------------------------
@@ -826,7 +756,60 @@ extern "C" int bzx_stage_gather_time(bzx_ctx *ctx, const uint8_t *src, size_t sr
     return stage_gather(ctx, src, src_len, nslices, src_offs, dst_offs, lens, out, out_len, reps, ms_best);
 }
 
-// ---- the inverse BWT alone, for the parity tests ------------------------------------------------------------------------
+// ---- the inverse BWT alone, for the parity tests and the probe ----------------------------------------------------------
+// What the block decoder leaves, for `copies` copies of one block side by side (scaffolding): L and the byte counts in
+// every slab (slab 0 from the host, the others from it on the device); the number of earlier occurrences of each byte and
+// the descriptors stay in `in` for ibwt_arm.
+struct IbwtIn {
+    std::vector<uint32_t> occ, freq;
+    std::vector<BzxBlock> d;
+};
+
+static int ibwt_load(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t orig_ptr, uint32_t copies, IbwtIn &in)
+{
+    const int rc = ensure_blocks(ctx, copies);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    BzxBatch &B = ctx->B;
+    B.nblk = copies;
+    B.blk_first = 0;
+    B.blk_step = 1;
+    try {
+        in.occ.resize(n);
+        in.freq.assign(260, 0);
+        in.d.resize(copies);
+    } catch (const std::bad_alloc &) {
+        ctx->err = "out of host memory";
+        return BZX_E_NOMEM;
+    }
+    for (size_t i = 0; i < n; i++) in.occ[i] = in.freq[L[i]]++;
+    memset(in.d.data(), 0, copies * sizeof(BzxBlock));
+    for (uint32_t b = 0; b < copies; b++) {
+        in.d[b].n = (uint32_t)n;
+        in.d[b].orig_ptr = orig_ptr;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(B.bwt, L, n, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(B.freq, in.freq.data(), 260 * 4, hipMemcpyHostToDevice, st));
+    for (uint32_t b = 1; b < copies; b++) {
+        HIP_TRY(ctx, hipMemcpyAsync(B.bwt + (size_t)b * BZX_BLK_STRIDE, B.bwt, n, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(B.freq + (size_t)b * 260, B.freq, 260 * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return BZX_OK;
+}
+
+// The pack kernel overwrites the occurrence counts: they and the descriptors are put in place before every launch.
+static int ibwt_arm(bzx_ctx *ctx, const IbwtIn &in)
+{
+    hipStream_t st = ctx->stream;
+    const BzxBatch &B = ctx->B;
+    const size_t n = in.occ.size();
+    HIP_TRY(ctx, hipMemcpyAsync(B.rec_a, in.occ.data(), n * 4, hipMemcpyHostToDevice, st));
+    for (uint32_t b = 1; b < B.nblk; b++)
+        HIP_TRY(ctx, hipMemcpyAsync(B.rec_a + (size_t)b * BZX_MAX_N, B.rec_a, n * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(B.blk, in.d.data(), B.nblk * sizeof(BzxBlock), hipMemcpyHostToDevice, st));
+    return BZX_OK;
+}
+
 extern "C" int bzx_stage_ibwt(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t orig_ptr, int wide, uint8_t *img_out,
                               uint8_t *raw_out, size_t raw_cap, uint64_t *raw_len, uint32_t *status)
 {
@@ -835,46 +818,26 @@ extern "C" int bzx_stage_ibwt(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t
     if (!ctx || !L || !img_out || !raw_len || !status || (raw_cap && !raw_out) || n == 0 || n > BZX_MAX_N || orig_ptr >= n)
         return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_blocks(ctx, 1);
-    if (rc) return rc;
     hipStream_t st = ctx->stream;
     BzxBatch &B = ctx->B;
-    B.nblk = 1;
-    B.blk_first = 0;
-    B.blk_step = 1;
-    // what the block decoder leaves: L, the number of earlier occurrences of each byte, the byte counts (scaffolding)
-    std::vector<uint32_t> occ, freq;
-    try {
-        occ.resize(n);
-        freq.assign(260, 0);
-    } catch (const std::bad_alloc &) {
-        ctx->err = "out of host memory";
-        return BZX_E_NOMEM;
-    }
-    for (size_t i = 0; i < n; i++) occ[i] = freq[L[i]]++;
-    BzxBlock d;
-    memset(&d, 0, sizeof(d));
-    d.n = (uint32_t)n;
-    d.orig_ptr = orig_ptr;
     uint8_t *d_raw = nullptr;
     if (hipMalloc((void **)&d_raw, raw_cap + 64) != hipSuccess) {
         ctx->err = "bzx_stage_ibwt: hipMalloc(expansion) failed";
         return BZX_E_NOMEM;
     }
     const BzxDcDst dst{raw_cap ? d_raw : nullptr, raw_cap};
-    BzxDcDst *d_dst = reinterpret_cast<BzxDcDst *>(B.selector);          // (a slab the inverse BWT does not touch)
+    IbwtIn in;
     auto run = [&]() -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(B.bwt, L, n, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(B.rec_a, occ.data(), n * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(B.freq, freq.data(), 260 * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(B.blk, &d, sizeof(d), hipMemcpyHostToDevice, st));
+        int rc;
+        if ((rc = ibwt_load(ctx, L, n, orig_ptr, 1, in)) || (rc = ibwt_arm(ctx, in))) return rc;
+        BzxDcDst *d_dst = reinterpret_cast<BzxDcDst *>(B.selector);      // (a slab the inverse BWT does not touch)
         HIP_TRY(ctx, hipMemcpyAsync(d_dst, &dst, sizeof(dst), hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_in, 0xEE, n, st));
         if (wide) bzx_launch_dc_ibwt_wide(B, ctx->d_in, (uint32_t)n, st);
         else bzx_launch_dc_ibwt(B, ctx->d_in, st);
         bzx_launch_dc_expand(B, ctx->d_in, d_dst, st);
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, sizeof(d), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, sizeof(BzxBlock), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipMemcpyAsync(img_out, ctx->d_in, n, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         *status = ctx->h_blk[0].status;
@@ -883,14 +846,14 @@ extern "C" int bzx_stage_ibwt(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t
         if (k && !*status) HIP_TRY(ctx, hipMemcpy(raw_out, d_raw, k, hipMemcpyDeviceToHost));
         return BZX_OK;
     };
-    rc = run();
+    const int rc = run();
     (void)hipStreamSynchronize(st);
     (void)hipFree(d_raw);
     return rc;
 }
 
-// The inverse BWT launchers alone under HIP events, for the probe: `copies` copies of one block side by side (slab 0 is
-// filled from the host, the others from it on the device), `reps` launches, the best one's milliseconds.
+// The inverse BWT launchers alone under HIP events, for the probe: `copies` copies of one block side by side, `reps`
+// launches, the best one's milliseconds.
 extern "C" int bzx_stage_ibwt_time(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t orig_ptr, int wide, uint32_t copies,
                                    uint32_t reps, float *ms_best)
 {
@@ -898,42 +861,14 @@ extern "C" int bzx_stage_ibwt_time(bzx_ctx *ctx, const uint8_t *L, size_t n, uin
     BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !L || !ms_best || n == 0 || n > BZX_MAX_N || orig_ptr >= n || copies == 0 || reps == 0) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_blocks(ctx, copies);
+    IbwtIn in;
+    int rc = ibwt_load(ctx, L, n, orig_ptr, copies, in);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
-    BzxBatch &B = ctx->B;
-    B.nblk = copies;
-    B.blk_first = 0;
-    B.blk_step = 1;
-    std::vector<uint32_t> occ, freq;
-    std::vector<BzxBlock> d;
-    try {
-        occ.resize(n);
-        freq.assign(260, 0);
-        d.resize(copies);
-    } catch (const std::bad_alloc &) {
-        ctx->err = "out of host memory";
-        return BZX_E_NOMEM;
-    }
-    for (size_t i = 0; i < n; i++) occ[i] = freq[L[i]]++;
-    memset(d.data(), 0, copies * sizeof(BzxBlock));
-    for (uint32_t b = 0; b < copies; b++) {
-        d[b].n = (uint32_t)n;
-        d[b].orig_ptr = orig_ptr;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(B.bwt, L, n, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(B.freq, freq.data(), 260 * 4, hipMemcpyHostToDevice, st));
-    for (uint32_t b = 1; b < copies; b++) {
-        HIP_TRY(ctx, hipMemcpyAsync(B.bwt + (size_t)b * BZX_BLK_STRIDE, B.bwt, n, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(B.freq + (size_t)b * 260, B.freq, 260 * 4, hipMemcpyDeviceToDevice, st));
-    }
+    const BzxBatch &B = ctx->B;
     float best = 0.f;
     for (uint32_t r = 0; r < reps; r++) {
-        // the pack kernel overwrites the occurrence counts: they are put back before every launch
-        HIP_TRY(ctx, hipMemcpyAsync(B.rec_a, occ.data(), n * 4, hipMemcpyHostToDevice, st));
-        for (uint32_t b = 1; b < copies; b++)
-            HIP_TRY(ctx, hipMemcpyAsync(B.rec_a + (size_t)b * BZX_MAX_N, B.rec_a, n * 4, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(B.blk, d.data(), copies * sizeof(BzxBlock), hipMemcpyHostToDevice, st));
+        if ((rc = ibwt_arm(ctx, in))) return rc;
         HIP_TRY(ctx, hipEventRecord(ctx->ev[5], st));
         if (wide) bzx_launch_dc_ibwt_wide(B, ctx->d_in, (uint32_t)n, st);
         else bzx_launch_dc_ibwt(B, ctx->d_in, st);

@@ -406,12 +406,16 @@ int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_ind
  * computed CRC against the CRC stored in the block and against entry.crc.  BZX_E_DATA with "index does not match the
  * input: ..." (no block magic at `bit`, another stored CRC, another decoded length or block size), the damaged-block
  * or the "block CRC mismatch in block N" text otherwise (N: the entry's number); *got = 0, and _buffer has not
- * written out (_device may have written d_out).  Blocks wholly inside the range expand at their final place in d_out,
- * the at most two edge blocks into device staging areas of 259/5 x 900,000 bytes each, from which the slice is copied;
- * _buffer uploads the span only and brings back one slice.  A range of more blocks than the context holds slabs runs
- * in rounds of that many blocks, one host synchronisation each.  Device memory: the span and at most `want` bytes of
- * output (_buffer: two buffers of 4 MiB at least that the context keeps and grows, so a small read allocates nothing),
- * the two staging areas (kept by the context from the first call on) and the context's slabs (a context holds 16 at
+ * written out (_device may have written d_out).  When several blocks fail, the text is that of the lowest-numbered one;
+ * an entry of a corrupt index whose bytes lie outside bz2[0, len) (_buffer: outside the span) reads as zeros: BZX_E_DATA,
+ * "no block magic at bit ...", and that text comes first.  The call is count = 1 of the many-range call below over one
+ * piece, by the same code: blocks wholly inside the range expand at their final place in d_out, the at most two edge
+ * blocks into a device staging pool of 2 x 259/5 x 900,000 bytes, from which one launch of bzx_rg_gather_kernel per
+ * round puts the slices in place; _buffer uploads the span only and brings back one slice.  A range of more blocks than
+ * the context holds slabs runs in rounds of that many blocks, one host synchronisation each; the round that holds the
+ * first failing block is the last.  Device memory: the span and at most `want` bytes of output (_buffer: two buffers of
+ * 4 MiB at least that the context keeps and grows, so a small read allocates nothing), the pool and a slice table of
+ * 96 KiB (kept by the context from the first call on) and the context's slabs (a context holds 16 at
  * least from bzx_ctx_create on, about 450 MB, whatever max_blocks said; a range read never adds to them);
  * nothing depends on the length of the file.  d_bz2 and d_out may have any alignment.  The inverse BWT of these calls
  * is the many-lane walk (one workgroup per block; bzx_stage_ibwt below), since one to three blocks have nothing to hide
@@ -446,8 +450,8 @@ int bzx_decompress_range_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, ui
  *   not in output order), BZX_E_OUTBUF, BZX_E_NOMEM, BZX_E_HIP, BZX_E_STATE (an open bzx_dstream or bzx_index).  count = 0:
  *   BZX_OK.  After any error the context stays usable.
  *   Memory: a block that one range alone touches and wholly contains expands at its final place in d_out; every other
- *   block expands into a staging pool -- the two staging areas of the single call used as one region of about 93 MB, at
- *   256-byte aligned offsets -- from which ONE launch per round of bzx_rg_gather_kernel puts the slices of the verified
+ *   block expands into the staging pool -- about 93 MB, room for the two edge blocks of one range, at 256-byte aligned
+ *   offsets -- from which ONE launch per round of bzx_rg_gather_kernel puts the slices of the verified
  *   blocks in place.  A round takes blocks in ascending order until it holds as many as the context has slabs or the next
  *   pool block does not fit.  Nothing but small tables grows (the block tables, a slice table of 24 bytes per 64 KiB of
  *   slice).  _buffer uploads the pieces that hold a touched block, and nothing else, into the span buffer the context

@@ -414,6 +414,48 @@ def test_emu_range_refusals(emu, oracle):
     L.bzx_index_end(None)
 
 
+def single_text_cases(entries, n):
+    """(name, stale entries, modes, the text bzx_last_error carries): what the single call says when several blocks of one
+    read fail, and when an inner entry points outside the input given.  The texts are those of the single call before it
+    ran on the core of the batched call, recorded then; nothing here is held against the batched call."""
+    pre = "index does not match the input: "
+    both = ("file", "span")
+    far = entries[2].bit + 100000
+    e12 = stale(entries, n, 1, crc=entries[1].crc ^ 4)
+    e12[2].crc ^= 4
+    e01 = stale(entries, n, 0, crc=entries[0].crc ^ 4)
+    e01[1].bit += 1
+    return [("crc of blocks 1 and 2", e12, both, pre + "another stored CRC (block 1)"),
+            ("crc of block 0, bit of block 1", e01, both, pre + "another stored CRC (block 0)"),
+            ("entry 1 behind the input", stale(entries, n, 1, bit=far), both, pre + f"no block magic at bit {far} (block 1)"),
+            ("entry 1 before the span", stale(entries, n, 1, bit=8), ("span",), pre + "no block magic at bit 8 (block 1)")]
+
+
+def check_single_texts(lib, z, want, entries, n):
+    off, w = 0, len(want)
+    for name, e, modes, expected in single_text_cases(entries, n):
+        rc, first, count, lo, hi = lib.span(e, n, off, w)
+        assert (rc, first, count) == (0, 0, 3), name
+        for mode in modes:
+            zz, base = (z, 0) if mode == "file" else (z[lo:hi], lo)
+            rc, got, room, g = lib.range_buffer(zz, base, e, n, off, w)
+            msg = lib.last_error()
+            assert rc == BZX_E_DATA and g == 0 and room == b"\xa5" * w, (name, mode, rc, msg)
+            assert not msg.startswith("range ") and msg == expected, (name, mode, msg)
+            rc, got, _, _ = lib.range_buffer(zz, base, entries, n, off, w)           # the context is as good as new
+            assert rc == 0 and got == want, (name, mode, lib.last_error())
+            assert lib.stats().nblk == 3 and lib.stats().raw_bytes == len(want)
+
+
+def test_emu_range_single_texts(emu, oracle):
+    """The three-block stream of test_emu_range_refusals, the whole output as the range."""
+    b = [W.Block(few(oracle, 70, 21)), W.Block(few(oracle, 60, 22, b"klmno")), W.Block(few(oracle, 50, 23))]
+    z = W.write_stream(oracle, b, 1)
+    entries, n, _ = build(emu, z)
+    assert n == 3
+    check_single_texts(emu, z, bz2.decompress(z), entries, n)
+
+
 # ---- GPU --------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def gpu16():
@@ -589,3 +631,37 @@ def test_gpu_range_refusals_and_small_shapes(gpu16, maker, oracle):
     assert rc == BZX_E_DATA and g == 0 and "index does not match" in gpu16.last_error()
     rc, info2 = gpu16.index_build(bytes(bad))[::2]
     assert rc == BZX_E_DATA and info2.nblk == 10
+    # several failing blocks of one read, an inner entry outside the input: the texts of the CPU part
+    b = [W.Block(few(oracle, 70, 21)), W.Block(few(oracle, 60, 22, b"klmno")), W.Block(few(oracle, 50, 23))]
+    z = W.write_stream(oracle, b, 1)
+    rc, entries, info = gpu16.index_build(z)
+    assert rc == 0 and info.nblk == 3
+    check_single_texts(gpu16, z, bz2.decompress(z), entries, 3)
+
+
+EDGE = (900_000 // 5 * 259 + 16 + 255) & ~255     # half of the pool: room for one expanded block
+
+
+@pytest.mark.gpu
+def test_gpu_range_pool_edges(gpu16, maker):
+    """The pool at its limit through the single call: 128 MiB of zeros are three blocks, of which the first two fill it."""
+    import torch
+    total = 128 << 20
+    z = maker.compress_buffer(bytes(total), 9)
+    assert len(z) < 1000
+    rc, entries, info = gpu16.index_build(z)
+    assert rc == 0 and info.nblk == 3 and info.out_bytes == total
+    n = 3
+    al = [(entries[k].out_len + 255) & ~255 for k in range(n)]
+    assert al[0] + al[1] <= 2 * EDGE < al[0] + al[1] + al[2]
+    d_z = torch.frombuffer(bytearray(z), dtype=torch.uint8).cuda()
+    d_o = torch.empty(total + 64, dtype=torch.uint8, device="cuda")
+    # two edge blocks that fill the pool; blocks 0 and 2 in the pool and block 1 in place
+    for (off, w), nblk in (((entries[1].out_off - 70_001, 140_003), 2), ((entries[0].out_off + 5, total - 11), 3)):
+        d_o.fill_(0xA5)
+        rc, got = gpu16.range_device_raw(d_z.data_ptr(), len(z), 0, entries, n, off, w, d_o.data_ptr() + 3)
+        assert rc == 0 and got == w, (off, w, rc, gpu16.last_error())
+        assert gpu16.stats().nblk == nblk
+        torch.cuda.synchronize()
+        assert int(d_o[3:3 + w].max()) == 0
+        assert d_o[:3].cpu().numpy().tobytes() == b"\xa5" * 3 and int(d_o[3 + w]) == 0xA5
