@@ -31,23 +31,16 @@ extern "C" const char *bzx_strerror(int code)
 
 extern "C" const char *bzx_last_error(const bzx_ctx *ctx) { return ctx ? ctx->err.c_str() : ""; }
 
-template <typename T> static int dev_alloc(bzx_ctx *ctx, std::vector<void *> &owner, T **p, size_t count)
+template <typename T> static int dev_alloc(bzx_ctx *ctx, std::vector<DevMem<>> &owner, T **p, size_t count)
 {
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, count * sizeof(T));
-    if (e != hipSuccess) {
-        ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+    DevMem<> m;
+    if (!m.reserve(count * sizeof(T))) {
+        ctx->err = std::string("hipMalloc: ") + hipGetErrorString(hipGetLastError());
         return BZX_E_NOMEM;
     }
-    owner.push_back(v);
-    *p = (T *)v;
+    *p = m.get<T>();
+    owner.push_back(std::move(m));
     return BZX_OK;
-}
-
-static void free_all(std::vector<void *> &v)
-{
-    for (void *p : v) (void)hipFree(p);
-    v.clear();
 }
 
 // Block descriptors for `nblk` blocks (global block numbers) and per-block slabs for `nslab` of them (the blocks
@@ -58,20 +51,21 @@ int ensure_blocks(bzx_ctx *ctx, uint32_t nblk, uint32_t nslab)
     BzxBatch &B = ctx->B;
     int rc;
     if (nblk > ctx->cap_blocks) {
-        free_all(ctx->descs);
+        ctx->descs.clear();
         ctx->cap_blocks = 0;
         const uint32_t cap = nblk < 16 ? 16 : nblk;
         if ((rc = dev_alloc(ctx, ctx->descs, &B.blk, cap))) return rc;
         if ((rc = dev_alloc(ctx, ctx->descs, &B.plist, (size_t)cap))) return rc;
         if ((rc = dev_alloc(ctx, ctx->descs, &B.redo_list, (size_t)cap))) return rc;
         if ((rc = dev_alloc(ctx, ctx->descs, &B.resume_list, (size_t)cap))) return rc;
-        if (ctx->h_blk) (void)hipHostFree(ctx->h_blk);
-        ctx->h_blk = nullptr;
-        if (hipHostMalloc((void **)&ctx->h_blk, (size_t)cap * sizeof(BzxBlock), 0) != hipSuccess) return BZX_E_NOMEM;
+        if (!ctx->h_blk.reserve((size_t)cap * sizeof(BzxBlock))) {
+            ctx->err = "hipHostMalloc(block descriptors) failed";
+            return BZX_E_NOMEM;
+        }
         ctx->cap_blocks = cap;
     }
     if (nslab <= ctx->cap_slabs) return BZX_OK;
-    free_all(ctx->slabs);
+    ctx->slabs.clear();
     ctx->cap_slabs = 0;
     const uint32_t cap = nslab < 16 ? 16 : nslab;
     if ((rc = dev_alloc(ctx, ctx->slabs, &ctx->d_in, (size_t)cap * BZX_BLK_STRIDE))) return rc;
@@ -106,7 +100,7 @@ int ensure_blocks(bzx_ctx *ctx, uint32_t nblk, uint32_t nslab)
 static int ensure_slots(bzx_ctx *ctx, uint32_t n_slots)
 {
     if (n_slots <= ctx->n_slots) return BZX_OK;
-    free_all(ctx->slot_allocs);
+    ctx->slot_allocs.clear();
     ctx->n_slots = 0;
     std::vector<BzxSortWs> h(n_slots);
     int rc;
@@ -167,10 +161,8 @@ extern "C" int bzx_ctx_create(int device, uint32_t max_blocks, bzx_ctx **out)
         bzx_ctx_destroy(ctx);
         return BZX_E_HIP;
     }
-    bool ok = hipMalloc((void **)&ctx->d_counters, BZX_N_COUNTERS * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc((void **)&ctx->d_scalars, 8 * sizeof(uint64_t)) == hipSuccess &&
-              hipHostMalloc((void **)&ctx->h_scalars, 8 * sizeof(uint64_t), 0) == hipSuccess &&
-              hipHostMalloc((void **)&ctx->h_counters, 64 * sizeof(uint32_t), 0) == hipSuccess;
+    bool ok = ctx->d_counters.reserve(BZX_N_COUNTERS * sizeof(uint32_t)) && ctx->d_scalars.reserve(8 * sizeof(uint64_t)) &&
+              ctx->h_scalars.reserve(8 * sizeof(uint64_t)) && ctx->h_counters.reserve(64 * sizeof(uint32_t));
     if (!ok || ensure_blocks(ctx, max_blocks ? max_blocks : 16) != BZX_OK) {
         bzx_ctx_destroy(ctx);
         return BZX_E_NOMEM;
@@ -189,24 +181,7 @@ extern "C" void bzx_ctx_destroy(bzx_ctx *ctx)
     }
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
-    free_all(ctx->slabs);
-    free_all(ctx->descs);
-    free_all(ctx->slot_allocs);
-    if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
-    if (ctx->split_ws) (void)hipFree(ctx->split_ws);
-    if (ctx->batch_ws) (void)hipFree(ctx->batch_ws);
-    if (ctx->dbatch_ws) (void)hipFree(ctx->dbatch_ws);
-    if (ctx->range_ws) (void)hipFree(ctx->range_ws);
-    if (ctx->range_pin) (void)hipHostFree(ctx->range_pin);
-    if (ctx->range_sl) (void)hipFree(ctx->range_sl);
-    for (int i = 0; i < 2; i++)
-        if (ctx->range_io[i]) (void)hipFree(ctx->range_io[i]);
-    for (int i = 0; i < 2; i++)
-        if (ctx->dbatch_pin[i]) (void)hipHostFree(ctx->dbatch_pin[i]);
-    if (ctx->h_blk) (void)hipHostFree(ctx->h_blk);
-    if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);
-    if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
+    // (the device is current and both streams are idle: `delete` below frees every buffer the context owns)
     if (ctx->ev_b1) (void)hipEventDestroy(ctx->ev_b1);
     if (ctx->ev_b2) (void)hipEventDestroy(ctx->ev_b2);
     if (ctx->ev_b3) (void)hipEventDestroy(ctx->ev_b3);
@@ -397,15 +372,9 @@ int run_stages(bzx_ctx *ctx, uint32_t nblk, int stages, int out_level, void *d_s
 
 int bzx_ctx_split_scratch(bzx_ctx *ctx, size_t bytes, void **p)
 {
-    if (bytes > ctx->split_ws_bytes) {
-        if (ctx->split_ws) (void)hipFree(ctx->split_ws);
-        ctx->split_ws = nullptr;
-        ctx->split_ws_bytes = 0;
-        if (hipMalloc(&ctx->split_ws, bytes) != hipSuccess) {
-            ctx->err = "hipMalloc(split scratch) failed";
-            return BZX_E_NOMEM;
-        }
-        ctx->split_ws_bytes = bytes;
+    if (!ctx->split_ws.reserve(bytes)) {
+        ctx->err = "hipMalloc(split scratch) failed";
+        return BZX_E_NOMEM;
     }
     *p = ctx->split_ws;
     return BZX_OK;
@@ -806,13 +775,16 @@ static int split_to_host(bzx_ctx *ctx, const uint8_t *pre, size_t npre, const ui
 {
     const size_t total = npre + len;
     if (total == 0) return BZX_OK;
-    void *d_raw = nullptr;
-    if (hipMalloc(&d_raw, total) != hipSuccess) return BZX_E_NOMEM;
+    DevMem<> d_raw;                          // (freed on return, behind the synchronisation below)
+    if (!d_raw.reserve(total)) {
+        ctx->err = "hipMalloc(split input) failed";
+        return BZX_E_NOMEM;
+    }
     int rc = BZX_OK;
     uint32_t nblk = 0, use = 0;
     if (npre && hipMemcpyAsync(d_raw, pre, npre, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = BZX_E_HIP;
-    if (!rc && len && hipMemcpyAsync((uint8_t *)d_raw + npre, raw, len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = BZX_E_HIP;
-    if (!rc) rc = split_on_device(ctx, (const uint8_t *)d_raw, total, level, &nblk, 0, 1, last_start);
+    if (!rc && len && hipMemcpyAsync(d_raw + npre, raw, len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = BZX_E_HIP;
+    if (!rc) rc = split_on_device(ctx, d_raw, total, level, &nblk, 0, 1, last_start);
     if (!rc) {
         use = final ? nblk : nblk - 1;
         if (use > nblk_cap) rc = BZX_E_OUTBUF;
@@ -831,12 +803,11 @@ static int split_to_host(bzx_ctx *ctx, const uint8_t *pre, size_t npre, const ui
             break;
         }
         const uint64_t off = ctx->h_blk[b].in_off;
-        const uint8_t *src = (off & BZX_IN_RAW) ? (const uint8_t *)d_raw + (off & ~BZX_IN_RAW) : ctx->d_in + off;
+        const uint8_t *src = (off & BZX_IN_RAW) ? d_raw + (off & ~BZX_IN_RAW) : ctx->d_in + off;
         if (hipMemcpy(blocks_out + (size_t)b * BZX_MAX_BLOCK, src, ns[b], hipMemcpyDeviceToHost) != hipSuccess)
             rc = BZX_E_HIP;
     }
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_raw);
     if (!rc) *nblk_out = use;
     return rc;
 }
@@ -1141,14 +1112,14 @@ extern "C" int bzx_dbg_phase_timers(bzx_ctx *ctx, int enable, unsigned long long
 {
     if (!ctx) return BZX_E_PARAM;
     if (enable && !ctx->d_dbg) {
-        if (hipMalloc((void **)&ctx->d_dbg, 128 * sizeof(unsigned long long)) != hipSuccess) return BZX_E_NOMEM;
+        if (!ctx->d_dbg.reserve(128 * sizeof(unsigned long long))) return BZX_E_NOMEM;
     }
     if (out && ctx->d_dbg) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipMemcpy(out, ctx->d_dbg, 128 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     }
     if (ctx->d_dbg) HIP_TRY(ctx, hipMemset(ctx->d_dbg, 0, 128 * sizeof(unsigned long long)));
-    ctx->B.dbg = enable ? ctx->d_dbg : nullptr;
+    ctx->B.dbg = enable ? ctx->d_dbg.get() : nullptr;
     return BZX_OK;
 }
 

@@ -348,42 +348,30 @@ extern "C" size_t bzx_compress_batch_bound(uint32_t count, const size_t *lens)
 // Carves the device tables of a batch call out of ctx->batch_ws (grown on demand).
 static int batch_ws_alloc(bzx_ctx *ctx, uint32_t count, uint64_t ntiles, uint64_t nslots, uint32_t max_round, BzxBatchWs *ws)
 {
-    const size_t words = (size_t)count * (sizeof(BzxSeg) / 8) + (ntiles + 8) / 2 + 3 * (ntiles + 2) + 2 * (nslots + 2) +
-                         (nslots + 8) / 2 + 2 * ((size_t)count + 2) / 2 + ((size_t)max_round + 8) / 2 + ((size_t)max_round + 2) +
-                         2 * ((size_t)count + 2) + 2 + bzx_split_scan_words(ntiles) + 16;
-    const size_t bytes = words * 8;
-    if (bytes > ctx->batch_ws_bytes) {
-        if (ctx->batch_ws) (void)hipFree(ctx->batch_ws);
-        ctx->batch_ws = nullptr;
-        ctx->batch_ws_bytes = 0;
-        if (hipMalloc(&ctx->batch_ws, bytes) != hipSuccess) {
-            ctx->err = "hipMalloc(batch tables) failed";
-            return BZX_E_NOMEM;
-        }
-        ctx->batch_ws_bytes = bytes;
+    const bool ok = carved(ctx->batch_ws, 8, [&](Carver &c) {
+        auto take = [&](size_t nwords) { return c.take<uint64_t>(nwords); };
+        ws->seg = (BzxSeg *)take((size_t)count * (sizeof(BzxSeg) / 8));
+        ws->tile_seg = (uint32_t *)take((ntiles + 8) / 2);
+        ws->tile_rs = take(ntiles + 2);
+        ws->tile_off = take(ntiles + 2);
+        ws->tile_np = take(ntiles + 2);
+        ws->blk_raw = take(nslots + 2);
+        ws->blk_f = take(nslots + 2);
+        ws->blk_plain = (uint32_t *)take((nslots + 8) / 2);
+        ws->seg_nblk = (uint32_t *)take(((size_t)count + 2) / 2);
+        ws->seg_blk = (uint32_t *)take(((size_t)count + 2) / 2);
+        ws->blk_seg = (uint32_t *)take(((size_t)max_round + 8) / 2);
+        ws->pre = take((size_t)max_round + 2);
+        ws->s_off = take((size_t)count + 2);
+        ws->s_len = take((size_t)count + 2);
+        ws->round_end = take(2);
+        ws->segtot = take(bzx_split_scan_words(ntiles));
+        take(16 + 1);        // slack nobody uses: 16 words, and the one an odd count leaves between seg_nblk and seg_blk
+    });
+    if (!ok) {
+        ctx->err = "hipMalloc(batch tables) failed";
+        return BZX_E_NOMEM;
     }
-    uint64_t *q = (uint64_t *)ctx->batch_ws;
-    auto take = [&](size_t nwords) {
-        uint64_t *p = q;
-        q += nwords;
-        return p;
-    };
-    ws->seg = (BzxSeg *)take((size_t)count * (sizeof(BzxSeg) / 8));
-    ws->tile_seg = (uint32_t *)take((ntiles + 8) / 2);
-    ws->tile_rs = take(ntiles + 2);
-    ws->tile_off = take(ntiles + 2);
-    ws->tile_np = take(ntiles + 2);
-    ws->blk_raw = take(nslots + 2);
-    ws->blk_f = take(nslots + 2);
-    ws->blk_plain = (uint32_t *)take((nslots + 8) / 2);
-    ws->seg_nblk = (uint32_t *)take(((size_t)count + 2) / 2);
-    ws->seg_blk = (uint32_t *)take(((size_t)count + 2) / 2);
-    ws->blk_seg = (uint32_t *)take(((size_t)max_round + 8) / 2);
-    ws->pre = take((size_t)max_round + 2);
-    ws->s_off = take((size_t)count + 2);
-    ws->s_len = take((size_t)count + 2);
-    ws->round_end = take(2);
-    ws->segtot = take(bzx_split_scan_words(ntiles));
     ws->ntiles = ntiles;
     ws->count = count;
     return BZX_OK;
@@ -637,13 +625,12 @@ static int batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws
     std::vector<const void *> d_raws(count, nullptr);
     const size_t bound = bzx_compress_batch_bound(count, lens);
     const size_t dcap = (cap < bound ? cap : bound) & ~(size_t)3;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    if (hipMalloc((void **)&d_in, staged ? staged : 16) != hipSuccess) {
+    DevMem<> d_in, d_out;                    // (freed on return, behind the synchronisation below)
+    if (!d_in.reserve(staged ? staged : 16)) {
         ctx->err = "hipMalloc(batch inputs) failed";
         return BZX_E_NOMEM;
     }
-    if (hipMalloc((void **)&d_out, dcap ? dcap : 4) != hipSuccess) {
-        (void)hipFree(d_in);
+    if (!d_out.reserve(dcap ? dcap : 4)) {
         ctx->err = "hipMalloc(batch output) failed";
         return BZX_E_NOMEM;
     }
@@ -655,7 +642,12 @@ static int batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws
             rc = BZX_E_HIP;
         }
     }
-    if (!rc) rc = batch_run(ctx, count, d_raws.data(), lens, level, d_out, dcap, out_offs, out_lens);
+    try {
+        if (!rc) rc = batch_run(ctx, count, d_raws.data(), lens, level, d_out, dcap, out_offs, out_lens);
+    } catch (const std::bad_alloc &) {             // (caught here: the buffers must outlive what is in flight)
+        ctx->err = "out of host memory";
+        rc = BZX_E_NOMEM;
+    }
     if (!rc) {
         const size_t end = out_offs[count - 1] + round_up4(out_lens[count - 1]);
         if (hipMemcpyAsync(out, d_out, end, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
@@ -664,7 +656,5 @@ static int batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws
         }
     }
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     return rc;
 }

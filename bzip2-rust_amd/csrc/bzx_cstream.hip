@@ -60,17 +60,15 @@ bool ChunkLane::alloc(size_t in_cap, size_t out_cap, uint32_t blk_cap)
 {
     bool ok = true;
     for (int i = 0; i < 2 && ok; i++) {
-        ok = hipMalloc((void **)&d_in[i], in_cap) == hipSuccess && hipMalloc((void **)&d_out[i], out_cap) == hipSuccess &&
+        ok = d_in[i].reserve(in_cap) && d_out[i].reserve(out_cap) &&
              hipEventCreateWithFlags(&ev_h2d[i], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&ev_done[i], hipEventDisableTiming) == hipSuccess &&
-             hipHostMalloc((void **)&h_info[i], 4 * sizeof(uint64_t), 0) == hipSuccess &&
-             hipHostMalloc((void **)&h_blk[i], (size_t)blk_cap * sizeof(BzxBlock), 0) == hipSuccess;
+             h_info[i].reserve(4 * sizeof(uint64_t)) && h_blk[i].reserve((size_t)blk_cap * sizeof(BzxBlock));
     }
     device_bytes = 2 * in_cap + 2 * out_cap + 4 * sizeof(uint64_t);
     pinned_bytes = 2 * (4 * sizeof(uint64_t) + (size_t)blk_cap * sizeof(BzxBlock)) + 16;
     return ok && hipEventCreateWithFlags(&ev_d2h, hipEventDisableTiming) == hipSuccess &&
-           hipMalloc((void **)&d_phase, 4 * sizeof(uint64_t)) == hipSuccess &&
-           hipHostMalloc((void **)&h_w0, 16, 0) == hipSuccess &&
+           d_phase.reserve(4 * sizeof(uint64_t)) && h_w0.reserve(16) &&
            hipStreamCreateWithFlags(&s_h2d, hipStreamNonBlocking) == hipSuccess &&
            hipStreamCreateWithFlags(&s_d2h, hipStreamNonBlocking) == hipSuccess;
 }
@@ -79,17 +77,17 @@ void ChunkLane::free()
 {
     if (s_h2d) (void)hipStreamSynchronize(s_h2d);
     if (s_d2h) (void)hipStreamSynchronize(s_d2h);
-    for (int i = 0; i < 2; i++) {
-        if (d_in[i]) (void)hipFree(d_in[i]);
-        if (d_out[i]) (void)hipFree(d_out[i]);
+    for (int i = 0; i < 2; i++) {              // (here, with the lane's device current: not left to the destructor)
+        d_in[i].reset();
+        d_out[i].reset();
+        h_info[i].reset();
+        h_blk[i].reset();
         if (ev_h2d[i]) (void)hipEventDestroy(ev_h2d[i]);
         if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
-        if (h_info[i]) (void)hipHostFree(h_info[i]);
-        if (h_blk[i]) (void)hipHostFree(h_blk[i]);
     }
+    d_phase.reset();
+    h_w0.reset();
     if (ev_d2h) (void)hipEventDestroy(ev_d2h);
-    if (d_phase) (void)hipFree(d_phase);
-    if (h_w0) (void)hipHostFree(h_w0);
     if (s_h2d) (void)hipStreamDestroy(s_h2d);
     if (s_d2h) (void)hipStreamDestroy(s_d2h);
 }

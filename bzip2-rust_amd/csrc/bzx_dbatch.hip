@@ -137,36 +137,13 @@ __global__ __launch_bounds__(DB_NT) void bzx_db_layout_kernel(BzxBatch B, DbIo *
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-static int db_pin(bzx_ctx *ctx, int k, size_t bytes, void **p)
+// The tables of a call are carved out of ctx->dbatch_ws and ctx->dbatch_pin[0], both grown on demand: first the scan's,
+// then -- the scan's are dead by then -- the rounds'.  Every table starts on a 16-byte boundary.
+template <typename M, typename F> static int db_tables(bzx_ctx *ctx, M &mem, const char *what, F &&layout)
 {
-    if (bytes > ctx->dbatch_pin_bytes[k]) {
-        if (ctx->dbatch_pin[k]) (void)hipHostFree(ctx->dbatch_pin[k]);
-        ctx->dbatch_pin[k] = nullptr;
-        ctx->dbatch_pin_bytes[k] = 0;
-        if (hipHostMalloc(&ctx->dbatch_pin[k], bytes, 0) != hipSuccess) {
-            ctx->err = "hipHostMalloc(batch decompression tables) failed";
-            return BZX_E_NOMEM;
-        }
-        ctx->dbatch_pin_bytes[k] = bytes;
-    }
-    *p = ctx->dbatch_pin[k];
-    return BZX_OK;
-}
-
-static int db_dev(bzx_ctx *ctx, size_t bytes, void **p)
-{
-    if (bytes > ctx->dbatch_ws_bytes) {
-        if (ctx->dbatch_ws) (void)hipFree(ctx->dbatch_ws);
-        ctx->dbatch_ws = nullptr;
-        ctx->dbatch_ws_bytes = 0;
-        if (hipMalloc(&ctx->dbatch_ws, bytes) != hipSuccess) {
-            ctx->err = "hipMalloc(batch decompression tables) failed";
-            return BZX_E_NOMEM;
-        }
-        ctx->dbatch_ws_bytes = bytes;
-    }
-    *p = ctx->dbatch_ws;
-    return BZX_OK;
+    if (carved(mem, 16, layout)) return BZX_OK;
+    ctx->err = std::string(what) + "(batch decompression tables) failed";
+    return BZX_E_NOMEM;
 }
 
 static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -214,25 +191,23 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
     DbCand *h_cand = nullptr;
     for (int pass = 0;; pass++) {
         if (cap_cand > 0xffffffffu) cap_cand = 0xffffffffu;
-        const size_t ws_bytes = al16(count * sizeof(DbIn)) + al16(ntiles * 4) + al16(cap_cand * sizeof(DbCand)) +
-                                al16((size_t)count * 4) + 16;
-        void *ws = nullptr, *pin = nullptr;
-        int rc = db_dev(ctx, ws_bytes, &ws);
+        DbIn *d_in = nullptr;
+        DbCand *d_cand = nullptr;
+        uint32_t *d_tile_in = nullptr, *d_level = nullptr, *d_ncand = nullptr, *h_level = nullptr, *h_ncand = nullptr;
+        int rc = db_tables(ctx, ctx->dbatch_ws, "hipMalloc", [&](Carver &c) {
+            d_in = c.take<DbIn>(count);
+            d_tile_in = c.take<uint32_t>(ntiles);
+            d_cand = c.take<DbCand>(cap_cand);
+            d_level = c.take<uint32_t>(count);
+            d_ncand = c.take<uint32_t>(4);
+        });
         if (rc) return rc;
-        if ((rc = db_pin(ctx, 0, al16(cap_cand * sizeof(DbCand)) + al16((size_t)count * 4) + 16, &pin))) return rc;
-        uint8_t *q = (uint8_t *)ws;
-        DbIn *d_in = (DbIn *)q;
-        q += al16(count * sizeof(DbIn));
-        uint32_t *d_tile_in = (uint32_t *)q;
-        q += al16(ntiles * 4);
-        DbCand *d_cand = (DbCand *)q;
-        q += al16(cap_cand * sizeof(DbCand));
-        uint32_t *d_level = (uint32_t *)q;
-        q += al16((size_t)count * 4);
-        uint32_t *d_ncand = (uint32_t *)q;
-        h_cand = (DbCand *)pin;
-        uint32_t *h_level = (uint32_t *)((uint8_t *)pin + al16(cap_cand * sizeof(DbCand)));
-        uint32_t *h_ncand = h_level + al16((size_t)count * 4) / 4;
+        rc = db_tables(ctx, ctx->dbatch_pin[0], "hipHostMalloc", [&](Carver &c) {
+            h_cand = c.take<DbCand>(cap_cand);
+            h_level = c.take<uint32_t>(count);
+            h_ncand = c.take<uint32_t>(4);
+        });
+        if (rc) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(d_in, in.data(), count * sizeof(DbIn), hipMemcpyHostToDevice, st));
         if (ntiles) HIP_TRY(ctx, hipMemcpyAsync(d_tile_in, tile_in.data(), ntiles * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemsetAsync(d_level, 0, (size_t)count * 4, st));
@@ -278,50 +253,39 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
     }
     int rc = ensure_blocks(ctx, R);
     if (rc) return rc;
-    // ---- round tables: device [src R][dst R][got R][chain R][io count][end], pinned [io count][got R]
-    {
-        const size_t dev = al16((size_t)R * sizeof(BzxDcSrc)) + al16((size_t)R * sizeof(BzxDcDst)) + al16((size_t)R * 4) * 2 +
-                           al16((size_t)count * sizeof(DbIo)) + 16;
-        // the scan's tables are dead: the round tables reuse the workspace
-        void *ws = nullptr;
-        if ((rc = db_dev(ctx, dev, &ws))) return rc;
-    }
-    uint8_t *q = (uint8_t *)ctx->dbatch_ws;
-    BzxDcSrc *d_src = (BzxDcSrc *)q;
-    q += al16((size_t)R * sizeof(BzxDcSrc));
-    BzxDcDst *d_dst = (BzxDcDst *)q;
-    q += al16((size_t)R * sizeof(BzxDcDst));
-    uint32_t *d_got = (uint32_t *)q;
-    q += al16((size_t)R * 4);
-    uint32_t *d_chain = (uint32_t *)q;
-    q += al16((size_t)R * 4);
-    DbIo *d_io = (DbIo *)q;
-    q += al16((size_t)count * sizeof(DbIo));
-    uint64_t *d_end = (uint64_t *)q;
-    void *pin = nullptr;
-    if ((rc = db_pin(ctx, 0, al16((size_t)count * sizeof(DbIo)) + al16((size_t)R * 4) + 16, &pin))) return rc;
-    DbIo *h_io = (DbIo *)pin;
-    uint32_t *h_got = (uint32_t *)((uint8_t *)pin + al16((size_t)count * sizeof(DbIo)));
-    uint64_t *h_end = (uint64_t *)(h_got + al16((size_t)R * 4) / 4);
+    // ---- round tables: device [src R][dst R][got R][chain R][io count][end], pinned [io count][got R][end]
+    BzxDcSrc *d_src = nullptr;
+    BzxDcDst *d_dst = nullptr;
+    uint32_t *d_got = nullptr, *d_chain = nullptr, *h_got = nullptr;
+    DbIo *d_io = nullptr, *h_io = nullptr;
+    uint64_t *d_end = nullptr, *h_end = nullptr;
+    rc = db_tables(ctx, ctx->dbatch_ws, "hipMalloc", [&](Carver &c) {
+        d_src = c.take<BzxDcSrc>(R);
+        d_dst = c.take<BzxDcDst>(R);
+        d_got = c.take<uint32_t>(R);
+        d_chain = c.take<uint32_t>(R);
+        d_io = c.take<DbIo>(count);
+        d_end = c.take<uint64_t>(2);
+    });
+    if (rc) return rc;
+    rc = db_tables(ctx, ctx->dbatch_pin[0], "hipHostMalloc", [&](Carver &c) {
+        h_io = c.take<DbIo>(count);
+        h_got = c.take<uint32_t>(R);
+        h_end = c.take<uint64_t>(2);
+    });
+    if (rc) return rc;
 
     BzxBatch &B = ctx->B;
     B.blk_first = 0;
     B.blk_step = 1;
-    struct Staging {                             // _buffer form: the round's outputs, packed
-        uint8_t *p = nullptr;
-        size_t bytes = 0;
-        ~Staging()
-        {
-            if (p) (void)hipFree(p);
-        }
-    } stg;
+    DevMem<> stg;                                // _buffer form: the round's outputs, packed
     struct Pending {                             // _buffer form: outputs of the last round, in the bounce buffer
         uint32_t i;
         uint64_t at, n;
     };
     std::vector<Pending> pending;
     auto drain = [&]() {                         // after a synchronisation: the bounce buffer holds them
-        for (const Pending &p : pending) memcpy(h_outs[p.i], (const uint8_t *)ctx->dbatch_pin[1] + p.at, p.n);
+        for (const Pending &p : pending) memcpy(h_outs[p.i], ctx->dbatch_pin[1] + p.at, p.n);
         pending.clear();
     };
     std::vector<BzxDcSrc> src;
@@ -432,15 +396,9 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
         }
         for (uint32_t b = 0; b < nb; b++)
             if (!on_chain[b]) ctx->h_blk[b].status |= DC_SKIP;
-        if (!d_outs && staging_need > stg.bytes) {
-            if (stg.p) (void)hipFree(stg.p);
-            stg.p = nullptr;
-            stg.bytes = 0;
-            if (hipMalloc((void **)&stg.p, staging_need) != hipSuccess) {
-                ctx->err = "hipMalloc(batch output staging) failed";
-                return BZX_E_NOMEM;
-            }
-            stg.bytes = staging_need;
+        if (!d_outs && !stg.reserve(staging_need)) {
+            ctx->err = "hipMalloc(batch output staging) failed";
+            return BZX_E_NOMEM;
         }
         // ---- inverse BWT, layout, expansion and CRCs of the chain blocks; no synchronisation in between
         if (nb) {
@@ -451,7 +409,7 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
         }
         HIP_TRY(ctx, hipMemcpyAsync(d_io, h_io, nio * sizeof(DbIo), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(bzx_db_layout_kernel, dim3(1), dim3(DB_NT), 0, st, B, d_io, nio, d_chain,
-                           d_outs ? nullptr : stg.p, d_dst, d_end);
+                           d_outs ? nullptr : stg.get(), d_dst, d_end);
         if (nb) {
             bzx_launch_dc_expand(B, ctx->d_in, d_dst, st);
             bzx_launch_dc_crc(B, d_dst, d_got, (uint32_t)ctx->n_cu, st);
@@ -503,9 +461,12 @@ static int dbatch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_srcs, c
             if (!d_outs && io.total) pending.push_back(Pending{i, io.at, io.total});
         }
         if (!d_outs && *h_end) {                             // the round's outputs, one copy into the bounce buffer
-            void *bounce = nullptr;
-            if ((rc = db_pin(ctx, 1, *h_end, &bounce))) break;
-            if (hipMemcpyAsync(bounce, stg.p, *h_end, hipMemcpyDeviceToHost, st) != hipSuccess) {
+            if (!ctx->dbatch_pin[1].reserve(*h_end)) {
+                ctx->err = "hipHostMalloc(batch decompression tables) failed";
+                rc = BZX_E_NOMEM;
+                break;
+            }
+            if (hipMemcpyAsync(ctx->dbatch_pin[1], stg, *h_end, hipMemcpyDeviceToHost, st) != hipSuccess) {
                 ctx->err = "hipMemcpyAsync(batch output) failed";
                 rc = BZX_E_HIP;
                 break;
@@ -621,8 +582,7 @@ extern "C" int bzx_decompress_batch_buffer(bzx_ctx *ctx, uint32_t count, const u
         ctx->err = "hipSetDevice failed";
         rc = BZX_E_HIP;
     }
-    uint8_t *d_in = nullptr;
-    size_t d_in_bytes = 0;
+    DevMem<> d_in;                               // the staged inputs of a group (freed on return, behind the synchronisations)
     if (!rc) {
         (void)hipEventRecord(ctx->ev[5], ctx->stream);
         try {
@@ -632,16 +592,10 @@ extern "C" int bzx_decompress_batch_buffer(bzx_ctx *ctx, uint32_t count, const u
                 uint32_t g1 = g0;
                 size_t staged = 0;
                 while (g1 < count && (g1 == g0 || staged + al16(src_lens[g1]) <= DB_GROUP_BYTES)) staged += al16(src_lens[g1++]);
-                if (staged > d_in_bytes) {
-                    if (d_in) (void)hipFree(d_in);
-                    d_in = nullptr;
-                    d_in_bytes = 0;
-                    if (hipMalloc((void **)&d_in, staged ? staged : 16) != hipSuccess) {
-                        ctx->err = "hipMalloc(batch inputs) failed";
-                        rc = BZX_E_NOMEM;
-                        break;
-                    }
-                    d_in_bytes = staged;
+                if (!d_in.reserve(staged)) {
+                    ctx->err = "hipMalloc(batch inputs) failed";
+                    rc = BZX_E_NOMEM;
+                    break;
                 }
                 std::vector<const void *> d_srcs(g1 - g0, nullptr);
                 size_t at = 0;
@@ -670,7 +624,6 @@ extern "C" int bzx_decompress_batch_buffer(bzx_ctx *ctx, uint32_t count, const u
             rc = BZX_E_NOMEM;
         }
         (void)hipStreamSynchronize(ctx->stream);
-        if (d_in) (void)hipFree(d_in);
         if (!rc) {
             float ms = 0.f;
             (void)hipEventRecord(ctx->ev[7], ctx->stream);
@@ -729,17 +682,14 @@ extern "C" int bzx_decompress_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t le
     if (!ctx || !bz2 || !out_len || (cap && !out)) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *out_len = 0;
-    void *d_z = nullptr, *d_o = nullptr;
-    if (hipMalloc(&d_z, len + 64) != hipSuccess) return BZX_E_NOMEM;
-    if (hipMalloc(&d_o, cap + 64) != hipSuccess) {
-        (void)hipFree(d_z);
+    DevMem<> d_z, d_o;                           // (freed on return, behind the synchronisation below)
+    if (!d_z.reserve(len + 64) || !d_o.reserve(cap + 64)) {
+        ctx->err = "bzx_decompress_buffer: device allocation failed";
         return BZX_E_NOMEM;
     }
     int rc = hipMemcpyAsync(d_z, bz2, len, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? BZX_OK : BZX_E_HIP;
     if (!rc) rc = dbatch_one(ctx, d_z, len, d_o, cap, out_len, false);
     if (!rc && *out_len && hipMemcpy(out, d_o, *out_len, hipMemcpyDeviceToHost) != hipSuccess) rc = BZX_E_HIP;
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_z);
-    (void)hipFree(d_o);
     return rc;
 }

@@ -319,14 +319,18 @@ struct bzx_dstream {
     bzx_ctx *ctx = nullptr;
     size_t max_chunk = 0, in_cap = 0;
     uint32_t cap_cand = 0, R = 0;
-    uint8_t *d_in[2] = {nullptr, nullptr};
-    uint8_t *d_stage[2] = {nullptr, nullptr}, *h_stage[2] = {nullptr, nullptr};
-    uint64_t *d_cand = nullptr, *h_cand = nullptr;         // h_cand[cap_cand]: the window's candidates, sorted
-    uint32_t *d_ncand = nullptr, *h_ncand = nullptr;
-    BzxDcSrc *d_src = nullptr, *h_src = nullptr;
-    BzxDcDst *d_dst = nullptr;
-    uint32_t *d_chain = nullptr, *d_got = nullptr;
-    DsRec *d_rec = nullptr, *h_rec = nullptr;
+    DevMem<uint8_t> d_in[2], d_stage[2];
+    PinMem<uint8_t> h_stage[2];
+    DevMem<uint64_t> d_cand;
+    PinMem<uint64_t> h_cand;                               // h_cand[cap_cand]: the window's candidates, sorted
+    DevMem<uint32_t> d_ncand;
+    PinMem<uint32_t> h_ncand;
+    DevMem<BzxDcSrc> d_src;
+    PinMem<BzxDcSrc> h_src;
+    DevMem<BzxDcDst> d_dst;
+    DevMem<uint32_t> d_chain, d_got;
+    DevMem<DsRec> d_rec;
+    PinMem<DsRec> h_rec;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     hipEvent_t ev_h2d = nullptr, ev_carry = nullptr, ev_d2h[2] = {nullptr, nullptr};
     // input
@@ -359,8 +363,9 @@ struct bzx_dstream {
     float ms = 0.f;
     // index mode (bzx_index_*): nothing is copied back or handed out; the placed blocks' figures come with the record
     bzx_index *ix = nullptr;
-    uint32_t *d_meta = nullptr;
-    DsIxRec *d_ix = nullptr, *h_ix = nullptr;
+    DevMem<uint32_t> d_meta;
+    DevMem<DsIxRec> d_ix;
+    PinMem<DsIxRec> h_ix;
 };
 
 extern "C" void bzx_dstream_end(bzx_dstream *s)
@@ -375,26 +380,9 @@ extern "C" void bzx_dstream_end(bzx_dstream *s)
     }
     if (s->s_h2d) (void)hipStreamSynchronize(s->s_h2d);
     if (s->s_d2h) (void)hipStreamSynchronize(s->s_d2h);
-    for (int i = 0; i < 2; i++) {
-        if (s->d_in[i]) (void)hipFree(s->d_in[i]);
-        if (s->d_stage[i]) (void)hipFree(s->d_stage[i]);
-        if (s->h_stage[i]) (void)hipHostFree(s->h_stage[i]);
+    // (the device is current and the three streams are idle: `delete` below frees every buffer the stream owns)
+    for (int i = 0; i < 2; i++)
         if (s->ev_d2h[i]) (void)hipEventDestroy(s->ev_d2h[i]);
-    }
-    if (s->d_cand) (void)hipFree(s->d_cand);
-    if (s->h_cand) (void)hipHostFree(s->h_cand);
-    if (s->d_ncand) (void)hipFree(s->d_ncand);
-    if (s->h_ncand) (void)hipHostFree(s->h_ncand);
-    if (s->d_src) (void)hipFree(s->d_src);
-    if (s->h_src) (void)hipHostFree(s->h_src);
-    if (s->d_dst) (void)hipFree(s->d_dst);
-    if (s->d_chain) (void)hipFree(s->d_chain);
-    if (s->d_got) (void)hipFree(s->d_got);
-    if (s->d_rec) (void)hipFree(s->d_rec);
-    if (s->h_rec) (void)hipHostFree(s->h_rec);
-    if (s->d_meta) (void)hipFree(s->d_meta);
-    if (s->d_ix) (void)hipFree(s->d_ix);
-    if (s->h_ix) (void)hipHostFree(s->h_ix);
     if (s->ev_h2d) (void)hipEventDestroy(s->ev_h2d);
     if (s->ev_carry) (void)hipEventDestroy(s->ev_carry);
     if (s->s_h2d) (void)hipStreamDestroy(s->s_h2d);
@@ -424,28 +412,28 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bzx_dstream **ou
     s->cap_cand = (uint32_t)std::min<size_t>(s->in_cap / 256 + 1024, 0x7fffffffu);
     const size_t R = s->R;
     uint64_t dev = 0, pin = 0;
-    auto dmal = [&](void **p, size_t n) {
+    auto dmal = [&](auto &m, size_t n) {
         dev += n;
-        return hipMalloc(p, n) == hipSuccess;
+        return m.reserve(n);
     };
-    auto hmal = [&](void **p, size_t n) {
+    auto hmal = [&](auto &m, size_t n) {
         pin += n;
-        return hipHostMalloc(p, n, 0) == hipSuccess;
+        return m.reserve(n);
     };
     bool ok = true;
     for (int i = 0; i < 2 && ok; i++)
-        ok = dmal((void **)&s->d_in[i], s->in_cap) && (index && i ? true : dmal((void **)&s->d_stage[i], DS_STAGE_BYTES)) &&
-             (index || hmal((void **)&s->h_stage[i], DS_STAGE_BYTES)) &&
+        ok = dmal(s->d_in[i], s->in_cap) && (index && i ? true : dmal(s->d_stage[i], DS_STAGE_BYTES)) &&
+             (index || hmal(s->h_stage[i], DS_STAGE_BYTES)) &&
              hipEventCreateWithFlags(&s->ev_d2h[i], hipEventDisableTiming) == hipSuccess;
     if (index)                                               // (zeroed: a pass copies the whole R-entry table back and
-        ok = ok && dmal((void **)&s->d_meta, R * 4) &&       // writes the entries of the blocks it placed only)
-             dmal((void **)&s->d_ix, R * sizeof(DsIxRec)) && hmal((void **)&s->h_ix, R * sizeof(DsIxRec)) &&
+        ok = ok && dmal(s->d_meta, R * 4) &&       // writes the entries of the blocks it placed only)
+             dmal(s->d_ix, R * sizeof(DsIxRec)) && hmal(s->h_ix, R * sizeof(DsIxRec)) &&
              hipMemset(s->d_ix, 0, R * sizeof(DsIxRec)) == hipSuccess;
-    ok = ok && dmal((void **)&s->d_cand, (size_t)s->cap_cand * 8) && hmal((void **)&s->h_cand, (size_t)s->cap_cand * 8) &&
-         dmal((void **)&s->d_ncand, 64) && hmal((void **)&s->h_ncand, 64) && dmal((void **)&s->d_src, R * sizeof(BzxDcSrc)) &&
-         hmal((void **)&s->h_src, R * sizeof(BzxDcSrc)) && dmal((void **)&s->d_dst, R * sizeof(BzxDcDst)) &&
-         dmal((void **)&s->d_chain, R * 4) && dmal((void **)&s->d_got, R * 4) && dmal((void **)&s->d_rec, sizeof(DsRec)) &&
-         hmal((void **)&s->h_rec, sizeof(DsRec)) && hipEventCreateWithFlags(&s->ev_h2d, hipEventDisableTiming) == hipSuccess &&
+    ok = ok && dmal(s->d_cand, (size_t)s->cap_cand * 8) && hmal(s->h_cand, (size_t)s->cap_cand * 8) &&
+         dmal(s->d_ncand, 64) && hmal(s->h_ncand, 64) && dmal(s->d_src, R * sizeof(BzxDcSrc)) &&
+         hmal(s->h_src, R * sizeof(BzxDcSrc)) && dmal(s->d_dst, R * sizeof(BzxDcDst)) &&
+         dmal(s->d_chain, R * 4) && dmal(s->d_got, R * 4) && dmal(s->d_rec, sizeof(DsRec)) &&
+         hmal(s->h_rec, sizeof(DsRec)) && hipEventCreateWithFlags(&s->ev_h2d, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&s->ev_carry, hipEventDisableTiming) == hipSuccess &&
          hipStreamCreateWithFlags(&s->s_h2d, hipStreamNonBlocking) == hipSuccess &&
          hipStreamCreateWithFlags(&s->s_d2h, hipStreamNonBlocking) == hipSuccess;
@@ -497,7 +485,7 @@ static int ds_scan(bzx_dstream *s)
             const uint64_t nwords = (to - from + 3) / 4, g = (uint64_t)ctx->n_cu * 8;
             const uint64_t need = (nwords + 255) / 256;
             hipLaunchKernelGGL(bzx_ds_scan_kernel, dim3((uint32_t)(need < g ? need : g)), dim3(256), 0, st, s->wptr, s->wlen,
-                               from, to, s->wbase * 8, s->d_cand, s->d_ncand, s->cap_cand);
+                               from, to, s->wbase * 8, s->d_cand.get(), s->d_ncand.get(), s->cap_cand);
             HIP_TRY(ctx, hipGetLastError());
         }
         HIP_TRY(ctx, hipMemcpyAsync(s->h_ncand, s->d_ncand, 4, hipMemcpyDeviceToHost, st));
@@ -508,7 +496,7 @@ static int ds_scan(bzx_dstream *s)
         to = from + (to - from) / 2;                         // (cap_cand >= 1024 magics of 6 bytes: ends above 6 KiB)
     }
     s->ncand = *s->h_ncand;
-    std::sort(s->h_cand, s->h_cand + s->ncand);
+    std::sort(s->h_cand.get(), s->h_cand + s->ncand);
     if (s->ncand) HIP_TRY(ctx, hipMemcpyAsync(s->d_cand, s->h_cand, (size_t)s->ncand * 8, hipMemcpyHostToDevice, st));
     s->scan_to = to;
     s->ci = 0;
@@ -590,8 +578,8 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
             bzx_launch_dc_decode(B, s->d_src, st);
         }
         hipLaunchKernelGGL(bzx_ds_chain_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8,
-                           s->wfinal ? 1u : 0u, s->d_cand, c0, c1, s->chain_bit, s->comb, s->level, s->d_chain, s->d_rec,
-                           s->d_meta);
+                           s->wfinal ? 1u : 0u, s->d_cand.get(), c0, c1, s->chain_bit, s->comb, s->level, s->d_chain.get(), s->d_rec.get(),
+                           s->d_meta.get());
         if (nb) bzx_launch_dc_ibwt(B, ctx->d_in, st);
     } else {
         B.nblk = s->rd_nb;
@@ -601,15 +589,15 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
     }
     const uint32_t nb = s->rd_nb;
     if (nb) {
-        hipLaunchKernelGGL(bzx_ds_layout_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_stage[q],
-                           (uint64_t)DS_STAGE_BYTES, s->d_dst, s->d_rec);
+        hipLaunchKernelGGL(bzx_ds_layout_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_stage[q].get(),
+                           (uint64_t)DS_STAGE_BYTES, s->d_dst.get(), s->d_rec.get());
         bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
         bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
-        hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_dst, s->d_got, s->d_stage[q],
-                           s->d_rec);
+        hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_dst.get(), s->d_got.get(), s->d_stage[q].get(),
+                           s->d_rec.get());
         if (s->ix) {
-            hipLaunchKernelGGL(bzx_ds_index_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain, s->d_meta, s->wbase * 8, s->d_rec,
-                               s->d_ix);
+            hipLaunchKernelGGL(bzx_ds_index_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_meta.get(), s->wbase * 8, s->d_rec.get(),
+                               s->d_ix.get());
             // (the round's share of the table; the pass wrote its first placed - pass_j0 entries, the host reads
             // r.good <= that many, the rest is what bzx_index_begin zeroed or an earlier pass left)
             HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, nb * sizeof(DsIxRec), hipMemcpyDeviceToHost, st));

@@ -10,6 +10,7 @@
 #include "../../include/bzx.h"
 #include "bzx_dc.h"
 #include "bzx_device.h"
+#include "bzx_mem.h"
 
 struct BlockReq {
     const uint8_t *blk;
@@ -41,23 +42,23 @@ struct bzx_ctx {
     hipEvent_t ev_b3 = nullptr, ev_b4 = nullptr;     // ... around the rank rounds
     hipEvent_t ev_b1 = nullptr, ev_b2 = nullptr;     // bucket sorter: after the split kernel, after the sort kernel
     bool bsort_used = false;
-    uint32_t *h_counters = nullptr;                   // pinned copy of d_counters after a run
+    PinMem<uint32_t> h_counters;                      // pinned copy of d_counters after a run
     std::string err;
 
     uint32_t cap_blocks = 0;   // block descriptor capacity (global block numbers)
     uint32_t cap_slabs = 0;    // per-block slab capacity (owned blocks)
-    std::vector<void *> descs; // everything hipMalloc'ed for cap_blocks
+    std::vector<DevMem<>> descs;   // the device arrays for cap_blocks
     uint32_t n_slots = 0;      // per-workgroup scratch slots
     BzxBatch B;                // device pointers (by value into kernels)
-    std::vector<void *> slabs; // everything hipMalloc'ed for cap_blocks
-    std::vector<void *> slot_allocs;
-    uint8_t *d_in = nullptr;   // block slab buffer owned by the context
-    uint32_t *d_outbuf = nullptr;   // per-block output slabs (per-block entry points)
-    uint32_t *d_counters = nullptr;
-    uint64_t *d_scalars = nullptr;   // [0] total bits, [1] out bytes
-    unsigned long long *d_dbg = nullptr;   // [64] phase timers, only when bzx_dbg_phase_timers(ctx, 1)
-    BzxBlock *h_blk = nullptr;       // pinned mirror
-    uint64_t *h_scalars = nullptr;   // pinned
+    std::vector<DevMem<>> slabs;   // the device arrays for cap_slabs
+    std::vector<DevMem<>> slot_allocs;
+    uint8_t *d_in = nullptr;   // block slab buffer (one of slabs)
+    uint32_t *d_outbuf = nullptr;   // per-block output slabs (per-block entry points; one of slabs)
+    DevMem<uint32_t> d_counters;
+    DevMem<uint64_t> d_scalars;      // [0] total bits, [1] out bytes
+    DevMem<unsigned long long> d_dbg;   // [128] phase timers, only when bzx_dbg_phase_timers(ctx, 1)
+    PinMem<BzxBlock> h_blk;          // pinned mirror of the descriptors, cap_blocks of them
+    PinMem<uint64_t> h_scalars;
     hipEvent_t ev[8];
     bzx_stats stats;
 
@@ -72,30 +73,24 @@ struct bzx_ctx {
     struct bzx_dstream *ds = nullptr;        // open streaming decompressor (bzx_dstream_begin .. _end): it owns the slabs
 
     // device split scratch (bzx_rle1.hip)
-    void *split_ws = nullptr;
-    size_t split_ws_bytes = 0;
+    DevMem<> split_ws;
 
     // batched compression (bzx_compress_batch_*): tables and scratch of the batched splitter and layout
-    void *batch_ws = nullptr;
-    size_t batch_ws_bytes = 0;
+    DevMem<> batch_ws;
     hipEvent_t ev_bt[3] = {nullptr, nullptr, nullptr};   // round: before its split part, before emit, after framing
     bool stats_batch = false;        // the stats describe a batch call or a decompression: no per-block figures
                                      // (bzx_get_block_info)
 
     // batched decompression (bzx_decompress_batch_*): device tables and pinned host mirrors, grown on demand
-    void *dbatch_ws = nullptr;
-    size_t dbatch_ws_bytes = 0;
-    void *dbatch_pin[2] = {nullptr, nullptr};   // [0] candidates and round tables, [1] the _buffer form's bounce buffer
-    size_t dbatch_pin_bytes[2] = {0, 0};
+    DevMem<> dbatch_ws;
+    PinMem<> dbatch_pin[2];                     // [0] candidates and round tables, [1] the _buffer form's bounce buffer
 
     // range reads (bzx_decompress_range_*, _ranges_*): the staging pool and the round tables, allocated by the first call
-    void *range_ws = nullptr;
-    void *range_pin = nullptr;
+    DevMem<> range_ws;
+    PinMem<> range_pin;
     uint32_t range_slabs = 0;                   // blocks the round tables hold
-    void *range_io[2] = {nullptr, nullptr};     // the _buffer form's span [0] and output [1] on the device, grown on demand
-    size_t range_io_bytes[2] = {0, 0};
-    void *range_sl = nullptr;                   // the gather kernel's slice table, grown on demand
-    size_t range_sl_cap = 0;                    // ... entries it holds
+    DevMem<> range_io[2];                       // the _buffer form's span [0] and output [1] on the device, grown on demand
+    DevMem<> range_sl;                          // the gather kernel's slice table, grown on demand
 };
 
 #define HIP_TRY(ctx, expr)                                                                       \
@@ -158,17 +153,17 @@ ChunkCaps chunk_caps(size_t max_chunk);
 size_t buffer_chunk(size_t len, int n_cu, size_t chunk_min);
 // What one device holds for a chunk pipeline beside its context.  alloc and free run with that device current.
 struct ChunkLane {
-    uint8_t *d_in[2] = {nullptr, nullptr};
-    uint32_t *d_out[2] = {nullptr, nullptr};
-    uint64_t *d_phase = nullptr;                  // [0] bit phase of the next chunk, [1] bits of the last laid-out chunk
+    DevMem<uint8_t> d_in[2];
+    DevMem<uint32_t> d_out[2];
+    DevMem<uint64_t> d_phase;                     // [0] bit phase of the next chunk, [1] bits of the last laid-out chunk
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_d2h = nullptr;
-    uint64_t *h_info[2] = {nullptr, nullptr};     // pinned: d_phase after the chunk emitted into d_out[slot]
-    BzxBlock *h_blk[2] = {nullptr, nullptr};      // pinned: descriptors of the chunk's blocks (CRCs)
-    uint32_t *h_w0 = nullptr;                     // pinned: first word of a chunk's output (shared with its predecessor)
+    PinMem<uint64_t> h_info[2];                   // d_phase after the chunk emitted into d_out[slot]
+    PinMem<BzxBlock> h_blk[2];                    // descriptors of the chunk's blocks (CRCs)
+    PinMem<uint32_t> h_w0;                        // first word of a chunk's output (shared with its predecessor)
     size_t device_bytes = 0, pinned_bytes = 0;    // what alloc asked for
     bool alloc(size_t in_cap, size_t out_cap, uint32_t blk_cap);      // false: something failed; free() releases the rest
-    void free();                                  // waits for the two copy streams, then releases everything
+    void free();                                  // waits for the two copy streams, then releases the buffers, events and streams
 };
 // Where a finished chunk goes: bit phase of its first word, words it touches, byte offset of the first in `out`.
 struct ChunkPlace { uint64_t phase, nwords; size_t off; };

@@ -73,22 +73,19 @@ extern "C" int bzx_stage_shift_bits(bzx_ctx *ctx, const uint8_t *in, size_t nbyt
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t n_words = (uint32_t)((nbytes + 3) / 4);
     const size_t bytes = (size_t)shift_vecs(n_words) * 16;
-    uint8_t *d_a = nullptr, *d_b = nullptr;
-    if (hipMalloc((void **)&d_a, bytes) != hipSuccess || hipMalloc((void **)&d_b, bytes) != hipSuccess) {
-        if (d_a) (void)hipFree(d_a);
+    DevMem<uint32_t> d_a, d_b;               // (freed on return, behind the synchronisation below)
+    if (!d_a.reserve(bytes) || !d_b.reserve(bytes)) {
         ctx->err = "bzx_stage_shift_bits: device allocation failed";
         return BZX_E_NOMEM;
     }
     hipError_t e = hipMemsetAsync(d_a, 0, bytes, ctx->stream);
     if (e == hipSuccess && nbytes) e = hipMemcpyAsync(d_a, in, nbytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
-        bzx_launch_shift_bits((const uint32_t *)d_a, n_words, p, (uint32_t *)d_b, (uint32_t)ctx->n_cu, ctx->stream);
+        bzx_launch_shift_bits(d_a, n_words, p, d_b, (uint32_t)ctx->n_cu, ctx->stream);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_b, ((size_t)n_words + 1) * 4, hipMemcpyDeviceToHost, ctx->stream);
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
     HIP_TRY(ctx, e);
     HIP_TRY(ctx, e2);
     return BZX_OK;
@@ -109,7 +106,7 @@ struct bzx_mctx {
 
 struct MEntry {
     ChunkLane L;                                  // d_out: the chunk at bit phase 0; d_phase: zeroed before every chunk
-    uint32_t *d_shift = nullptr;                  // ... shifted to its phase in the stream
+    DevMem<uint32_t> d_shift;                     // ... shifted to its phase in the stream
     uint32_t pend_nblk[2] = {0, 0};
     bool timed = false;                           // the stage events of the context belong to a chunk not yet accounted for
 };
@@ -119,7 +116,7 @@ struct bzx_mstream {
     ChunkCaps c = {};                        // (out_cap rounded up to whole vectors of the shift kernel)
     ChunkAcct a;
     MEntry ent[BZX_MAX_DEVICES];
-    uint8_t *h_tail = nullptr;               // pinned: raw bytes of the withheld block
+    PinMem<uint8_t> h_tail;                  // raw bytes of the withheld block
     size_t tail_cap = 0, tail_len = 0;
     uint32_t k_coll = 0;                     // chunks collected (in order; a.k: chunks fed)
 };
@@ -211,9 +208,8 @@ static void mstream_free(bzx_mstream *s)
         (void)hipSetDevice(m->device[e]);
         (void)hipStreamSynchronize(m->ctx[e]->stream);
         E.L.free();
-        if (E.d_shift) (void)hipFree(E.d_shift);
+        E.d_shift.reset();                   // (with its device current; `delete` frees the tail buffer)
     }
-    if (s->h_tail) (void)hipHostFree(s->h_tail);
     delete s;
 }
 
@@ -256,13 +252,13 @@ static int mstream_make(bzx_mctx *m, int level, size_t max_chunk, bzx_mstream **
     // Read by every entry's device: asked for as portable explicitly (as bzx_host_alloc does for the callers' buffers).
     // The runtime's header calls the default flag "the same definition" as the portable one, but that is a comment, not
     // a promise, and a machine with one device cannot show the difference.
-    bool ok = hipHostMalloc((void **)&s->h_tail, s->tail_cap, BZX_HOST_PORTABLE) == hipSuccess;
+    bool ok = s->h_tail.reserve(s->tail_cap, BZX_HOST_PORTABLE);
     uint32_t bad = 0;
     for (uint32_t e = 0; e < m->ndev && ok; e++) {
         MEntry &E = s->ent[e];
         bad = e;
         ok = hipSetDevice(m->device[e]) == hipSuccess && E.L.alloc(s->c.in_cap, s->c.out_cap, s->c.blk_cap) &&
-             hipMalloc((void **)&E.d_shift, s->c.out_cap) == hipSuccess;
+             E.d_shift.reserve(s->c.out_cap);
         m->info.dev[e].device_bytes = ok ? E.L.device_bytes + s->c.out_cap : 0;
         m->info.dev[e].pinned_bytes = ok ? E.L.pinned_bytes + (e == 0 ? s->tail_cap : 0) : 0;      // (the one tail buffer is counted with entry 0)
     }

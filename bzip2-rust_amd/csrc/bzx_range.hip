@@ -89,51 +89,36 @@ static size_t rg_al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static int rg_tables(bzx_ctx *ctx, uint32_t R, RgTables *t)
 {
-    if (R > ctx->range_slabs) {
-        if (ctx->range_ws) (void)hipFree(ctx->range_ws);
-        if (ctx->range_pin) (void)hipHostFree(ctx->range_pin);
-        ctx->range_ws = ctx->range_pin = nullptr;
+    if (R < ctx->range_slabs) R = ctx->range_slabs;          // (the tables are laid out for the blocks they hold)
+    const bool ok = carved(ctx->range_ws, 256, [&](Carver &c) {
+        t->d_src = c.take<BzxDcSrc>(R);
+        t->d_dst = c.take<BzxDcDst>(R);
+        t->d_len = c.take<uint32_t>(R);
+        t->d_got = c.take<uint32_t>(R);                      // (got and flag lie side by side: one memset clears both)
+        t->d_flag = c.take<uint32_t>(R);
+        t->pool = c.take<uint8_t>(RG_POOL_BYTES);
+    }) && carved(ctx->range_pin, 256, [&](Carver &c) {
+        t->h_got = c.take<uint32_t>(R);
+        t->h_flag = c.take<uint32_t>(R);
+    });
+    if (!ok) {
+        ctx->range_ws.reset();
+        ctx->range_pin.reset();
         ctx->range_slabs = 0;
-        const size_t dev = rg_al(R * sizeof(BzxDcSrc)) + rg_al(R * sizeof(BzxDcDst)) + 3 * rg_al((size_t)R * 4) + RG_POOL_BYTES;
-        if (hipMalloc(&ctx->range_ws, dev) != hipSuccess || hipHostMalloc(&ctx->range_pin, 2 * rg_al((size_t)R * 4), 0) != hipSuccess) {
-            if (ctx->range_ws) (void)hipFree(ctx->range_ws);
-            ctx->range_ws = nullptr;
-            ctx->err = "range read: device or pinned allocation failed";
-            return BZX_E_NOMEM;
-        }
-        ctx->range_slabs = R;
+        ctx->err = "range read: device or pinned allocation failed";
+        return BZX_E_NOMEM;
     }
-    R = ctx->range_slabs;
-    uint8_t *q = (uint8_t *)ctx->range_ws;
-    t->d_src = (BzxDcSrc *)q;
-    q += rg_al(R * sizeof(BzxDcSrc));
-    t->d_dst = (BzxDcDst *)q;
-    q += rg_al(R * sizeof(BzxDcDst));
-    t->d_len = (uint32_t *)q;
-    q += rg_al((size_t)R * 4);
-    t->d_got = (uint32_t *)q;                  // (got and flag lie side by side: one copy brings both)
-    q += rg_al((size_t)R * 4);
-    t->d_flag = (uint32_t *)q;
-    q += rg_al((size_t)R * 4);
-    t->pool = q;
-    t->h_got = (uint32_t *)ctx->range_pin;
-    t->h_flag = (uint32_t *)((uint8_t *)ctx->range_pin + rg_al((size_t)R * 4));
+    ctx->range_slabs = R;
     return BZX_OK;
 }
 
 // The _buffer form's device buffer k of at least `bytes` bytes: kept by the context, grown when a call needs more.
 static int rg_io(bzx_ctx *ctx, int k, size_t bytes, void **p)
 {
-    if (bytes > ctx->range_io_bytes[k]) {
-        if (ctx->range_io[k]) (void)hipFree(ctx->range_io[k]);
-        ctx->range_io[k] = nullptr;
-        ctx->range_io_bytes[k] = 0;
-        const size_t want = std::max<size_t>(bytes, (size_t)4 << 20);      // (a 900k block's span and a few MB of output)
-        if (hipMalloc(&ctx->range_io[k], want) != hipSuccess) {
-            ctx->err = k ? "range read: hipMalloc(output) failed" : "range read: hipMalloc(span) failed";
-            return BZX_E_NOMEM;
-        }
-        ctx->range_io_bytes[k] = want;
+    // (at least 4 MiB: a 900k block's span and a few MB of output)
+    if (!ctx->range_io[k].reserve(std::max<size_t>(bytes, (size_t)4 << 20))) {
+        ctx->err = k ? "range read: hipMalloc(output) failed" : "range read: hipMalloc(span) failed";
+        return BZX_E_NOMEM;
     }
     *p = ctx->range_io[k];
     return BZX_OK;
@@ -263,22 +248,17 @@ static void rg_cut(std::vector<RgSlice> &v, const uint8_t *src, uint8_t *dst, ui
 static int rg_gather(bzx_ctx *ctx, const std::vector<RgSlice> &v)
 {
     if (v.empty()) return BZX_OK;
-    if (v.size() > ctx->range_sl_cap) {
-        if (ctx->range_sl) (void)hipFree(ctx->range_sl);
-        ctx->range_sl = nullptr;
-        ctx->range_sl_cap = 0;
-        const size_t cap = std::max<size_t>(v.size() + v.size() / 2, 4096);
-        if (hipMalloc(&ctx->range_sl, cap * sizeof(RgSlice)) != hipSuccess) {
-            ctx->err = "range read: hipMalloc(slice table) failed";
-            return BZX_E_NOMEM;
-        }
-        ctx->range_sl_cap = cap;
+    // (grown to 1.5 times what the call needs, at least 4096 entries)
+    if (v.size() * sizeof(RgSlice) > ctx->range_sl.bytes() &&
+        !ctx->range_sl.reserve(std::max<size_t>(v.size() + v.size() / 2, 4096) * sizeof(RgSlice))) {
+        ctx->err = "range read: hipMalloc(slice table) failed";
+        return BZX_E_NOMEM;
     }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->range_sl, v.data(), v.size() * sizeof(RgSlice), hipMemcpyHostToDevice, ctx->stream));
     const size_t GMAX = (size_t)1 << 30;                     // (a grid holds 2^31 - 1 workgroups)
     for (size_t at = 0; at < v.size(); at += GMAX)
         hipLaunchKernelGGL(bzx_rg_gather_kernel, dim3((uint32_t)std::min(GMAX, v.size() - at)), dim3(RG_NT), 0, ctx->stream,
-                           (const RgSlice *)ctx->range_sl + at);
+                           ctx->range_sl.get<const RgSlice>() + at);
     HIP_TRY(ctx, hipGetLastError());
     return BZX_OK;
 }
@@ -694,13 +674,12 @@ static int stage_gather(bzx_ctx *ctx, const uint8_t *src, size_t src_len, uint32
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // (both buffers start at a 256-byte boundary, so that an offset's low bits are the address's; the source is read in
     // aligned dwords: room for the one that holds its last byte)
-    uint8_t *d_a = nullptr, *d_b = nullptr;
-    if (hipMalloc((void **)&d_a, src_len + 512) != hipSuccess || hipMalloc((void **)&d_b, out_len + 512) != hipSuccess) {
-        if (d_a) (void)hipFree(d_a);
+    DevMem<> d_a, d_b;                           // (freed on return: every path below ends behind a synchronisation)
+    if (!d_a.reserve(src_len + 512) || !d_b.reserve(out_len + 512)) {
         ctx->err = "bzx_stage_gather: device allocation failed";
         return BZX_E_NOMEM;
     }
-    uint8_t *a = (uint8_t *)rg_al((size_t)(uintptr_t)d_a), *b = (uint8_t *)rg_al((size_t)(uintptr_t)d_b);
+    uint8_t *a = (uint8_t *)rg_al((size_t)(uintptr_t)d_a.get()), *b = (uint8_t *)rg_al((size_t)(uintptr_t)d_b.get());
     auto run = [&]() -> int {
         std::vector<RgSlice> sl;
         for (uint32_t i = 0; i < nslices; i++) rg_cut(sl, a + src_offs[i], b + dst_offs[i], lens[i]);
@@ -732,8 +711,6 @@ static int stage_gather(bzx_ctx *ctx, const uint8_t *src, size_t src_len, uint32
         rc = BZX_E_NOMEM;
     }
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
     return rc;
 }
 
@@ -820,12 +797,12 @@ extern "C" int bzx_stage_ibwt(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     BzxBatch &B = ctx->B;
-    uint8_t *d_raw = nullptr;
-    if (hipMalloc((void **)&d_raw, raw_cap + 64) != hipSuccess) {
+    DevMem<> d_raw;                              // (freed on return, behind the synchronisation below)
+    if (!d_raw.reserve(raw_cap + 64)) {
         ctx->err = "bzx_stage_ibwt: hipMalloc(expansion) failed";
         return BZX_E_NOMEM;
     }
-    const BzxDcDst dst{raw_cap ? d_raw : nullptr, raw_cap};
+    const BzxDcDst dst{raw_cap ? d_raw.get() : nullptr, raw_cap};
     IbwtIn in;
     auto run = [&]() -> int {
         int rc;
@@ -846,9 +823,14 @@ extern "C" int bzx_stage_ibwt(bzx_ctx *ctx, const uint8_t *L, size_t n, uint32_t
         if (k && !*status) HIP_TRY(ctx, hipMemcpy(raw_out, d_raw, k, hipMemcpyDeviceToHost));
         return BZX_OK;
     };
-    const int rc = run();
+    int rc;
+    try {
+        rc = run();
+    } catch (const std::bad_alloc &) {             // (nothing may unwind across the C ABI)
+        ctx->err = "out of host memory";
+        rc = BZX_E_NOMEM;
+    }
     (void)hipStreamSynchronize(st);
-    (void)hipFree(d_raw);
     return rc;
 }
 
@@ -861,24 +843,29 @@ extern "C" int bzx_stage_ibwt_time(bzx_ctx *ctx, const uint8_t *L, size_t n, uin
     BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx || !L || !ms_best || n == 0 || n > BZX_MAX_N || orig_ptr >= n || copies == 0 || reps == 0) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IbwtIn in;
-    int rc = ibwt_load(ctx, L, n, orig_ptr, copies, in);
-    if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    const BzxBatch &B = ctx->B;
-    float best = 0.f;
-    for (uint32_t r = 0; r < reps; r++) {
-        if ((rc = ibwt_arm(ctx, in))) return rc;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[5], st));
-        if (wide) bzx_launch_dc_ibwt_wide(B, ctx->d_in, (uint32_t)n, st);
-        else bzx_launch_dc_ibwt(B, ctx->d_in, st);
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[7], st));
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[7]));
-        if (r == 0 || ms < best) best = ms;
+    try {
+        IbwtIn in;
+        int rc = ibwt_load(ctx, L, n, orig_ptr, copies, in);
+        if (rc) return rc;
+        hipStream_t st = ctx->stream;
+        const BzxBatch &B = ctx->B;
+        float best = 0.f;
+        for (uint32_t r = 0; r < reps; r++) {
+            if ((rc = ibwt_arm(ctx, in))) return rc;
+            HIP_TRY(ctx, hipEventRecord(ctx->ev[5], st));
+            if (wide) bzx_launch_dc_ibwt_wide(B, ctx->d_in, (uint32_t)n, st);
+            else bzx_launch_dc_ibwt(B, ctx->d_in, st);
+            HIP_TRY(ctx, hipEventRecord(ctx->ev[7], st));
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            float ms = 0.f;
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[7]));
+            if (r == 0 || ms < best) best = ms;
+        }
+        *ms_best = best;
+        return BZX_OK;
+    } catch (const std::bad_alloc &) {             // (nothing may unwind across the C ABI)
+        ctx->err = "out of host memory";
+        return BZX_E_NOMEM;
     }
-    *ms_best = best;
-    return BZX_OK;
 }

@@ -43,6 +43,7 @@ typedef void *hipStream_t;
 typedef void *hipEvent_t;
 #define hipSuccess 0
 #define hipErrorInvalidValue 1
+#define hipErrorOutOfMemory 2
 #define hipMemcpyHostToDevice 1
 #define hipMemcpyDeviceToHost 2
 #define hipMemcpyDeviceToDevice 3
@@ -132,11 +133,13 @@ template <typename T> inline T atomicMin(T *p, T v) { T o = *p; if (v < o) *p = 
 template <typename T> inline T atomicExch(T *p, T v) { T o = *p; *p = v; return o; }
 template <typename T> inline T atomicCAS(T *p, T c, T v) { T o = *p; if (o == c) *p = v; return o; }
 
-/* ---- host runtime subset: device memory is host memory ---- */
-inline hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
-inline hipError_t hipFree(void *p) { free(p); return 0; }
-inline hipError_t hipHostMalloc(void **p, size_t n, unsigned = 0) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
-inline hipError_t hipHostFree(void *p) { free(p); return 0; }
+/* ---- host runtime subset: device memory is host memory, counted in hip_emu.cpp (the hipemu_* functions there) ---- */
+extern "C" hipError_t hipemu_alloc(void **p, size_t n, int pinned);
+extern "C" hipError_t hipemu_free(void *p, int pinned);
+inline hipError_t hipMalloc(void **p, size_t n) { return hipemu_alloc(p, n, 0); }
+inline hipError_t hipFree(void *p) { return hipemu_free(p, 0); }
+inline hipError_t hipHostMalloc(void **p, size_t n, unsigned = 0) { return hipemu_alloc(p, n, 1); }
+inline hipError_t hipHostFree(void *p) { return hipemu_free(p, 1); }
 inline hipError_t hipMemcpy(void *d, const void *s, size_t n, int) { memmove(d, s, n); return 0; }
 inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, int, hipStream_t = 0) { memmove(d, s, n); return 0; }
 inline hipError_t hipMemset(void *d, int v, size_t n) { memset(d, v, n); return 0; }

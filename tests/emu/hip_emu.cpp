@@ -4,6 +4,32 @@
 uint3_emu threadIdx, blockIdx;
 dim3 blockDim, gridDim;
 
+/* Allocation bookkeeping for tests/test_emu_mem.py: live[0] device and live[1] pinned allocations, the allocations made
+   so far, and a one-shot switch that fails the k-th allocation from now (k = 0: the next one) and then disarms. */
+static long mem_live[2], mem_total, mem_fail_in = -1;
+
+extern "C" hipError_t hipemu_alloc(void **p, size_t n, int pinned)
+{
+    *p = nullptr;
+    mem_total++;
+    if (mem_fail_in >= 0 && mem_fail_in-- == 0) return hipErrorOutOfMemory;
+    *p = malloc(n ? n : 1);
+    if (!*p) return hipErrorOutOfMemory;
+    mem_live[pinned]++;
+    return hipSuccess;
+}
+
+extern "C" hipError_t hipemu_free(void *p, int pinned)
+{
+    if (p) mem_live[pinned]--;
+    free(p);
+    return hipSuccess;
+}
+
+extern "C" long hipemu_mem_live(int pinned) { return mem_live[pinned]; }
+extern "C" long hipemu_mem_total(void) { return mem_total; }
+extern "C" void hipemu_mem_fail_after(long k) { mem_fail_in = k; }      /* k < 0: disarmed */
+
 namespace hipemu {
 
 struct Fiber {
