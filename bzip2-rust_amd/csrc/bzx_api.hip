@@ -216,13 +216,8 @@ extern "C" int bzx_get_stats(const bzx_ctx *ctx, bzx_stats *out)
     return BZX_OK;
 }
 
-extern "C" int bzx_get_block_info(const bzx_ctx *ctx, uint32_t block, bzx_block_info *out)
+static void block_info_of(const BzxBlock &d, bzx_block_info *out)
 {
-    if (!ctx || !out) return BZX_E_PARAM;
-    std::unique_lock<std::recursive_mutex> api_lock_(const_cast<bzx_ctx *>(ctx)->api_mu);
-    if (ctx->stats_batch) return BZX_E_STATE;
-    if (!ctx->h_blk || block >= ctx->stats.nblk || block >= ctx->cap_blocks) return BZX_E_PARAM;
-    const BzxBlock &d = ctx->h_blk[block];
     out->n = d.n;
     out->crc = d.crc;
     out->orig_ptr = d.orig_ptr;
@@ -236,6 +231,15 @@ extern "C" int bzx_get_block_info(const bzx_ctx *ctx, uint32_t block, bzx_block_
     out->bits_payload = d.sec_bits[2];
     out->bits_symbol_map = d.sec_bits[3];
     out->bits = d.bits;
+}
+
+extern "C" int bzx_get_block_info(const bzx_ctx *ctx, uint32_t block, bzx_block_info *out)
+{
+    if (!ctx || !out) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(const_cast<bzx_ctx *>(ctx)->api_mu);
+    if (ctx->stats_batch) return BZX_E_STATE;
+    if (!ctx->h_blk || block >= ctx->stats.nblk || block >= ctx->cap_blocks) return BZX_E_PARAM;
+    block_info_of(ctx->h_blk[block], out);
     return BZX_OK;
 }
 
@@ -548,6 +552,68 @@ extern "C" int bzx_stage_huffman(bzx_ctx *ctx, const uint16_t *mtfv, uint32_t n_
             len_out[t][v] = hl[t * 260 + v];
             code_out[t][v] = hc[t * 260 + v];
         }
+    return BZX_OK;
+}
+
+// Huffman stage, then emit stage, of one block whose descriptor and symbol slabs the host fills (the MTF stage's part
+// of the descriptor: n, n_mtf, n_in_use; the BWT's orig_ptr; the splitter's crc).  The emit stage runs only once the
+// Huffman stage's size of the image is known to fit the block's output slab.
+extern "C" int bzx_stage_encode(bzx_ctx *ctx, const uint16_t *mtfv, uint32_t n_mtf, const uint32_t freq[258],
+                                const uint8_t in_use[256], uint32_t orig_ptr, uint32_t crc, uint8_t *out, size_t cap,
+                                size_t *out_len, uint8_t *pad_bits, uint8_t *selector_mtf, bzx_block_info *info)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
+    if (!ctx || !mtfv || !freq || !in_use || !out || !out_len || !pad_bits || !selector_mtf || !info) return BZX_E_PARAM;
+    uint32_t alpha_size = 2;
+    uint8_t iu[256];
+    for (int i = 0; i < 256; i++) alpha_size += (iu[i] = in_use[i] ? 1 : 0);
+    if (n_mtf == 0 || n_mtf > BZX_MAX_BLOCK + 1 || alpha_size < 3 || alpha_size > BZX_MAX_ALPHA || orig_ptr > 0xffffffu)
+        return BZX_E_PARAM;
+    for (uint32_t i = 0; i < n_mtf; i++)
+        if (mtfv[i] >= alpha_size) {
+            ctx->err = "bzx_stage_encode: symbol outside the alphabet";
+            return BZX_E_PARAM;
+        }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_blocks(ctx, 1);
+    if (rc) return rc;
+    memset(&ctx->h_blk[0], 0, sizeof(BzxBlock));
+    ctx->h_blk[0].n = n_mtf - 1;
+    ctx->h_blk[0].n_mtf = n_mtf;
+    ctx->h_blk[0].n_in_use = alpha_size - 2;
+    ctx->h_blk[0].orig_ptr = orig_ptr;
+    ctx->h_blk[0].crc = crc;
+    uint32_t f260[260];
+    memset(f260, 0, sizeof(f260));
+    memcpy(f260, freq, 258 * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemcpy(ctx->B.mtfv, mtfv, (size_t)n_mtf * 2, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->B.freq, f260, sizeof(f260), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->B.in_use, iu, 256, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->B.blk, ctx->h_blk, sizeof(BzxBlock), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run_stages(ctx, 1, STG_HUF))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, ctx->B.blk, sizeof(BzxBlock), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const BzxBlock &d = ctx->h_blk[0];
+    if (d.n_selectors != (n_mtf + BZX_G_SIZE - 1) / BZX_G_SIZE || d.n_groups < 2 || d.n_groups > 6) {
+        ctx->err = "device Huffman stage produced an impossible selector or table count";
+        return BZX_E_HIP;
+    }
+    const uint64_t sum = 105ull + d.sec_bits[3] + 18 + d.sec_bits[0] + d.sec_bits[1] + d.sec_bits[2];
+    if (d.bits != sum || d.bits > (uint64_t)BZX_OUT_STRIDE * 8) {
+        ctx->err = d.bits != sum ? "device Huffman stage produced section sizes that do not add up"
+                                 : "bzx_stage_encode: the image of this symbol stream is larger than a block's output slab";
+        return d.bits != sum ? BZX_E_HIP : BZX_E_PARAM;
+    }
+    if ((rc = run_stages(ctx, 1, STG_EMIT, 0))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    block_info_of(d, info);
+    HIP_TRY(ctx, hipMemcpy(selector_mtf, ctx->B.selector_mtf, d.n_selectors, hipMemcpyDeviceToHost));
+    const size_t bytes = (size_t)((d.bits + 7) >> 3);
+    *out_len = bytes;
+    if (bytes > cap) return BZX_E_OUTBUF;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_outbuf, bytes, hipMemcpyDeviceToHost));
+    *pad_bits = (uint8_t)((8 - (d.bits & 7)) & 7);
     return BZX_OK;
 }
 

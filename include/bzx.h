@@ -81,6 +81,7 @@ int bzx_compress_blocks(bzx_ctx *ctx, uint32_t nblk, const uint8_t *const *blks,
  *   bzx_stage_bwt       bwt_encode            src/bwt_algorithms/bwt_sort.rs:27
  *   bzx_stage_mtf       rle2_mtf_encode       src/tools/rle2_mtf.rs:23
  *   bzx_stage_huffman   huf_encode tables     src/huffman_coding/huffman.rs:87-374
+ *   bzx_stage_encode    huf_encode, all of it (tables + bits) behind the block header, for a given symbol stream
  */
 int bzx_stage_bwt(bzx_ctx *ctx, const uint8_t *blk, size_t n, uint8_t *bwt_out, uint32_t *orig_ptr,
                   uint32_t *status);
@@ -89,6 +90,19 @@ int bzx_stage_mtf(bzx_ctx *ctx, const uint8_t *bwt, size_t n, uint16_t *mtfv_out
 int bzx_stage_huffman(bzx_ctx *ctx, const uint16_t *mtfv, uint32_t n_mtf, const uint32_t freq[258],
                       uint32_t alpha_size, uint32_t *n_groups, uint32_t *n_selectors, uint8_t *selectors,
                       uint8_t len_out[6][258], uint32_t code_out[6][258]);
+/*
+ * Test/diagnostic: the Huffman stage and the emit stage of ONE block over a symbol stream the caller supplies (mtfv ends
+ * with EOB = alphabet - 1, every symbol is below the alphabet size, freq counts the symbols of mtfv; the alphabet is
+ * the number of non-zero in_use entries + 2).  out/out_len/pad_bits: the byte-aligned block image as bzx_compress_block
+ * gives it; selector_mtf: info->n_selectors entries (room for 18002); info: n = n_mtf - 1, periodic = 0, the section
+ * sizes and the total as bzx_get_block_info reports them.  BZX_E_PARAM as bzx_stage_huffman, also for a symbol outside
+ * the alphabet, orig_ptr >= 2^24 or a stream whose image would not fit a block's output slab (no block of real data
+ * gets there); BZX_E_OUTBUF with *out_len = bytes needed when cap is too small.
+ */
+struct bzx_block_info;
+int bzx_stage_encode(bzx_ctx *ctx, const uint16_t *mtfv, uint32_t n_mtf, const uint32_t freq[258],
+                     const uint8_t in_use[256], uint32_t orig_ptr, uint32_t crc, uint8_t *out, size_t cap,
+                     size_t *out_len, uint8_t *pad_bits, uint8_t *selector_mtf, struct bzx_block_info *info);
 
 /*
  * RLE1 + block split + per-block CRC (replaces RLE1Block, rle1.rs:33-263, and do_crc,

@@ -132,6 +132,21 @@ typedef struct {
 int bzo_compress_block_info(const uint8_t *blk, size_t n, uint32_t crc, uint8_t *out, size_t cap,
                             size_t *out_len, uint8_t *pad_bits, bzo_block_info *info);
 
+/*
+ * The part of compress_block behind the MTF step, for a given symbol stream: table optimisation and the whole block
+ * image.  mtfv ends with EOB; the alphabet is the number of set in_use entries + 2.  selector_mtf (optional) gets
+ * n_selectors entries; the section sizes are in bits (bits_selectors without the 3 + 15 bits in front of them),
+ * bits = header .. last payload bit.  Returns 0, or -1 if cap is too small / n_mtf or the alphabet out of range.
+ */
+typedef struct {
+    int32_t n_in_use, n_groups, n_selectors;
+    uint32_t bits_symbol_map, bits_selectors, bits_tables, bits_payload;
+    uint64_t bits;
+} bzo_encode_info;
+int bzo_encode_block(const uint16_t *mtfv, int32_t n_mtf, const int32_t mtf_freq[BZO_MAX_ALPHA],
+                     const uint8_t in_use[256], uint32_t orig_ptr, uint32_t crc, uint8_t *out, size_t cap,
+                     size_t *out_len, uint8_t *pad_bits, uint8_t *selector_mtf, bzo_encode_info *info);
+
 /* ---- stream assembler (bitwriter.rs:42-172) ---- */
 typedef struct {
     uint8_t *out;

@@ -432,39 +432,41 @@ int bzo_bp_flush(bzo_bitpacker *bp)
 
 /* ------------------------------------------------------------------ compress_block (compress_block.rs:24-67) */
 
-int bzo_compress_block_info(const uint8_t *blk, size_t n, uint32_t crc, uint8_t *out, size_t cap,
-                            size_t *out_len, uint8_t *pad_bits, bzo_block_info *info)
+/* Everything of compress_block behind the MTF step: table optimisation and the bits of the block image. */
+int bzo_encode_block(const uint16_t *mtfv, int32_t n_mtf, const int32_t mtf_freq[BZO_MAX_ALPHA],
+                     const uint8_t in_use[256], uint32_t orig_ptr, uint32_t crc, uint8_t *out, size_t cap,
+                     size_t *out_len, uint8_t *pad_bits, uint8_t *selector_mtf, bzo_encode_info *info)
 {
-    if (n == 0 || n > 900000) return -1;
-    uint8_t *bwt = (uint8_t *)malloc(n);
-    uint16_t *mtfv = (uint16_t *)malloc(sizeof(uint16_t) * (n + 2));
+    int32_t n_in_use = 0, i, t;
+    for (i = 0; i < 256; i++) n_in_use += in_use[i] ? 1 : 0;
+    const int32_t alpha = n_in_use + 2;
+    if (n_mtf <= 0 || n_mtf > 900001 || alpha < 3) return -1;
     bzo_huff_tables *T = (bzo_huff_tables *)malloc(sizeof(bzo_huff_tables));
-    int32_t mtf_freq[BZO_MAX_ALPHA], n_in_use, n_mtf, orig, i, t;
-    uint8_t in_use[256];
     uint16_t map[17];
     bzo_bitpacker bp;
+    uint64_t at[5];
 
     bzo_bp_init(&bp, out, cap);
     bzo_bp_out24(&bp, 0x18314159u);
     bzo_bp_out24(&bp, 0x18265359u);
     bzo_bp_out32(&bp, crc);
     bzo_bp_out24(&bp, 0x01000000u);
+    bzo_bp_out24(&bp, 0x18000000u | orig_ptr);
 
-    orig = bzo_bwt(blk, (int32_t)n, bwt, NULL);
-    bzo_bp_out24(&bp, 0x18000000u | (uint32_t)orig);
-
-    n_mtf = bzo_mtf_rle2(bwt, (int32_t)n, mtfv, mtf_freq, in_use, &n_in_use);
-    int32_t alpha = n_in_use + 2;
     bzo_huff_optimise(mtfv, n_mtf, mtf_freq, alpha, T);
 
+#define BP_BITS() ((uint64_t)bp.len * 8 + (uint64_t)bp.q_bits)
+    at[0] = BP_BITS();
     int nmap = bzo_symbol_map(in_use, map);
     for (i = 0; i < nmap; i++) bzo_bp_out16(&bp, map[i]);
+    at[1] = BP_BITS();
     bzo_bp_put(&bp, 3, (uint32_t)T->n_groups);
     bzo_bp_put(&bp, 15, (uint32_t)T->n_selectors);
     for (i = 0; i < T->n_selectors; i++) {
         for (int j = 0; j < T->selector_mtf[i]; j++) bzo_bp_put(&bp, 1, 1);
         bzo_bp_put(&bp, 1, 0);
     }
+    at[2] = BP_BITS();
     for (t = 0; t < T->n_groups; t++) {
         int32_t curr = T->len[t][0];
         bzo_bp_put(&bp, 5, (uint32_t)curr);
@@ -474,6 +476,7 @@ int bzo_compress_block_info(const uint8_t *blk, size_t n, uint32_t crc, uint8_t 
             bzo_bp_put(&bp, 1, 0);
         }
     }
+    at[3] = BP_BITS();
     {
         int32_t sel = 0, gs = 0, ge;
         while (gs < n_mtf) {
@@ -486,25 +489,54 @@ int bzo_compress_block_info(const uint8_t *blk, size_t n, uint32_t crc, uint8_t 
             sel++;
         }
     }
-    uint64_t bits = (uint64_t)bp.len * 8 + (uint64_t)bp.q_bits;
+    at[4] = BP_BITS();
+#undef BP_BITS
     int pad = bzo_bp_flush(&bp);
+    if (selector_mtf) memcpy(selector_mtf, T->selector_mtf, (size_t)T->n_selectors);
     if (info) {
-        info->nblock = (int32_t)n;
-        info->orig_ptr = orig;
-        info->n_mtf = n_mtf;
         info->n_in_use = n_in_use;
         info->n_groups = T->n_groups;
         info->n_selectors = T->n_selectors;
-        info->crc = crc;
-        info->bits = bits;
+        info->bits_symbol_map = (uint32_t)(at[1] - at[0]);
+        info->bits_selectors = (uint32_t)(at[2] - at[1] - 18);
+        info->bits_tables = (uint32_t)(at[3] - at[2]);
+        info->bits_payload = (uint32_t)(at[4] - at[3]);
+        info->bits = at[4];
     }
-    free(bwt);
-    free(mtfv);
     free(T);
     if (bp.overflow) return -1;
     *out_len = bp.len;
     *pad_bits = (uint8_t)pad;
     return 0;
+}
+
+int bzo_compress_block_info(const uint8_t *blk, size_t n, uint32_t crc, uint8_t *out, size_t cap,
+                            size_t *out_len, uint8_t *pad_bits, bzo_block_info *info)
+{
+    if (n == 0 || n > 900000) return -1;
+    uint8_t *bwt = (uint8_t *)malloc(n);
+    uint16_t *mtfv = (uint16_t *)malloc(sizeof(uint16_t) * (n + 2));
+    int32_t mtf_freq[BZO_MAX_ALPHA], n_in_use, n_mtf, orig;
+    uint8_t in_use[256];
+    bzo_encode_info ei;
+    memset(&ei, 0, sizeof(ei));
+
+    orig = bzo_bwt(blk, (int32_t)n, bwt, NULL);
+    n_mtf = bzo_mtf_rle2(bwt, (int32_t)n, mtfv, mtf_freq, in_use, &n_in_use);
+    int rc = bzo_encode_block(mtfv, n_mtf, mtf_freq, in_use, (uint32_t)orig, crc, out, cap, out_len, pad_bits, NULL, &ei);
+    if (info) {
+        info->nblock = (int32_t)n;
+        info->orig_ptr = orig;
+        info->n_mtf = n_mtf;
+        info->n_in_use = n_in_use;
+        info->n_groups = ei.n_groups;
+        info->n_selectors = ei.n_selectors;
+        info->crc = crc;
+        info->bits = ei.bits;
+    }
+    free(bwt);
+    free(mtfv);
+    return rc;
 }
 
 int bzo_compress_block(const uint8_t *blk, size_t n, uint32_t crc, uint8_t *out, size_t cap, size_t *out_len,

@@ -106,7 +106,7 @@ class BzxLib:
 
     def stage_huffman(self, mtfv, freq, alpha):
         n_mtf = len(mtfv)
-        arr = (C.c_uint16 * n_mtf)(*mtfv)
+        arr = (C.c_uint16 * n_mtf).from_buffer_copy(_u16(mtfv))
         f = (C.c_uint32 * 258)(*freq)
         ng = C.c_uint32()
         ns = C.c_uint32()
@@ -117,6 +117,27 @@ class BzxLib:
         lens = [list(ln[t * 258:t * 258 + alpha]) for t in range(ng.value)]
         codes = [list(code[t * 258:t * 258 + alpha]) for t in range(ng.value)]
         return ng.value, list(sel[:ns.value]), lens, codes
+
+    def stage_encode(self, mtfv, freq, in_use: bytes, orig_ptr=0, crc=0):
+        """bzx_stage_encode -> (image, pad_bits, selector_mtf, (n_tables, n_selectors, map, selector, table, payload
+        bits, total bits)), the tuple Oracle.encode_block returns."""
+        n_mtf = len(mtfv)
+        arr = (C.c_uint16 * n_mtf).from_buffer_copy(_u16(mtfv))
+        f = (C.c_uint32 * 258)(*freq)
+        cap = 921600
+        out = C.create_string_buffer(cap)
+        ol, pad = C.c_size_t(), C.c_uint8()
+        selm = (C.c_uint8 * 18002)()
+        bi = BzxBlockInfo()
+        self.lib.bzx_stage_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32,
+                                              C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                              C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(BzxBlockInfo)]
+        self._check(self.lib.bzx_stage_encode(self.ctx, arr, n_mtf, f, bytes(in_use), orig_ptr, crc, out, cap,
+                                              C.byref(ol), C.byref(pad), selm, C.byref(bi)))
+        assert (bi.n, bi.n_mtf, bi.crc, bi.orig_ptr, bi.periodic) == (n_mtf - 1, n_mtf, crc, orig_ptr, 0)
+        assert bi.n_in_use == sum(1 for b in in_use if b)
+        return out.raw[:ol.value], pad.value, bytes(selm[:bi.n_selectors]), (
+            bi.n_tables, bi.n_selectors, bi.bits_symbol_map, bi.bits_selectors, bi.bits_tables, bi.bits_payload, bi.bits)
 
     def compress_blocks(self, blocks, crcs):
         """blocks: list of bytes (RLE1'd), crcs: list of int -> list of (image bytes, pad_bits)."""
@@ -263,6 +284,19 @@ class CStream:
             self.h = C.c_void_p()
 
 
+def _u16(values):
+    """A symbol list as the bytes of a uint16 array (a ctypes array built from a million arguments takes a second)."""
+    import array
+    a = values if isinstance(values, array.array) and values.typecode == "H" else array.array("H", values)
+    return a.tobytes()
+
+
+class OracleEncodeInfo(C.Structure):
+    _fields_ = [("n_in_use", C.c_int32), ("n_groups", C.c_int32), ("n_selectors", C.c_int32),
+                ("bits_symbol_map", C.c_uint32), ("bits_selectors", C.c_uint32), ("bits_tables", C.c_uint32),
+                ("bits_payload", C.c_uint32), ("bits", C.c_uint64)]
+
+
 class OracleHuff(C.Structure):
     _fields_ = [("n_groups", C.c_int32), ("n_selectors", C.c_int32), ("selector", C.c_uint8 * 18002),
                 ("selector_mtf", C.c_uint8 * 18002), ("len", (C.c_uint8 * 258) * 6), ("code", (C.c_int32 * 258) * 6)]
@@ -291,12 +325,49 @@ class Oracle:
 
     def huff(self, mtfv, freq, alpha):
         T = OracleHuff()
-        arr = (C.c_uint16 * len(mtfv))(*mtfv)
+        arr = (C.c_uint16 * len(mtfv)).from_buffer_copy(_u16(mtfv))
         f = (C.c_int32 * 258)(*freq)
         self.lib.bzo_huff_optimise(arr, len(mtfv), f, alpha, C.byref(T))
         lens = [list(T.len[t][:alpha]) for t in range(T.n_groups)]
         codes = [list(T.code[t][:alpha]) for t in range(T.n_groups)]
         return T.n_groups, list(T.selector[:T.n_selectors]), lens, codes
+
+    def huff_full(self, mtfv, freq, alpha):
+        """bzo_huff_optimise -> the whole table structure (selector_mtf included)."""
+        T = OracleHuff()
+        arr = (C.c_uint16 * len(mtfv)).from_buffer_copy(_u16(mtfv))
+        f = (C.c_int32 * 258)(*freq)
+        self.lib.bzo_huff_optimise(arr, len(mtfv), f, alpha, C.byref(T))
+        return T
+
+    def make_code_lengths(self, freq, alpha, max_len=17):
+        """bzo_make_code_lengths (libbz2's hbMakeCodeLengths) -> the alpha code lengths."""
+        ln = (C.c_uint8 * 258)()
+        f = (C.c_int32 * 258)(*(list(freq) + [0] * (258 - len(freq))))
+        self.lib.bzo_make_code_lengths.restype = None
+        self.lib.bzo_make_code_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+        self.lib.bzo_make_code_lengths(ln, f, alpha, max_len)
+        return list(ln[:alpha])
+
+    def encode_block(self, mtfv, freq, in_use: bytes, orig_ptr=0, crc=0):
+        """bzo_encode_block -> the tuple BzxLib.stage_encode returns."""
+        n_mtf = len(mtfv)
+        arr = (C.c_uint16 * n_mtf).from_buffer_copy(_u16(mtfv))
+        f = (C.c_int32 * 258)(*freq)
+        cap = 2 * n_mtf * 17 // 8 + 4096
+        out = C.create_string_buffer(cap)
+        ol, pad = C.c_size_t(), C.c_uint8()
+        selm = (C.c_uint8 * 18002)()
+        ei = OracleEncodeInfo()
+        self.lib.bzo_encode_block.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32,
+                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint8),
+                                              C.c_void_p, C.POINTER(OracleEncodeInfo)]
+        rc = self.lib.bzo_encode_block(arr, n_mtf, f, bytes(in_use), orig_ptr, crc, out, cap, C.byref(ol), C.byref(pad),
+                                       selm, C.byref(ei))
+        assert rc == 0
+        assert ei.n_in_use == sum(1 for b in in_use if b)
+        return out.raw[:ol.value], pad.value, bytes(selm[:ei.n_selectors]), (
+            ei.n_groups, ei.n_selectors, ei.bits_symbol_map, ei.bits_selectors, ei.bits_tables, ei.bits_payload, ei.bits)
 
     def split_rle1(self, data: bytes, level=9):
         self.lib.bzo_rle1_block.restype = C.c_size_t
