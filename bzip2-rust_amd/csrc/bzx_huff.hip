@@ -11,8 +11,9 @@
 //
 // Parallel shape: one workgroup per block; one lane per 50-symbol group (<= 18002 groups);
 // six 10-bit code-length fields packed in two LDS words per symbol so a group cost is 50 x 2
-// LDS reads; rfreq in LDS atomics.  Also produces every section size so the emitter and the
-// stream layout know all bit offsets.
+// LDS reads; rfreq of the low symbols (RUNA, RUNB and the first ranks: most of a text block) counted per group in
+// packed register fields and added with three 64-bit LDS atomics per group, LDS atomics per occurrence only for the
+// symbols above them.  Also produces every section size so the emitter and the stream layout know all bit offsets.
 #include <hip/hip_runtime.h>
 #include "bzx_host.h"
 #include "bzx_wg.h"
@@ -25,6 +26,14 @@ __shared__ uint8_t h_len[6][BZX_MAX_ALPHA + 2];
 // per symbol, ONE 8-byte word: low half len0 | len1<<10 | len2<<20, high half len3 | len4<<10 | len5<<20
 __shared__ uint2 h_lenAB[BZX_MAX_ALPHA + 2];
 __shared__ uint32_t h_rfreq[6][BZX_MAX_ALPHA + 2];
+// Frequencies of the symbols below HUF_PK (the packed range), per table: three 21-bit fields per word (a table holds at
+// most 900,001 symbols, so a field never carries into its neighbour), HUF_PK_COPIES copies that the lanes of a wave
+// spread over (same-address LDS atomics retire one lane per clock); a copy is 18 words in a
+// stride of 19, odd, so that the copies start on different banks.
+#define HUF_PK 9
+#define HUF_PK_COPIES 8
+#define HUF_PK_STRIDE 19
+__shared__ unsigned long long h_pk[HUF_PK_COPIES * HUF_PK_STRIDE];
 __shared__ __attribute__((aligned(16))) uint64_t h_heap[6][BZX_MAX_ALPHA + 2];     // [weight:32 | node:32]
 __shared__ int32_t h_weight[6][BZX_MAX_ALPHA + 2];                                  // leaves
 __shared__ int32_t h_parent[6][BZX_MAX_ALPHA * 2];
@@ -126,6 +135,33 @@ __device__ void make_code_lengths(int t, int32_t alpha, int32_t max_len)
     }
 }
 
+// The 50 symbols of a group, two per word.  The last group of a block may be short: the places behind its end take the
+// symbol HUF_NULL, which costs nothing under every table (h_lenAB) and counts into a row entry nothing reads, so the
+// loops over a group need no test of their own per symbol.  (The loads stay inside the block's slab of V.)
+#define HUF_NULL (BZX_MAX_ALPHA + 1)
+static_assert(BZX_MAX_N + 1 + BZX_G_SIZE <= BZX_BLK_STRIDE, "a whole last group is read");
+__device__ __forceinline__ void huff_load_group(const uint16_t *__restrict__ v, uint32_t cnt, uint32_t (&sy)[BZX_G_SIZE / 2])
+{
+    const uint32_t *__restrict__ vp = reinterpret_cast<const uint32_t *>(v);
+#pragma unroll
+    for (int k = 0; k < BZX_G_SIZE / 2; k++) sy[k] = vp[k];
+    if (cnt < BZX_G_SIZE) {
+#pragma unroll
+        for (int k = 0; k < BZX_G_SIZE; k++)
+            if ((uint32_t)k >= cnt)
+                sy[k >> 1] = (k & 1) ? (sy[k >> 1] & 0xffffu) | ((uint32_t)HUF_NULL << 16) : (sy[k >> 1] & 0xffff0000u) | (uint32_t)HUF_NULL;
+    }
+}
+
+// Makes the compiler forget what it knows about a register: the second loop over a group takes its symbols out of
+// the packed words again instead of keeping the first loop's fifty extracted symbols alive (they do not fit the
+// registers of six waves per SIMD, and spilled).
+#ifdef BZX_HIP_EMU
+#define HUF_FORGET(x) do {} while (0)
+#else
+#define HUF_FORGET(x) asm volatile("" : "+v"(x))
+#endif
+
 #define HUF_STAMP(slot)                                                       \
     do {                                                                      \
         if (B.dbg && tid == 0) {                                              \
@@ -146,14 +182,16 @@ __global__ __launch_bounds__(HUF_NT) __attribute__((amdgpu_waves_per_eu(HUF_WAVE
     for (;;) {
         if (tid == 0) h_bcast[0] = atomicAdd(&B.counters[2], 1u);
         __syncthreads();
-        const uint32_t j_ = h_bcast[0];
+        // (the block number and what follows from it -- sizes, slab pointers -- are the same in every lane: said so, the
+        // compiler may keep them in scalar registers and leave the vector ones to the group loops)
+        const uint32_t j_ = bzx_uni(h_bcast[0]);
         __syncthreads();
         if (j_ >= B.nblk) break;
         const uint32_t b = B.blk_first + j_ * B.blk_step;
 
         if (B.dbg && tid == 0) t_last = wall_clock64();
-        const uint32_t n_mtf = B.blk[b].n_mtf;
-        const uint32_t alpha = B.blk[b].n_in_use + 2;
+        const uint32_t n_mtf = bzx_uni(B.blk[b].n_mtf);
+        const uint32_t alpha = bzx_uni(B.blk[b].n_in_use) + 2;
         const uint16_t *__restrict__ V = B.mtfv + BZX_SLAB(B, b) * BZX_BLK_STRIDE;
         uint8_t *__restrict__ SEL = B.selector + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
         uint8_t *__restrict__ SELM = B.selector_mtf + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
@@ -199,27 +237,30 @@ __global__ __launch_bounds__(HUF_NT) __attribute__((amdgpu_waves_per_eu(HUF_WAVE
         // ---- four refinement passes
         for (int iter = 0; iter < BZX_N_ITERS; iter++) {
             for (uint32_t i = tid; i < 6 * (BZX_MAX_ALPHA + 2); i += HUF_NT) (&h_rfreq[0][0])[i] = 0;
+            if (tid < HUF_PK_COPIES * HUF_PK_STRIDE) h_pk[tid] = 0;
             for (uint32_t v = tid; v < BZX_MAX_ALPHA + 2; v += HUF_NT) {
                 h_lenAB[v] = make_uint2((uint32_t)h_len[0][v] | ((uint32_t)h_len[1][v] << 10) | ((uint32_t)h_len[2][v] << 20),
                                         (uint32_t)h_len[3][v] | ((uint32_t)h_len[4][v] << 10) | ((uint32_t)h_len[5][v] << 20));
+                if (v == HUF_NULL) h_lenAB[v] = make_uint2(0u, 0u);
             }
             __syncthreads();
             for (uint32_t g = tid; g < n_sel; g += HUF_NT) {
                 const uint32_t gs = g * BZX_G_SIZE;
                 const uint32_t cnt = (n_mtf - gs < BZX_G_SIZE) ? n_mtf - gs : BZX_G_SIZE;
-                const uint32_t *__restrict__ vp = reinterpret_cast<const uint32_t *>(V + gs);
                 uint32_t sy[BZX_G_SIZE / 2];
-#pragma unroll
-                for (int k = 0; k < BZX_G_SIZE / 2; k++) sy[k] = vp[k];
+                huff_load_group(V + gs, cnt, sy);
                 uint32_t accA = 0, accB = 0;
+                // occurrences of the symbols 0 .. HUF_PK-1 in the group, ten 6-bit fields (a count is at most 50); every
+                // symbol above them counts into field HUF_PK, which nothing reads
+                uint64_t low = 0;
+                static_assert(BZX_G_SIZE < 64 && 6 * (HUF_PK + 1) <= 64 && HUF_PK % 3 == 0, "packed group counts");
 #pragma unroll
                 for (int k = 0; k < BZX_G_SIZE; k++) {
-                    if ((uint32_t)k < cnt) {
-                        const uint32_t s = (sy[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-                        const uint2 l2 = h_lenAB[s];
-                        accA += l2.x;
-                        accB += l2.y;
-                    }
+                    const uint32_t s = (sy[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                    const uint2 l2 = h_lenAB[s];
+                    accA += l2.x;
+                    accB += l2.y;
+                    low += 1ull << (6u * (s < HUF_PK ? s : (uint32_t)HUF_PK));
                 }
                 const uint32_t cost[6] = {accA & 1023u, (accA >> 10) & 1023u, (accA >> 20) & 1023u,
                                           accB & 1023u, (accB >> 10) & 1023u, (accB >> 20) & 1023u};
@@ -231,13 +272,31 @@ __global__ __launch_bounds__(HUF_NT) __attribute__((amdgpu_waves_per_eu(HUF_WAVE
                         bt = t;
                     }
                 SEL[g] = (uint8_t)bt;
+                // the packed counts: word w of table bt takes the symbols 3w .. 3w+2, one atomic each
+                unsigned long long *pk = h_pk + (lane % HUF_PK_COPIES) * HUF_PK_STRIDE + bt * (HUF_PK / 3);
 #pragma unroll
-                for (int k = 0; k < BZX_G_SIZE; k++) {
-                    if ((uint32_t)k < cnt) {
+                for (uint32_t w = 0; w < HUF_PK / 3; w++) {
+                    const uint32_t x = (uint32_t)(low >> (18 * w));
+                    const uint64_t add = (uint64_t)(x & 63u) | ((uint64_t)((x >> 6) & 63u) << 21) | ((uint64_t)((x >> 12) & 63u) << 42);
+                    if (add) atomicAdd(&pk[w], (unsigned long long)add);
+                }
+                if ((low >> (6 * HUF_PK)) != 0) {           // (the group holds symbols above the packed range)
+#pragma unroll
+                    for (int k = 0; k < BZX_G_SIZE; k++) {
+                        if ((k & 1) == 0) HUF_FORGET(sy[k >> 1]);
                         const uint32_t s = (sy[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-                        atomicAdd(&h_rfreq[bt][s], 1u);
+                        if (s >= HUF_PK) atomicAdd(&h_rfreq[bt][s], 1u);
                     }
                 }
+            }
+            __syncthreads();
+            if (tid < 6 * HUF_PK) {                          // the packed counts of the copies -> h_rfreq
+                const uint32_t t = tid / HUF_PK, s = tid % HUF_PK;
+                uint32_t f = 0;
+#pragma unroll
+                for (uint32_t c = 0; c < HUF_PK_COPIES; c++)
+                    f += (uint32_t)(h_pk[c * HUF_PK_STRIDE + t * (HUF_PK / 3) + s / 3] >> (21 * (s % 3))) & 0x1FFFFFu;
+                h_rfreq[t][s] = f;
             }
             __syncthreads();
             HUF_STAMP(41);
@@ -283,6 +342,7 @@ __global__ __launch_bounds__(HUF_NT) __attribute__((amdgpu_waves_per_eu(HUF_WAVE
         for (uint32_t v = tid; v < BZX_MAX_ALPHA + 2; v += HUF_NT) {
             h_lenAB[v] = make_uint2((uint32_t)h_len[0][v] | ((uint32_t)h_len[1][v] << 10) | ((uint32_t)h_len[2][v] << 20),
                                     (uint32_t)h_len[3][v] | ((uint32_t)h_len[4][v] << 10) | ((uint32_t)h_len[5][v] << 20));
+            if (v == HUF_NULL) h_lenAB[v] = make_uint2(0u, 0u);
         }
         __syncthreads();
 
@@ -293,20 +353,16 @@ __global__ __launch_bounds__(HUF_NT) __attribute__((amdgpu_waves_per_eu(HUF_WAVE
             for (uint32_t g = tid; g < n_sel; g += HUF_NT) {
                 const uint32_t gs = g * BZX_G_SIZE;
                 const uint32_t cnt = (n_mtf - gs < BZX_G_SIZE) ? n_mtf - gs : BZX_G_SIZE;
-                const uint32_t *__restrict__ vp = reinterpret_cast<const uint32_t *>(V + gs);
                 const uint32_t bt = SEL[g];
                 uint32_t sy[BZX_G_SIZE / 2];
-#pragma unroll
-                for (int k = 0; k < BZX_G_SIZE / 2; k++) sy[k] = vp[k];
+                huff_load_group(V + gs, cnt, sy);
                 uint32_t accA = 0, accB = 0;
 #pragma unroll
                 for (int k = 0; k < BZX_G_SIZE; k++) {
-                    if ((uint32_t)k < cnt) {
-                        const uint32_t sm = (sy[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-                        const uint2 l2 = h_lenAB[sm];
-                        accA += l2.x;
-                        accB += l2.y;
-                    }
+                    const uint32_t sm = (sy[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                    const uint2 l2 = h_lenAB[sm];
+                    accA += l2.x;
+                    accB += l2.y;
                 }
                 const uint32_t pick = bt < 3 ? accA : accB;
                 const uint32_t acc = (pick >> (10 * (bt % 3))) & 1023u;
