@@ -807,6 +807,7 @@ extern "C" int bzx_compress_device(bzx_ctx *ctx, const void *d_raw, size_t len, 
 {
     auto api_lock_ = ctx_lock(ctx);
     BZX_REFUSE_WHILE_STREAMING(ctx);
+    if (ctx) ctx->cidx_ok = false;
     if (!ctx || !d_out || !out_len || !level_ok(level) || (len && !d_raw)) return BZX_E_PARAM;
     if (((uintptr_t)d_raw & 15u) || ((uintptr_t)d_out & 3u) || cap < 16) {
         ctx->err = "bzx_compress_device: d_raw must be 16-byte aligned, d_out 4-byte aligned, cap >= 16";
@@ -829,6 +830,20 @@ extern "C" int bzx_compress_device(bzx_ctx *ctx, const void *d_raw, size_t len, 
     ctx->stats.out_bits = (uint64_t)*out_len * 8;
     (void)hipEventElapsedTime(&ctx->stats.ms_split, ctx->ev[5], ctx->ev[6]);
     (void)hipEventElapsedTime(&ctx->stats.ms_total, ctx->ev[5], ctx->ev[7]);
+    if (ctx->keep_index) {                      // the descriptors are on the host already: the index costs no device work
+        uint64_t bit = 32, raw_off = 0;
+        ctx->cidx.clear();
+        if (index_append(ctx->cidx, ctx->h_blk, nblk, level, &bit, &raw_off)) {
+            ctx->err = "out of host memory for the block index";
+            return BZX_E_NOMEM;
+        }
+        memset(&ctx->cidx_info, 0, sizeof(ctx->cidx_info));
+        ctx->cidx_info.in_bytes = *out_len;
+        ctx->cidx_info.out_bytes = raw_off;
+        ctx->cidx_info.nblk = nblk;
+        ctx->cidx_info.nstreams = 1;
+        ctx->cidx_ok = true;
+    }
     return BZX_OK;
 }
 

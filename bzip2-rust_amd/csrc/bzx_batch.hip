@@ -25,6 +25,9 @@
 #include "bzx_rle1.h"
 
 #define BT_NT 1024        // layout kernel (one workgroup)
+#define BX_NT 256         // index kernel: entries per workgroup
+#define BX_WORDS 5        // 64-bit words of a bzx_index_entry
+static_assert(sizeof(bzx_index_entry) == BX_WORDS * 8 && (BX_NT * BX_WORDS) % 2 == 0, "index entries: whole 16-byte vectors per workgroup");
 
 __device__ __forceinline__ uint64_t bt_carry(const BzxBatchWs &ws, const BzxSeg &s, uint64_t tile)
 {
@@ -257,6 +260,33 @@ __global__ __launch_bounds__(BT_NT) void bzx_bt_layout_kernel(BzxBatchWs ws, uin
     }
 }
 
+// ---- index entries of the round's blocks [0, nb) (bzx_ctx_keep_index), after the layout: one lane per block builds the
+// 40-byte entry in registers -- bit and out_off count from the start of the block's own stream and input -- and the
+// workgroup's 256 entries, contiguous in ws.idx, leave through LDS as whole 16-byte vectors, lane after lane.
+__global__ __launch_bounds__(BX_NT) void bzx_bt_index_kernel(BzxBatchWs ws, uint32_t rb0, uint32_t nb,
+                                                             const BzxBlock *__restrict__ blk, uint32_t level)
+{
+    __shared__ __attribute__((aligned(16))) uint64_t s_w[BX_NT * BX_WORDS];
+    const uint32_t tid = threadIdx.x, b0 = blockIdx.x * BX_NT, b = b0 + tid;
+    if (b < nb) {
+        const uint32_t si = ws.blk_seg[b], first = ws.seg_blk[si] - rb0;
+        const uint64_t *braw = ws.blk_raw + ws.seg[si].slot0 + (b - first);
+        const uint64_t off = braw[0];
+        uint64_t *w = s_w + tid * BX_WORDS;
+        w[0] = 32 + ws.pre[b] - ws.pre[first];                                       // bit
+        w[1] = off;                                                                  // out_off
+        w[2] = (uint64_t)(uint32_t)(braw[1] - off) | ((uint64_t)blk[b].crc << 32);   // out_len, crc
+        w[3] = (uint64_t)(uint32_t)blk[b].bits;                                      // img_bits, stream = 0
+        w[4] = (uint64_t)(level & 0xffu);                                            // level, reserved = 0
+    }
+    __syncthreads();
+    const uint32_t cnt = nb - b0 < BX_NT ? nb - b0 : BX_NT, nw = cnt * BX_WORDS;     // words this workgroup owns
+    uint64_t *dst = ws.idx + (size_t)b0 * BX_WORDS;                                  // (16-byte aligned: b0 * 40 is)
+    for (uint32_t v = tid; v < nw / 2; v += BX_NT)
+        reinterpret_cast<uint4 *>(dst)[v] = reinterpret_cast<const uint4 *>(s_w)[v];
+    if ((nw & 1u) && tid == 0) dst[nw - 1] = s_w[nw - 1];
+}
+
 // OR the low nbits (1..32) of val into the big-endian bit buffer at bit pos (nothing else writes these words now)
 __device__ __forceinline__ void bt_or_bits(uint32_t *out, uint64_t pos, uint32_t nbits, uint32_t val)
 {
@@ -328,6 +358,13 @@ static void bzx_batch_launch_layout(const BzxBatchWs &ws, uint32_t i0, uint32_t 
     hipLaunchKernelGGL(bzx_bt_layout_kernel, dim3(1), dim3(BT_NT), 0, st, ws, i0, i1, rb0, nb, blk, base);
 }
 
+static void bzx_batch_launch_index(const BzxBatchWs &ws, uint32_t rb0, uint32_t nb, const BzxBlock *blk, int level,
+                                   hipStream_t st)
+{
+    hipLaunchKernelGGL(bzx_bt_index_kernel, dim3((nb + BX_NT - 1) / BX_NT), dim3(BX_NT), 0, st, ws, rb0, nb, blk,
+                       (uint32_t)level);
+}
+
 static void bzx_batch_launch_frame(const BzxBatchWs &ws, uint32_t i0, uint32_t i1, uint32_t rb0, const BzxBlock *blk,
                                    void *d_out, int level, hipStream_t st)
 {
@@ -346,10 +383,12 @@ extern "C" size_t bzx_compress_batch_bound(uint32_t count, const size_t *lens)
 }
 
 // Carves the device tables of a batch call out of ctx->batch_ws (grown on demand).
-static int batch_ws_alloc(bzx_ctx *ctx, uint32_t count, uint64_t ntiles, uint64_t nslots, uint32_t max_round, BzxBatchWs *ws)
+static int batch_ws_alloc(bzx_ctx *ctx, uint32_t count, uint64_t ntiles, uint64_t nslots, uint32_t max_round, bool keep,
+                          BzxBatchWs *ws)
 {
     const bool ok = carved(ctx->batch_ws, 8, [&](Carver &c) {
         auto take = [&](size_t nwords) { return c.take<uint64_t>(nwords); };
+        ws->idx = keep ? take((size_t)max_round * BX_WORDS + 2) : nullptr;      // (first: on the 16 bytes of the allocation)
         ws->seg = (BzxSeg *)take((size_t)count * (sizeof(BzxSeg) / 8));
         ws->tile_seg = (uint32_t *)take((ntiles + 8) / 2);
         ws->tile_rs = take(ntiles + 2);
@@ -428,6 +467,7 @@ static int batch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, co
                      size_t cap, size_t *out_offs, size_t *out_lens)
 {
     hipStream_t st = ctx->stream;
+    const bool keep = ctx->keep_index;
     const uint64_t nmax = (uint64_t)100000 * level - 19;
     std::vector<BzxSeg> seg(count);
     uint64_t ntiles = 0, nslots = 0;
@@ -456,7 +496,7 @@ static int batch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, co
         for (uint64_t t = seg[i].tile0; t < t1; t++) tile_seg[t] = i;
     }
     BzxBatchWs ws;
-    int rc = batch_ws_alloc(ctx, count, ntiles, nslots, max_round, &ws);
+    int rc = batch_ws_alloc(ctx, count, ntiles, nslots, max_round, keep, &ws);
     if (rc) return rc;
     bzx_stats &stt = ctx->stats;
     memset(&stt, 0, sizeof(stt));
@@ -483,6 +523,12 @@ static int batch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, co
         if (nblk[i] > R) R = nblk[i];
     }
     if ((rc = ensure_blocks(ctx, R))) return rc;
+    if (keep) {                                 // 40 bytes per block of the call, and where each stream's entries start
+        ctx->bidx.resize(total);
+        ctx->bidx_first.resize((size_t)count + 1);
+        for (uint32_t i = 0; i < count; i++) ctx->bidx_first[i] = first[i];
+        ctx->bidx_first[count] = total;
+    }
     HIP_TRY(ctx, hipMemcpyAsync(ws.seg_blk, first.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     BzxBatch &B = ctx->B;
     B.in = ctx->d_in;
@@ -509,6 +555,12 @@ static int batch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, co
         HIP_TRY(ctx, hipMemcpyAsync(out_lens + i0, ws.s_len + i0, (i1 - i0) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_scalars, ws.round_end, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         if (nb) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_blk, B.blk, nb * sizeof(BzxBlock), hipMemcpyDeviceToHost, st));
+        if (keep && nb) {                                    // the round's entries, in input order behind those before
+            bzx_batch_launch_index(ws, rb0, nb, B.blk, level, st);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->bidx.data() + rb0, ws.idx, (size_t)nb * sizeof(bzx_index_entry),
+                                        hipMemcpyDeviceToHost, st));
+        }
         HIP_TRY(ctx, hipStreamSynchronize(st));             // the round's one host synchronisation
         const uint64_t end = ctx->h_scalars[0];
         if (emit_pending) {                                  // emit time of the previous round
@@ -556,6 +608,34 @@ static int batch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, co
         stt.ms_emit += ms;
     }
     (void)hipEventElapsedTime(&stt.ms_total, ctx->ev[5], ctx->ev[7]);
+    ctx->bidx_ok = keep;
+    return BZX_OK;
+}
+
+// count == 0: nothing is written; a kept index has no entry and first[] = {0}.
+static int batch_empty(bzx_ctx *ctx)
+{
+    if (!ctx->keep_index) return BZX_OK;
+    try {
+        ctx->bidx.clear();
+        ctx->bidx_first.assign(1, 0);
+    } catch (const std::bad_alloc &) {
+        ctx->err = "out of host memory";
+        return BZX_E_NOMEM;
+    }
+    ctx->bidx_ok = true;
+    return BZX_OK;
+}
+
+extern "C" int bzx_compress_batch_get_index(const bzx_ctx *ctx, const bzx_index_entry **entries, const uint64_t **first,
+                                            uint32_t *count)
+{
+    if (!ctx || !entries || !first || !count) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(const_cast<bzx_ctx *>(ctx)->api_mu);
+    if (!ctx->keep_index || !ctx->bidx_ok) return BZX_E_STATE;
+    *entries = ctx->bidx.data();
+    *first = ctx->bidx_first.data();
+    *count = (uint32_t)(ctx->bidx_first.size() - 1);
     return BZX_OK;
 }
 
@@ -565,11 +645,12 @@ extern "C" int bzx_compress_batch_device(bzx_ctx *ctx, uint32_t count, const voi
     auto api_lock_ = ctx_lock(ctx);
     BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx) return BZX_E_PARAM;
+    ctx->bidx_ok = false;
     if (!level_ok(level)) {
         ctx->err = "bzx_compress_batch_device: level must be 1..9";
         return BZX_E_PARAM;
     }
-    if (count == 0) return BZX_OK;
+    if (count == 0) return batch_empty(ctx);
     int rc = batch_args(ctx, "bzx_compress_batch_device", count, d_raws, lens, d_out, out_offs, out_lens, true);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -594,11 +675,12 @@ extern "C" int bzx_compress_batch_buffer(bzx_ctx *ctx, uint32_t count, const uin
     auto api_lock_ = ctx_lock(ctx);
     BZX_REFUSE_WHILE_STREAMING(ctx);
     if (!ctx) return BZX_E_PARAM;
+    ctx->bidx_ok = false;
     if (!level_ok(level)) {
         ctx->err = "bzx_compress_batch_buffer: level must be 1..9";
         return BZX_E_PARAM;
     }
-    if (count == 0) return BZX_OK;
+    if (count == 0) return batch_empty(ctx);
     int rc = batch_args(ctx, "bzx_compress_batch_buffer", count, (const void *const *)raws, lens, out, out_offs, out_lens,
                         false);
     if (rc) return rc;
@@ -653,6 +735,7 @@ static int batch_buffer(bzx_ctx *ctx, uint32_t count, const uint8_t *const *raws
         if (hipMemcpyAsync(out, d_out, end, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
             ctx->err = "hipMemcpyAsync(batch output) failed";
             rc = BZX_E_HIP;
+            ctx->bidx_ok = false;
         }
     }
     (void)hipStreamSynchronize(ctx->stream);

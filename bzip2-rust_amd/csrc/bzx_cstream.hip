@@ -26,6 +26,7 @@ struct bzx_cstream {
     size_t carry_len = 0, carry_start = 0;  // raw bytes of the withheld block inside d_in[(k-1)&1]
     bool pend = false;                      // a chunk's output still sits in d_out[pend_slot]
     uint32_t pend_slot = 0, pend_nblk = 0;
+    bool counted = false;                   // the caller's object (bzx_cstream_begin), counted in ctx->n_cstreams
 };
 
 // A block covers at most nblockMAX RLE1 bytes = nblockMAX / 5 runs of 255: the withheld raw tail never exceeds this.
@@ -126,12 +127,57 @@ void ChunkAcct::merge_first_word(const ChunkPlace &p, const uint32_t *h_w0)
     else for (int i = 0; i < 4; i++) out[p.off + i] |= w[i];
 }
 
-void ChunkAcct::account_chunk(const BzxBlock *h_blk, uint32_t nblk, uint64_t cbits)
+int index_append(std::vector<bzx_index_entry> &idx, const BzxBlock *h_blk, uint32_t nblk, int level, uint64_t *bit,
+                 uint64_t *raw_off)
 {
+    try {
+        idx.reserve(idx.size() + nblk);
+    } catch (const std::bad_alloc &) {
+        return BZX_E_NOMEM;
+    }
+    for (uint32_t b = 0; b < nblk; b++) {
+        bzx_index_entry e;
+        memset(&e, 0, sizeof(e));
+        e.bit = *bit;
+        e.out_off = *raw_off;
+        e.out_len = h_blk[b].raw_len;
+        e.crc = h_blk[b].crc;
+        e.img_bits = (uint32_t)h_blk[b].bits;
+        e.level = (uint8_t)level;
+        idx.push_back(e);
+        *bit += h_blk[b].bits;
+        *raw_off += h_blk[b].raw_len;
+    }
+    return BZX_OK;
+}
+
+// (the withheld last block of a non-final chunk is not among h_blk: its entry comes with the chunk that finishes it)
+int ChunkAcct::account_chunk(const BzxBlock *h_blk, uint32_t nblk, uint64_t cbits, std::string &err)
+{
+    if (keep) {
+        uint64_t bit = bits;
+        if (index_append(idx, h_blk, nblk, level, &bit, &raw_off)) {
+            err = "out of host memory for the block index";
+            return BZX_E_NOMEM;
+        }
+    }
     fold_blocks(st, h_blk, 0, nblk, 1);
     for (uint32_t b = 0; b < nblk; b++) crc_comb = crc_fold(crc_comb, h_blk[b].crc);
     nblk_total += nblk;
     bits += cbits;
+    return BZX_OK;
+}
+
+int ChunkAcct::get_index(const bzx_index_entry **entries, bzx_index_info *info) const
+{
+    if (!keep || sticky) return BZX_E_STATE;
+    *entries = idx.data();
+    memset(info, 0, sizeof(*info));
+    info->nblk = idx.size();
+    info->out_bytes = raw_off;
+    info->in_bytes = finished ? stream_bytes : 0;
+    info->nstreams = finished ? 1 : 0;
+    return BZX_OK;
 }
 
 // Footer of a stream whose last block ends at bit `end`: magic, combined CRC (crc.rs:25-27), zero padding to a byte
@@ -162,6 +208,7 @@ int ChunkAcct::finish(size_t len, size_t *produced, std::string &err)
     stream_write_footer(out, bits, need, crc_comb);
     *produced = need;
     finished = true;
+    stream_bytes = need;
     st.nblk = (uint32_t)nblk_total;
     st.raw_bytes += len;
     st.out_bits = (uint64_t)need * 8;
@@ -171,23 +218,24 @@ int ChunkAcct::finish(size_t len, size_t *produced, std::string &err)
 extern "C" void bzx_cstream_end(bzx_cstream *s)
 {
     if (!s) return;
+    if (s->ctx && s->counted) {
+        std::unique_lock<std::recursive_mutex> api_lock_(s->ctx->api_mu);
+        s->ctx->n_cstreams--;
+    }
     if (s->ctx) (void)hipSetDevice(s->ctx->device);
     if (s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
     s->L.free();
     delete s;
 }
 
-extern "C" int bzx_cstream_begin(bzx_ctx *ctx, int level, size_t max_chunk, bzx_cstream **out)
+// The stream object of bzx_cstream_begin, and the one bzx_compress_buffer keeps in the context (the lock is held).
+static int cstream_make(bzx_ctx *ctx, int level, size_t max_chunk, bzx_cstream **out)
 {
-    if (!ctx || !out || !level_ok(level)) return BZX_E_PARAM;
-    *out = nullptr;
-    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
-    BZX_REFUSE_WHILE_STREAMING(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     bzx_cstream *s = new (std::nothrow) bzx_cstream();
     if (!s) return BZX_E_NOMEM;
     s->ctx = ctx;
-    s->a.reset(level);
+    s->a.reset(level, ctx->keep_index);
     s->c = chunk_caps(max_chunk);
     if (!s->L.alloc(s->c.in_cap, s->c.out_cap, s->c.blk_cap) ||
         hipMemsetAsync(s->L.d_phase, 0, 4 * sizeof(uint64_t), ctx->stream) != hipSuccess) {
@@ -196,6 +244,50 @@ extern "C" int bzx_cstream_begin(bzx_ctx *ctx, int level, size_t max_chunk, bzx_
         return BZX_E_NOMEM;
     }
     *out = s;
+    return BZX_OK;
+}
+
+extern "C" int bzx_cstream_begin(bzx_ctx *ctx, int level, size_t max_chunk, bzx_cstream **out)
+{
+    if (!ctx || !out || !level_ok(level)) return BZX_E_PARAM;
+    *out = nullptr;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
+    const int rc = cstream_make(ctx, level, max_chunk, out);
+    if (rc == BZX_OK) {
+        (*out)->counted = true;
+        ctx->n_cstreams++;
+    }
+    return rc;
+}
+
+extern "C" int bzx_cstream_get_index(const bzx_cstream *s, const bzx_index_entry **entries, bzx_index_info *info)
+{
+    if (!s || !s->ctx || !entries || !info) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(s->ctx->api_mu);
+    return s->a.get_index(entries, info);
+}
+
+extern "C" int bzx_ctx_keep_index(bzx_ctx *ctx, int on)
+{
+    if (!ctx) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    if (ctx->n_cstreams) {
+        ctx->err = "bzx_ctx_keep_index: a bzx_cstream is open on this context: call bzx_cstream_end first";
+        return BZX_E_STATE;
+    }
+    ctx->keep_index = on != 0;
+    ctx->cidx_ok = ctx->bidx_ok = false;
+    return BZX_OK;
+}
+
+extern "C" int bzx_compress_get_index(const bzx_ctx *ctx, const bzx_index_entry **entries, bzx_index_info *info)
+{
+    if (!ctx || !entries || !info) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(const_cast<bzx_ctx *>(ctx)->api_mu);
+    if (!ctx->keep_index || !ctx->cidx_ok) return BZX_E_STATE;
+    *entries = ctx->cidx.data();
+    *info = ctx->cidx_info;
     return BZX_OK;
 }
 
@@ -235,9 +327,9 @@ static int cstream_collect(bzx_cstream *s)
     // (bzx_get_block_info: the stream's descriptors in order, as far as the context's descriptor table reaches)
     for (uint32_t b = 0; b < s->pend_nblk && ctx->h_blk && s->a.nblk_total + b < ctx->cap_blocks; b++)
         ctx->h_blk[s->a.nblk_total + b] = L.h_blk[slot][b];
-    s->a.account_chunk(L.h_blk[slot], s->pend_nblk, cbits);
+    const uint32_t nblk = s->pend_nblk;
     s->pend = false;
-    return BZX_OK;
+    return s->a.account_chunk(L.h_blk[slot], nblk, cbits, ctx->err);
 }
 
 // Back to the state after bzx_cstream_begin (buffers kept): a new stream on the same object.
@@ -248,7 +340,7 @@ static int cstream_reset(bzx_cstream *s, int level)
     HIP_TRY(ctx, hipStreamSynchronize(s->L.s_h2d));
     HIP_TRY(ctx, hipStreamSynchronize(s->L.s_d2h));
     HIP_TRY(ctx, hipMemsetAsync(s->L.d_phase, 0, 4 * sizeof(uint64_t), ctx->stream));
-    s->a.reset(level);
+    s->a.reset(level, ctx->keep_index);
     s->carry_len = s->carry_start = 0;
     s->pend = false;
     return BZX_OK;
@@ -356,6 +448,7 @@ extern "C" int bzx_compress_buffer(bzx_ctx *ctx, const uint8_t *raw, size_t len,
 {
     auto api_lock_ = ctx_lock(ctx);
     BZX_REFUSE_WHILE_STREAMING(ctx);
+    if (ctx) ctx->cidx_ok = false;
     if (!ctx || !out || !out_len || !level_ok(level) || (len && !raw) || cap < 16) return BZX_E_PARAM;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     size_t chunk = buffer_chunk(len, ctx->n_cu, (size_t)16 << 20);      // (the emulator's smaller floor is bzx_mcompress_buffer's alone)
@@ -365,7 +458,7 @@ extern "C" int bzx_compress_buffer(bzx_ctx *ctx, const uint8_t *raw, size_t len,
         ctx->cs = nullptr;
     }
     if (!ctx->cs) {
-        if ((rc = bzx_cstream_begin(ctx, level, chunk, &ctx->cs))) return rc;
+        if ((rc = cstream_make(ctx, level, chunk, &ctx->cs))) return rc;
     } else if ((rc = cstream_reset(ctx->cs, level))) {
         return rc;
     }
@@ -387,5 +480,12 @@ extern "C" int bzx_compress_buffer(bzx_ctx *ctx, const uint8_t *raw, size_t len,
     (void)hipEventElapsedTime(&ctx->stats.ms_total, e0, e1);
     ctx->stats.raw_bytes = len;
     *out_len = produced;
+    if (ctx->keep_index) {                      // the stream's entries move to the context (no copy; the stream object
+        const bzx_index_entry *e;               // clears what it gets back when the next call starts it anew)
+        if (ctx->cs->a.get_index(&e, &ctx->cidx_info) == BZX_OK) {
+            ctx->cidx.swap(ctx->cs->a.idx);
+            ctx->cidx_ok = true;
+        }
+    }
     return BZX_OK;
 }

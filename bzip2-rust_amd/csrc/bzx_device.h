@@ -91,6 +91,8 @@ struct BzxBlock {
     uint32_t sec_bits[4];   // [0] selectors, [1] coding tables, [2] payload, [3] symbol map
     uint32_t pad_[2];       // [0] copies of every rotation in a periodic block, [1] debug: microseconds in the BWT kernel
     uint64_t pack_word;     // sharded runs: first 32-bit word of the block image in this rank's packed buffer
+    uint32_t raw_len;       // raw bytes the block covers (at most 259/5 x 900,000), left by the one-input splitter for the
+    uint32_t pad2_;         // compressor's block index (bzx_ctx_keep_index); 0 where the host made the descriptor
 };
 
 // Per-workgroup-slot scratch of the suffix sorter (one slot per resident workgroup).
@@ -205,6 +207,8 @@ struct BzxBatchWs {
     uint64_t *s_len;        // [count] byte length of each stream
     uint64_t *round_end;    // [1] end of the round's last stream, rounded up to 4 bytes
     uint64_t *segtot;       // scratch of the tile scans
+    uint64_t *idx;          // [5 * round blocks] index entries of the round (40 bytes each), 16-byte aligned; null unless the
+                            // context keeps the index (bzx_ctx_keep_index)
     uint64_t ntiles;
     uint32_t count;
 };

@@ -91,6 +91,17 @@ struct bzx_ctx {
     uint32_t range_slabs = 0;                   // blocks the round tables hold
     DevMem<> range_io[2];                       // the _buffer form's span [0] and output [1] on the device, grown on demand
     DevMem<> range_sl;                          // the gather kernel's slice table, grown on demand
+
+    // block index kept by the compressor (bzx_ctx_keep_index; off: nothing below is touched but the two flags a
+    // compression call clears)
+    bool keep_index = false;
+    uint32_t n_cstreams = 0;                    // bzx_cstream objects the caller has open on this context
+    bool cidx_ok = false;                       // cidx / cidx_info describe the last bzx_compress_device / _buffer call
+    std::vector<bzx_index_entry> cidx;
+    bzx_index_info cidx_info = {};
+    bool bidx_ok = false;                       // bidx / bidx_first describe the last bzx_compress_batch_* call
+    std::vector<bzx_index_entry> bidx;          // the entries of all streams, in input order
+    std::vector<uint64_t> bidx_first;           // [count + 1] stream i owns bidx[bidx_first[i] .. bidx_first[i + 1])
 };
 
 #define HIP_TRY(ctx, expr)                                                                       \
@@ -179,14 +190,34 @@ struct ChunkAcct {
     int sticky = BZX_OK;                          // the error a feed call returned: later feed calls return it again
     uint8_t *out = nullptr;
     size_t cap = 0, need_hint = 0;                // need_hint, after BZX_E_OUTBUF: bytes the output needs at least
-    void reset(int l) { *this = ChunkAcct(); level = l; }      // a new stream on the same object
+    // the stream's block index (bzx_ctx_keep_index): one entry per block accounted for, 40 bytes each; empty when off
+    bool keep = false;
+    std::vector<bzx_index_entry> idx;
+    uint64_t raw_off = 0;                         // raw bytes the entries cover
+    uint64_t stream_bytes = 0;                    // length of the finished stream
+    void reset(int l, bool keep_index = false)    // a new stream on the same object (the index keeps its memory)
+    {
+        std::vector<bzx_index_entry> v;
+        v.swap(idx);
+        *this = ChunkAcct();
+        level = l;
+        keep = keep_index;
+        v.clear();
+        idx.swap(v);
+    }
     void begin_output(uint8_t *out, size_t cap);  // the caller's buffer of this feed call; chunk 0: the stream header
     int place_chunk(uint64_t cbits, ChunkPlace *p, std::string &err);
     void merge_first_word(const ChunkPlace &p, const uint32_t *h_w0);
-    void account_chunk(const BzxBlock *h_blk, uint32_t nblk, uint64_t cbits);
+    int account_chunk(const BzxBlock *h_blk, uint32_t nblk, uint64_t cbits, std::string &err);
+    // the entries so far; in_bytes and nstreams are 0 until finish() has run (BZX_E_STATE when the index is not kept)
+    int get_index(const bzx_index_entry **entries, bzx_index_info *info) const;
     // final feed call of len bytes, every chunk accounted for: footer, *produced, and nblk / raw_bytes / out_bits of st
     int finish(size_t len, size_t *produced, std::string &err);
 };
+// Appends the index entries of nblk blocks of one stream, in order, from their descriptors (crc, bits, raw_len): *bit and
+// *raw_off are the running sums, before and after.  BZX_E_NOMEM when the vector cannot grow (nothing unwinds).
+int index_append(std::vector<bzx_index_entry> &idx, const BzxBlock *h_blk, uint32_t nblk, int level, uint64_t *bit,
+                 uint64_t *raw_off);
 // combined CRC of a stream after one more block (crc.rs:25-27)
 __host__ __device__ static inline uint32_t crc_fold(uint32_t comb, uint32_t crc) { return ((comb << 1) | (comb >> 31)) ^ crc; }
 

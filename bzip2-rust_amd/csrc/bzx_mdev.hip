@@ -102,6 +102,10 @@ struct bzx_mctx {
     bzx_mstream *cs = nullptr;       // stream object kept for bzx_mcompress_buffer
     bzx_stats stats;
     bzx_mdev_info info;
+    bool keep_index = false;         // bzx_mctx_keep_index
+    bool cidx_ok = false;            // cidx / cidx_info describe the last bzx_mcompress_buffer call
+    std::vector<bzx_index_entry> cidx;
+    bzx_index_info cidx_info = {};
 };
 
 struct MEntry {
@@ -227,7 +231,7 @@ extern "C" void bzx_mstream_end(bzx_mstream *s)
 static void mstream_reset_counts(bzx_mstream *s, int level)
 {
     bzx_mctx *m = s->m;
-    s->a.reset(level);
+    s->a.reset(level, m->keep_index);
     s->k_coll = 0;
     s->tail_len = 0;
     m->info.chunks = m->info.shifted = 0;
@@ -343,7 +347,7 @@ static int mstream_collect(bzx_mstream *s, uint32_t j)
     M_TRY(m, e, hipEventRecord(L.ev_d2h, L.s_d2h));
     M_TRY(m, e, hipEventSynchronize(L.ev_d2h));
     s->a.merge_first_word(p, L.h_w0);
-    s->a.account_chunk(L.h_blk[slot], nblk, cbits);
+    if ((rc = s->a.account_chunk(L.h_blk[slot], nblk, cbits, m->err))) return rc;
     m->info.nblk = s->a.nblk_total;
     return BZX_OK;
 }
@@ -454,8 +458,15 @@ extern "C" int bzx_mstream_feed(bzx_mstream *s, const uint8_t *raw, size_t len, 
 extern "C" int bzx_mcompress_buffer(bzx_mctx *m, const uint8_t *raw, size_t len, int level, uint8_t *out, size_t cap,
                                     size_t *out_len)
 {
-    if (!m || !out || !out_len || !level_ok(level) || (len && !raw) || cap < 16) return BZX_E_PARAM;
+    if (!m || !out || !out_len || !level_ok(level) || (len && !raw) || cap < 16) {
+        if (m) {
+            std::unique_lock<std::recursive_mutex> lock_(m->mu);
+            m->cidx_ok = false;
+        }
+        return BZX_E_PARAM;
+    }
     std::unique_lock<std::recursive_mutex> lock_(m->mu);
+    m->cidx_ok = false;
     if (m->open) {
         m->err = "a bzx_mstream is open on this bzx_mctx: call bzx_mstream_end first";
         return BZX_E_STATE;
@@ -491,5 +502,46 @@ extern "C" int bzx_mcompress_buffer(bzx_mctx *m, const uint8_t *raw, size_t len,
         off += n;
     } while (off < len);
     *out_len = produced;
+    if (m->keep_index) {                         // the stream's entries move to the bzx_mctx (bzx_compress_buffer likewise)
+        const bzx_index_entry *e;
+        if (s->a.get_index(&e, &m->cidx_info) == BZX_OK) {
+            m->cidx.swap(s->a.idx);
+            m->cidx_ok = true;
+        }
+    }
     return BZX_OK;
+}
+
+extern "C" int bzx_mctx_keep_index(bzx_mctx *m, int on)
+{
+    if (!m) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> lock_(m->mu);
+    if (m->open) {
+        m->err = "bzx_mctx_keep_index: a bzx_mstream is open on this bzx_mctx: call bzx_mstream_end first";
+        return BZX_E_STATE;
+    }
+    for (uint32_t e = 0; e < m->ndev; e++) {
+        const int rc = bzx_ctx_keep_index(m->ctx[e], on);
+        if (rc) return ctx_failed(m, e, rc);
+    }
+    m->keep_index = on != 0;
+    m->cidx_ok = false;
+    return BZX_OK;
+}
+
+extern "C" int bzx_mctx_get_index(const bzx_mctx *m, const bzx_index_entry **entries, bzx_index_info *info)
+{
+    if (!m || !entries || !info) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> lock_(const_cast<bzx_mctx *>(m)->mu);
+    if (!m->keep_index || !m->cidx_ok) return BZX_E_STATE;
+    *entries = m->cidx.data();
+    *info = m->cidx_info;
+    return BZX_OK;
+}
+
+extern "C" int bzx_mstream_get_index(const bzx_mstream *s, const bzx_index_entry **entries, bzx_index_info *info)
+{
+    if (!s || !s->m || !entries || !info) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> lock_(s->m->mu);
+    return s->a.get_index(entries, info);
 }

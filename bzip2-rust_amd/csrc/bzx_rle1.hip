@@ -271,6 +271,7 @@ __global__ __launch_bounds__(RL_NT) void bzx_rl_scatter_kernel(const uint8_t *__
     for (uint32_t b = blockIdx.x * RL_NT + threadIdx.x; b < nblk; b += gridDim.x * RL_NT) {
         blk[b].in_off = (ws.blk_plain[b] || all_plain) ? (BZX_IN_RAW | ws.blk_raw[b]) : (uint64_t)(b / own_step) * BZX_BLK_STRIDE;
         blk[b].n = (uint32_t)(ws.blk_f[b + 1] - ws.blk_f[b]);
+        blk[b].raw_len = (uint32_t)(ws.blk_raw[b + 1] - ws.blk_raw[b]);
         blk[b].status = 0;
     }
 }

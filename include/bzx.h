@@ -406,6 +406,51 @@ void bzx_index_end(bzx_index *ix);
 int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries, uint64_t cap_entries,
                            bzx_index_info *info);
 /*
+ * The index straight from compression: with keeping switched on, a compression call leaves the index of the stream it
+ * wrote, so the first range read needs no decode pass over the library's own output.
+ * The rule: after a successful call of an entry point named below, the entries and the bzx_index_info are identical,
+ * field for field and byte for byte (memcmp of the 40-byte entries, reserved zero), to what bzx_index_build_buffer returns
+ * for the stream the call produced.  An empty input gives 0 entries and info = {in_bytes 14, out_bytes 0, nblk 0,
+ * nstreams 1}.  The compressed bytes do not change: they stay byte-identical to libbz2.
+ * Where a field comes from: bit = 32 + the sizes of the blocks before it; img_bits = the block's size; crc = its CRC;
+ * out_len = the raw bytes the block splitter gave it, out_off their running sum; stream 0; level = the call's level.
+ *   bzx_ctx_keep_index / bzx_mctx_keep_index: on != 0 switches keeping on.  The default is off, and off means off: no
+ *   compression path gains a kernel launch, a copy, a host synchronisation or a host allocation.  _mctx_ applies to every
+ *   entry's private context.  BZX_E_STATE while a bzx_cstream (bzx_mstream) of the caller is open on the object.
+ *   Switching, either way, drops the index a get call would have returned.
+ *   bzx_compress_get_index: the index of the last bzx_compress_device or bzx_compress_buffer call on the context; the
+ *   pointer stays valid until the next of these two calls or bzx_ctx_destroy.  BZX_E_STATE when keeping is off, when no
+ *   such call has happened or when the last one failed; BZX_E_PARAM for NULL arguments.  No other entry point disturbs
+ *   it: not decompression, not range reads, and not the batch and stream compressors, which keep an index of their own.
+ *   bzx_mctx_get_index: the same after bzx_mcompress_buffer.
+ *   bzx_cstream_get_index / bzx_mstream_get_index: the entries of the blocks accounted for so far; the copy-back runs
+ *   one chunk behind the feed, and the unfinished last block of a chunk appears with the chunk that finishes it.
+ *   Mid-stream every entry returned is final and the list only grows: an earlier result is a prefix of every later one.
+ *   info->nblk and info->out_bytes describe those entries; info->in_bytes and info->nstreams are 0 until the final
+ *   feed has succeeded, then the stream length and 1.  Valid until the next feed or _end.  BZX_E_STATE when keeping was
+ *   off at _begin, or after a feed that failed.
+ *   bzx_compress_batch_get_index: after bzx_compress_batch_device / _buffer.  Stream i's entries are
+ *   entries[first[i] .. first[i + 1]); first has *count + 1 values.  bit counts from the start of stream i, out_off from
+ *   the start of input i and stream is 0: the slice is the index of stream i on its own, what
+ *   bzx_index_build_buffer(out + out_offs[i], out_lens[i]) returns.  An empty input has an empty slice.  One small
+ *   kernel and one copy per device round build it (bzx_bt_index_kernel); the host synchronisations of the call stay:
+ *   one for the counts, one per round, one at the end.  Valid until the next batch call on the context.
+ * Host memory with keeping on: 40 bytes per block, held in the stream object, the context or the batch call's vector
+ * (the stream compressors already require the whole output buffer, so this is no new kind of growth).
+ * Not covered: bzx_compress_block(s) -- the caller supplies RLE1'd blocks, so the library never sees raw lengths -- and
+ * the bzx_shard_* family -- one process per GPU, so no one place sees all blocks.
+ */
+struct bzx_mctx;
+struct bzx_mstream;        /* (bzx_mctx_* / bzx_mstream_*: below) */
+int bzx_ctx_keep_index(bzx_ctx *ctx, int on);
+int bzx_mctx_keep_index(struct bzx_mctx *m, int on);
+int bzx_compress_get_index(const bzx_ctx *ctx, const bzx_index_entry **entries, bzx_index_info *info);
+int bzx_cstream_get_index(const bzx_cstream *s, const bzx_index_entry **entries, bzx_index_info *info);
+int bzx_mctx_get_index(const struct bzx_mctx *m, const bzx_index_entry **entries, bzx_index_info *info);
+int bzx_mstream_get_index(const struct bzx_mstream *s, const bzx_index_entry **entries, bzx_index_info *info);
+int bzx_compress_batch_get_index(const bzx_ctx *ctx, const bzx_index_entry **entries, const uint64_t **first,
+                                 uint32_t *count);
+/*
  * bzx_index_span (host only, no context): which entries and which input bytes the range [off, off + want) needs:
  * entries [*first, *first + *count) and input bytes [*byte_lo, *byte_hi) -- from the byte that holds the first block's
  * magic to the last block's img_bits, rounded up to a byte, + 8 (inside the file: a block is followed by ten bytes of

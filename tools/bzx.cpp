@@ -15,6 +15,9 @@
 // refuses: there is no silent full decode behind --range.  -dc --ranges LIST FILE.bz2 does the same for a list of OFF:LEN
 // lines in one bzx_decompress_ranges_buffer call: it reads the byte intervals of the file that bzx_index_spans names and
 // writes the ranges in list order, back to back; when any range fails, nothing is written.
+// --with-index FILE ... (compression) writes FILE.bz2 and FILE.bz2.bzxi in one pass: the library keeps the index while it
+// compresses (bzx_ctx_keep_index / bzx_mctx_keep_index), on the chunked path, with --devices and on the batched path; the
+// index is written after its .bz2 closed cleanly, in the format --index writes.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,6 +40,7 @@ struct Opts {
     std::vector<std::string> files;
     std::vector<int> devices;          // --devices: entries of a bzx_mctx for the chunked compression path
     bool index = false, range = false; // --index; --range OFF:LEN
+    bool with_index = false;           // --with-index: FILE.bz2.bzxi beside FILE.bz2, from the compressor
     uint64_t range_off = 0, range_len = 0;
     std::string ranges;                // --ranges LIST
 };
@@ -54,6 +58,7 @@ static void help()
          "  --index           write FILE.bzxi, the block index of every FILE (a .bz2), for --range\n"
          "  --range OFF:LEN   with -dc: decoded bytes [OFF, OFF + LEN) of FILE to standard output, through FILE.bzxi\n"
          "  --ranges LIST     with -dc: the same for every OFF:LEN line of the text file LIST, in one call, back to back\n"
+         "  --with-index      compress FILE to FILE.bz2 and write FILE.bz2.bzxi in the same pass (not with -c or standard input)\n"
          "With no file, or when a file is -, reads standard input and writes standard output.");
 }
 
@@ -80,8 +85,15 @@ static int mfail(const Opts &o, const char *what, const char *name, bzx_mctx *m,
     return 1;
 }
 
-// (mctx: with --devices the chunks go through bzx_mstream_feed, dealt over its entries, instead of bzx_cstream_feed)
-static int do_zip(const Opts &o, bzx_ctx *ctx, bzx_mctx *mctx, FILE *in, FILE *out, const char *name)
+// The index of one compressed file, copied out of the library before its stream object ends.
+struct KeptIndex {
+    std::vector<bzx_index_entry> e;
+    bzx_index_info info;
+};
+
+// (mctx: with --devices the chunks go through bzx_mstream_feed, dealt over its entries, instead of bzx_cstream_feed;
+// kept: with --with-index, receives the stream's index)
+static int do_zip(const Opts &o, bzx_ctx *ctx, bzx_mctx *mctx, FILE *in, FILE *out, const char *name, KeptIndex *kept)
 {
     const size_t CH = (size_t)64 << 20;
     bzx_cstream *cs = nullptr;
@@ -151,6 +163,19 @@ static int do_zip(const Opts &o, bzx_ctx *ctx, bzx_mctx *mctx, FILE *in, FILE *o
                     bi.n_selectors, bi.bits_symbol_map, bi.bits_selectors, bi.bits_tables, bi.bits_payload,
                     (unsigned long long)bi.bits);
     }
+    if (!ret && kept) {
+        const bzx_index_entry *e = nullptr;
+        rc = mctx ? bzx_mstream_get_index(ms, &e, &kept->info) : bzx_cstream_get_index(cs, &e, &kept->info);
+        if (rc) {
+            ret = mctx ? mfail(o, "no index", name, mctx, rc) : fail(o, "no index", name, ctx, rc);
+        } else {
+            try {
+                kept->e.assign(e, e + kept->info.nblk);
+            } catch (const std::bad_alloc &) {
+                ret = fail(o, "out of memory", name, nullptr, BZX_E_NOMEM);
+            }
+        }
+    }
     if (mctx) bzx_mstream_end(ms);
     else bzx_cstream_end(cs);
     bzx_host_free(buf[0]);
@@ -218,6 +243,40 @@ static uint64_t get_le(const uint8_t *p, int n)
 }
 static const size_t BZXI_HEADER = 64, BZXI_ENTRY = 40;
 
+// The stored form of an index (include/bzx.h) into oname; after a failure: a message, the partial file removed, 1.
+static int write_bzxi(const Opts &o, const std::string &oname, const bzx_index_entry *e, const bzx_index_info &info)
+{
+    FILE *out = fopen(oname.c_str(), "wb");
+    uint8_t head[BZXI_HEADER] = {'B', 'Z', 'X', 'I'}, rec[BZXI_ENTRY];
+    put_le(head + 4, 1, 4);
+    put_le(head + 8, info.in_bytes, 8);
+    put_le(head + 16, info.out_bytes, 8);
+    put_le(head + 24, info.nblk, 8);
+    put_le(head + 32, info.nstreams, 4);
+    bool ok = out && fwrite(head, 1, sizeof head, out) == sizeof head;
+    for (uint64_t k = 0; ok && k < info.nblk; k++) {
+        memset(rec, 0, sizeof rec);
+        put_le(rec, e[k].bit, 8);
+        put_le(rec + 8, e[k].out_off, 8);
+        put_le(rec + 16, e[k].out_len, 4);
+        put_le(rec + 20, e[k].crc, 4);
+        put_le(rec + 24, e[k].img_bits, 4);
+        put_le(rec + 28, e[k].stream, 4);
+        rec[32] = e[k].level;
+        ok = fwrite(rec, 1, sizeof rec, out) == sizeof rec;
+    }
+    if (out && fclose(out) != 0) ok = false;
+    if (!ok) {
+        if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
+        unlink(oname.c_str());
+        return 1;
+    }
+    if (o.verbose)
+        fprintf(stderr, "  %s: %llu blocks in %u streams, %llu -> %llu bytes\n", oname.c_str(), (unsigned long long)info.nblk,
+                info.nstreams, (unsigned long long)info.in_bytes, (unsigned long long)info.out_bytes);
+    return 0;
+}
+
 // FILE.bz2 -> FILE.bz2.bzxi through bzx_index_feed, 64 MiB chunks in page-locked memory as -d reads them.
 static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
 {
@@ -262,37 +321,7 @@ static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
     const bzx_index_entry *e = nullptr;
     bzx_index_info info;
     if (!ret && (rc = bzx_index_get(ix, &e, &info))) ret = fail(o, "indexing failed", name, ctx, rc);
-    if (!ret) {
-        const std::string oname = f + ".bzxi";
-        FILE *out = fopen(oname.c_str(), "wb");
-        uint8_t head[BZXI_HEADER] = {'B', 'Z', 'X', 'I'}, rec[BZXI_ENTRY];
-        put_le(head + 4, 1, 4);
-        put_le(head + 8, info.in_bytes, 8);
-        put_le(head + 16, info.out_bytes, 8);
-        put_le(head + 24, info.nblk, 8);
-        put_le(head + 32, info.nstreams, 4);
-        bool ok = out && fwrite(head, 1, sizeof head, out) == sizeof head;
-        for (uint64_t k = 0; ok && k < info.nblk; k++) {
-            memset(rec, 0, sizeof rec);
-            put_le(rec, e[k].bit, 8);
-            put_le(rec + 8, e[k].out_off, 8);
-            put_le(rec + 16, e[k].out_len, 4);
-            put_le(rec + 20, e[k].crc, 4);
-            put_le(rec + 24, e[k].img_bits, 4);
-            put_le(rec + 28, e[k].stream, 4);
-            rec[32] = e[k].level;
-            ok = fwrite(rec, 1, sizeof rec, out) == sizeof rec;
-        }
-        if (out && fclose(out) != 0) ok = false;
-        if (!ok) {
-            if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
-            unlink(oname.c_str());
-            ret = 1;
-        } else if (o.verbose) {
-            fprintf(stderr, "  %s: %llu blocks in %u streams, %llu -> %llu bytes\n", oname.c_str(), (unsigned long long)info.nblk,
-                    info.nstreams, (unsigned long long)info.in_bytes, (unsigned long long)info.out_bytes);
-        }
-    }
+    if (!ret) ret = write_bzxi(o, f + ".bzxi", e, info);
     bzx_index_end(ix);
     if (ibuf) bzx_host_free(ibuf);
     return ret;
@@ -619,13 +648,32 @@ static int flush_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &pend, 
     const int rc = obuf ? bzx_compress_batch_buffer(ctx, n, raws.data(), lens.data(), o.level, obuf, cap, offs.data(),
                                                     olens.data())
                         : BZX_E_NOMEM;
+    // --with-index: stream i's slice of the call's index is the index of FILE.bz2 on its own
+    const bzx_index_entry *ie = nullptr;
+    const uint64_t *ifirst = nullptr;
+    uint32_t icount = 0;
+    int irc = BZX_OK;
+    if (!rc && o.with_index) irc = bzx_compress_batch_get_index(ctx, &ie, &ifirst, &icount);
+    if (!irc && o.with_index && !rc && icount != n) irc = BZX_E_STATE;
     int ret = 0;
     for (uint32_t i = 0; i < n; i++) {
         Pending &p = pend[i];
         int r = 0;
         if (rc) r = fail(o, "compression failed", p.name.c_str(), obuf ? ctx : nullptr, rc);
         else if (fwrite(obuf + offs[i], 1, olens[i], p.out) != olens[i]) r = fail(o, strerror(errno), p.name.c_str(), nullptr, BZX_OK);
-        ret |= finish_file(o, p.out, p.oname, p.name, r);
+        const int done = finish_file(o, p.out, p.oname, p.name, r);
+        ret |= done;
+        if (o.with_index && !done && irc) {
+            ret |= fail(o, "no index", p.name.c_str(), ctx, irc);
+        } else if (o.with_index && !done) {
+            bzx_index_info info;
+            memset(&info, 0, sizeof info);
+            info.in_bytes = olens[i];
+            info.out_bytes = lens[i];
+            info.nblk = ifirst[i + 1] - ifirst[i];
+            info.nstreams = 1;
+            ret |= write_bzxi(o, p.oname + ".bzxi", ie + ifirst[i], info);
+        }
     }
     free(obuf);
     pend.clear();
@@ -655,6 +703,7 @@ int main(int argc, char **argv)
             else if (a == "--fast") o.level = 1;
             else if (a == "--best") o.level = 9;
             else if (a == "--index") o.index = true;
+            else if (a == "--with-index") o.with_index = true;
             else if (a == "--range" || a.rfind("--range=", 0) == 0) {
                 const std::string v = a == "--range" ? (i + 1 < argc ? argv[++i] : "") : a.substr(8);
                 const size_t c = v.find(':');
@@ -708,6 +757,20 @@ int main(int argc, char **argv)
                 else if (c == 'V' || c == 'L') { printf("bzx, bzip2 block compression on MI355X; %s\n", bzx_version()); return 0; }
                 else { fprintf(stderr, "bzx: unexpected flag -%c\n", c); return 1; }
             }
+        }
+    }
+    if (o.with_index) {
+        const char *why = o.index || o.range || !o.ranges.empty() ? "--with-index does not go with --index, --range or --ranges"
+                          : o.mode == UNZIP                        ? "--with-index goes with compression, not with -d"
+                          : o.mode == TEST                         ? "--with-index goes with compression, not with -t"
+                          : o.to_stdout ? "--with-index needs a FILE.bz2 to name the index after: not with -c"
+                                        : nullptr;
+        for (const std::string &f : o.files)
+            if (!why && f == "-") why = "--with-index needs a FILE.bz2 to name the index after: not with standard input";
+        if (!why && o.files.empty()) why = "--with-index needs a FILE.bz2 to name the index after: not with standard input";
+        if (why) {
+            fprintf(stderr, "bzx: %s\n", why);
+            return 1;
         }
     }
     if (!o.ranges.empty()) {
@@ -764,6 +827,13 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    if (o.with_index && (rc = mctx ? bzx_mctx_keep_index(mctx, 1) : BZX_OK) == BZX_OK) rc = bzx_ctx_keep_index(ctx, 1);
+    if (rc) {
+        fprintf(stderr, "bzx: --with-index: %s\n", bzx_strerror(rc));
+        bzx_mctx_destroy(mctx);
+        bzx_ctx_destroy(ctx);
+        return 2;
+    }
     int ret = 0;
     std::vector<Pending> pend;
     size_t pend_bytes = 0;
@@ -804,9 +874,14 @@ int main(int argc, char **argv)
             pend.push_back(std::move(p));
             continue;
         }
-        const int r = o.mode == ZIP ? do_zip(o, ctx, mctx, in, out, f.c_str()) : do_unzip(o, ctx, in, nullptr, out, f.c_str());
+        KeptIndex kept;
+        const int r = o.mode == ZIP ? do_zip(o, ctx, mctx, in, out, f.c_str(), o.with_index ? &kept : nullptr)
+                                    : do_unzip(o, ctx, in, nullptr, out, f.c_str());
         if (!std_in) fclose(in);
-        ret |= finish_file(o, out, oname, f, r);
+        const int done = finish_file(o, out, oname, f, r);
+        ret |= done;
+        // the index only beside a .bz2 that closed cleanly; a failure here leaves the .bz2 and costs the exit status
+        if (o.with_index && !done) ret |= write_bzxi(o, oname + ".bzxi", kept.e.data(), kept.info);
     }
     ret |= flush_batch(o, ctx, pend, pend_bytes);
     bzx_mctx_destroy(mctx);
