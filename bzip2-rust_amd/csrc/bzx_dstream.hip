@@ -33,6 +33,8 @@
 //                         before; the verified bytes of a pass travel to page-locked memory beside the kernels of the
 //                         next pass (two staging areas); the host copies from there into the caller's buffer.
 // Only verified bytes leave the device: the copy-back of a pass is sized by the record's verified byte count.
+// Two more modes run on the same windows, scans and rounds: the index (bzx_index_*: nothing is copied back) and salvage
+// (bzx_salvage_*: the walk goes on behind a block that does not verify; its kernels and passes are further down).
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
@@ -304,10 +306,271 @@ __global__ __launch_bounds__(64) void bzx_ds_index_kernel(BzxBatch B, const uint
     }
 }
 
+// ---- salvage (bzx_salvage_*): the walk that goes on after a break ---------------------------------------------------------
+// The rule is in include/bzx.h.  A round decodes its block candidates as every mode does; then
+//   bzx_sv_trial_kernel    sorts them into classes: a candidate that decoded is a TRIAL and goes, in input order, into the
+//                          list the layout places (d_chain); the others (structure, randomised, withheld) get the skip
+//                          status.  No candidate is dropped by position here: whether it lies inside an accepted block is
+//                          known behind the CRCs only.  The price: trials behind a withheld candidate, or inside a block
+//                          the walk then accepts, go through inverse BWT, expansion and CRC for nothing, and the former
+//                          are decoded again with the next window.  That is nothing on a clean input and multiplies the
+//                          work on heavy damage fed in small windows; cutting the list at the first withheld candidate
+//                          would need a class "not looked at yet" and a round that ends early, and is not built.
+//   inverse BWT            unchanged; a trial it refuses keeps a status and gets no place (bzx_sv_layout_kernel skips it,
+//                          where bzx_ds_layout_kernel ends the pass)
+//   per pass               layout, expansion, CRCs as in the index mode, then bzx_sv_verdict_kernel (a verdict per placed
+//                          trial) and bzx_sv_walk_kernel: one lane takes the walk's state (DsSvState, a kernel argument;
+//                          the host keeps it between passes and windows and never looks into the window) over the round's
+//                          candidates up to the first trial that has no verdict yet, and leaves entries, closed gaps and
+//                          the new state in tables of fixed size that travel back with the record.   [1 synchronisation]
+// st.P is the bit behind the last accepted block or footer (where a gap opens), st.S the first bit not examined yet
+// (where the next window's carry starts): S runs ahead of P over failed candidates and over input that holds no magic,
+// so the carry stays below DS_CARRY_MAX however long the damage is.  Both keep the last 47 bits of a window, in which a
+// magic may straddle into the next.
+enum { SV_EOS = 0, SV_TRIAL, SV_WITHHOLD, SV_FAIL_STRUCTURE, SV_FAIL_RANDOMISED };     // DsSvCand.cls
+enum { SV_PENDING = 0, SV_GOOD, SV_BAD_CRC, SV_BAD_IBWT };                             // verdict of a trial
+
+struct DsSvCand {                  // one candidate of the round
+    uint32_t slab;                 // host: slab of a block candidate
+    uint32_t cls;                  // trial kernel: SV_*
+    uint32_t trial;                // trial kernel: its place in the trial list (cls == SV_TRIAL)
+    uint32_t pad_;
+};
+
+struct DsSvEnt {                   // an accepted block, as the host appends it
+    uint64_t bit, out_off;
+    uint32_t out_len, crc, img_bits, stream, level, pad_;
+};
+
+struct DsSvState {
+    uint64_t P, S;                 // see above (bits of the whole input)
+    uint64_t out_off;              // bytes of the entries so far
+    bzx_gap gap;                   // the open gap (gap_open), bit_hi not yet known
+    uint32_t gap_open;
+    uint32_t level;
+    uint32_t between;              // behind a footer that no header followed
+    uint32_t clean;                // the stream's header was read and no gap was opened or recorded since
+    uint32_t comb;                 // fold of the stream's entry CRCs
+    uint32_t streams;              // end-of-stream markers passed
+    uint32_t k;                    // candidates of the round the walk is through (between the passes of a round)
+    uint32_t pad_;
+};
+
+struct DsSvRec {                   // what the host reads of a salvage pass
+    DsSvState st;                  // walk
+    uint64_t bytes;                // layout: bytes placed in the staging area
+    uint32_t ntrial;               // trial kernel: trials of the round
+    uint32_t pass_j0, placed;      // layout: first trial of this pass, trials placed or skipped so far
+    uint32_t nent, ngap;           // walk: entries and closed gaps of this pass
+    uint32_t stop;                 // walk: DS_STOP_GO or DS_STOP_WITHHELD
+    uint32_t round_done;           // walk: through all candidates of the round (or withheld)
+    uint32_t pad_;
+};
+
+// cand[c0, c1): the round's candidates; svc[k - c0].slab: where block candidate k was decoded.
+__global__ __launch_bounds__(64) void bzx_sv_trial_kernel(BzxBatch B, uint64_t wlen, uint64_t base_bit, uint32_t final,
+                                                         const uint64_t *__restrict__ cand, uint32_t c0, uint32_t c1,
+                                                         DsSvCand *__restrict__ svc, uint32_t *__restrict__ trials,
+                                                         uint32_t *__restrict__ verdict, DsSvRec *__restrict__ rec)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint64_t wbits = wlen * 8;
+    uint32_t nt = 0;
+    for (uint32_t base = c0; base < c1; base += 64) {
+        const uint32_t k = base + lane;
+        const bool valid = k < c1;
+        const uint64_t pos = valid ? cand[k] : 1ull;
+        uint32_t cls = SV_EOS, slab = 0;
+        if (valid && !(pos & 1u)) {
+            slab = svc[k - c0].slab;
+            const uint32_t st = B.blk[slab].status;
+            const uint64_t end = B.blk[slab].bits, rel = (pos >> 1) - base_bit;
+            // the reader went past the window's end (it reads zeros there), or stopped on an error within reach of it
+            const bool ran_off = end > wbits || (st && end + 64 > wbits);
+            if (ran_off && !final && wbits - rel < DS_BLOCK_BOUND * 8) cls = SV_WITHHOLD;
+            else if (st & BZX_ST_DC_RANDOMISED) cls = SV_FAIL_RANDOMISED;
+            else if (st || ran_off) cls = SV_FAIL_STRUCTURE;
+            else cls = SV_TRIAL;
+            if (cls != SV_TRIAL) B.blk[slab].status = st | DC_SKIP;
+        }
+        const unsigned long long m = __ballot(cls == SV_TRIAL);
+        const uint32_t t = nt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (cls == SV_TRIAL) {
+            trials[t] = slab;
+            verdict[t] = SV_PENDING;
+        }
+        if (valid) {
+            svc[k - c0].cls = cls;
+            svc[k - c0].trial = t;
+        }
+        nt += (uint32_t)__popcll(m);
+    }
+    if (lane == 0) {
+        rec->ntrial = nt;
+        rec->pass_j0 = 0;
+        rec->placed = 0;
+        rec->bytes = 0;
+    }
+}
+
+// bzx_ds_layout_kernel over the trial list, except that a trial the inverse BWT refused takes no room and does not end
+// the pass.
+__global__ __launch_bounds__(64) void bzx_sv_layout_kernel(BzxBatch B, const uint32_t *__restrict__ trials, uint8_t *stage,
+                                                          uint64_t stage_cap, BzxDcDst *__restrict__ dst,
+                                                          DsSvRec *__restrict__ rec)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t nt = rec->ntrial, j0 = rec->placed;
+    for (uint32_t b = lane; b < B.nblk; b += 64) dst[b] = BzxDcDst{nullptr, 0};
+    __syncthreads();                                   // the places below are written after every "no place"
+    uint64_t off = 0;
+    uint32_t placed = j0;
+    bool stop = false;
+    for (uint32_t base = j0; base < nt && !stop; base += 64) {
+        const uint32_t j = base + lane;
+        const bool valid = j < nt;
+        const uint32_t b = valid ? trials[j] : 0u;
+        const bool bad = valid && B.blk[b].status;
+        const uint64_t size = valid && !bad ? B.blk[b].pack_word : 0ull;
+        const uint64_t x = bzx_wave_incl_sum64(size);
+        const bool fits = valid && off + x <= stage_cap;
+        const unsigned long long nf = __ballot(valid && !fits);
+        const uint32_t cnt = nt - base < 64u ? nt - base : 64u;
+        const uint32_t first = nf ? (uint32_t)__ffsll(nf) - 1u : 64u;
+        const uint32_t take = first < cnt ? first : cnt;
+        if (lane < take && !bad) dst[b] = BzxDcDst{stage + off + (x - size), size};
+        const uint64_t gx = __shfl(x, (int)(take ? take - 1u : 0u));
+        if (take) off += gx;
+        placed += take;
+        if (take < cnt) stop = true;
+    }
+    if (lane == 0) {
+        rec->pass_j0 = j0;
+        rec->placed = placed;
+        rec->bytes = off;
+    }
+}
+
+__global__ __launch_bounds__(64) void bzx_sv_verdict_kernel(BzxBatch B, const uint32_t *__restrict__ trials,
+                                                           const uint32_t *__restrict__ got, uint32_t *__restrict__ verdict,
+                                                           const DsSvRec *__restrict__ rec)
+{
+    const uint32_t j1 = rec->placed;
+    for (uint32_t j = rec->pass_j0 + threadIdx.x; j < j1; j += 64) {
+        const uint32_t b = trials[j];
+        verdict[j] = B.blk[b].status ? SV_BAD_IBWT : got[b] == B.blk[b].crc ? SV_GOOD : SV_BAD_CRC;
+    }
+}
+
+// ent[R], gaps[2 R]: a round has at most R block candidates and R end-of-stream candidates (the host cuts it so), and a
+// candidate closes or records at most one gap (a marker records COMBINED_CRC only where it had no other gap to settle).
+__global__ __launch_bounds__(64) void bzx_sv_walk_kernel(BzxBatch B, const uint8_t *__restrict__ z, uint64_t wlen,
+                                                        uint64_t base_bit, uint32_t final,
+                                                        const uint64_t *__restrict__ cand, uint32_t c0, uint32_t c1,
+                                                        const DsSvCand *__restrict__ svc,
+                                                        const uint32_t *__restrict__ verdict, DsSvState st,
+                                                        DsSvEnt *__restrict__ ent, bzx_gap *__restrict__ gaps,
+                                                        DsSvRec *__restrict__ rec)
+{
+    if (threadIdx.x) return;
+    const uint64_t wbits = wlen * 8;
+    const uint32_t placed = rec->placed;
+    uint32_t nent = 0, ngap = 0, stop = DS_STOP_GO;
+    // an accepted block or a marker at bit b: the open gap closes there, or what lies between P and b is one
+    auto settle = [&](uint64_t b) {
+        if (st.gap_open) {
+            st.gap.bit_hi = b;
+            gaps[ngap++] = st.gap;
+            st.gap_open = 0;
+        } else if (b > st.P) {
+            gaps[ngap++] = bzx_gap{st.P, b, st.out_off, 0u, BZX_GAP_NO_MAGIC | (st.between ? BZX_GAP_HEADER : 0u)};
+            st.clean = 0;
+        }
+    };
+    uint32_t k = st.k;
+    for (; c0 + k < c1; k++) {
+        const uint64_t pos = cand[c0 + k];
+        const uint64_t bit = pos >> 1, rel = bit - base_bit;
+        if (bit < st.S) continue;                                         // inside an accepted block or a footer
+        if (pos & 1u) {
+            const uint64_t after = (rel + 80 + 7) / 8;                    // first byte behind the footer
+            if (!final && after + 14 > wlen) {                            // is it a stream header?  not known yet
+                st.S = bit;
+                stop = DS_STOP_WITHHELD;
+                break;
+            }
+            if (rel + 80 > wbits) continue;                               // cut off by the end of the input: not there
+            settle(bit);
+            if (st.clean) {
+                const uint64_t fb = (rel + 48) >> 3;
+                uint64_t fv = 0;
+                for (uint32_t q = 0; q < 5; q++) fv = (fv << 8) | ds_byte(z, wlen, fb + q);
+                const uint32_t stored = (uint32_t)((fv << ((rel + 48) & 7u)) >> 8);
+                if (stored != st.comb) gaps[ngap++] = bzx_gap{bit, bit, st.out_off, 0u, BZX_GAP_COMBINED_CRC};
+            }
+            st.streams++;
+            st.comb = 0;
+            const uint32_t next = after + 14 <= wlen ? bzx_bzh_level(z + after) : 0u;
+            st.level = next ? next : 9u;
+            st.between = next ? 0u : 1u;
+            st.clean = next ? 1u : 0u;
+            st.P = st.S = base_bit + after * 8 + (next ? 32u : 0u);
+            continue;
+        }
+        const DsSvCand c = svc[k];
+        if (c.cls == SV_WITHHOLD) {                                       // more input may complete it
+            st.S = bit;
+            stop = DS_STOP_WITHHELD;
+            break;
+        }
+        uint32_t why = c.cls == SV_FAIL_RANDOMISED ? BZX_GAP_RANDOMISED : BZX_GAP_STRUCTURE;
+        if (c.cls == SV_TRIAL) {
+            if (c.trial >= placed) break;                                 // its verdict comes with a later pass
+            const uint32_t v = verdict[c.trial];
+            const BzxBlock &d = B.blk[c.slab];
+            if (v == SV_GOOD && d.n <= 100000u * st.level) {
+                settle(bit);
+                DsSvEnt e;
+                e.bit = bit;
+                e.out_off = st.out_off;
+                e.out_len = (uint32_t)d.pack_word;
+                e.crc = d.crc;
+                e.img_bits = (uint32_t)(d.bits - d.out_bit);
+                e.stream = st.streams;
+                e.level = st.level;
+                e.pad_ = 0;
+                ent[nent++] = e;
+                st.out_off += e.out_len;
+                st.comb = crc_fold(st.comb, d.crc);
+                st.between = 0;
+                st.P = st.S = bit + e.img_bits;
+                continue;
+            }
+            why = v == SV_BAD_CRC && d.n <= 100000u * st.level ? BZX_GAP_BLOCK_CRC : BZX_GAP_STRUCTURE;
+        }
+        if (!st.gap_open) {
+            st.gap = bzx_gap{st.P, 0, st.out_off, 0u, st.between ? BZX_GAP_HEADER : 0u};
+            st.gap_open = 1;
+            st.clean = 0;
+        }
+        st.gap.why |= why;
+        st.gap.candidates++;
+        st.S = bit + 1;
+    }
+    const uint32_t round_done = (c0 + k >= c1 || stop != DS_STOP_GO) ? 1u : 0u;
+    st.k = round_done ? 0u : k;
+    rec->st = st;
+    rec->nent = nent;
+    rec->ngap = ngap;
+    rec->stop = stop;
+    rec->round_done = round_done;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 struct bzx_index {
     bzx_dstream *s = nullptr;
     std::vector<bzx_index_entry> entries;
+    std::vector<bzx_gap> gaps;                             // (salvage)
 };
 
 struct DsSlot {                    // an output staging area: the verified bytes of one pass
@@ -366,6 +629,19 @@ struct bzx_dstream {
     DevMem<uint32_t> d_meta;
     DevMem<DsIxRec> d_ix;
     PinMem<DsIxRec> h_ix;
+    // salvage mode (bzx_salvage_*): the index mode's memory, with the tables of the salvage kernels in place of d_meta / d_ix
+    bool salvage = false;
+    DsSvState sv = {};                 // the walk's state between passes and windows
+    uint32_t sv_c0 = 0, sv_c1 = 0;     // the round's candidates
+    DevMem<DsSvCand> d_svc;
+    PinMem<DsSvCand> h_svc;
+    DevMem<uint32_t> d_verdict;
+    DevMem<DsSvEnt> d_ent;
+    PinMem<DsSvEnt> h_ent;
+    DevMem<bzx_gap> d_gap;
+    PinMem<bzx_gap> h_gap;
+    DevMem<DsSvRec> d_svrec;
+    PinMem<DsSvRec> h_svrec;
 };
 
 extern "C" void bzx_dstream_end(bzx_dstream *s)
@@ -392,7 +668,7 @@ extern "C" void bzx_dstream_end(bzx_dstream *s)
 }
 
 // index: the stream of a bzx_index -- one output staging area, none on the host, and the tables of the entries.
-static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bzx_dstream **out)
+static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bool salvage, bzx_dstream **out)
 {
     if (!ctx || !out) return BZX_E_PARAM;
     *out = nullptr;
@@ -425,7 +701,14 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bzx_dstream **ou
         ok = dmal(s->d_in[i], s->in_cap) && (index && i ? true : dmal(s->d_stage[i], DS_STAGE_BYTES)) &&
              (index || hmal(s->h_stage[i], DS_STAGE_BYTES)) &&
              hipEventCreateWithFlags(&s->ev_d2h[i], hipEventDisableTiming) == hipSuccess;
-    if (index)                                               // (zeroed: a pass copies the whole R-entry table back and
+    if (salvage)                                             // (zeroed as d_ix below)
+        ok = ok && dmal(s->d_svc, 2 * R * sizeof(DsSvCand)) && hmal(s->h_svc, 2 * R * sizeof(DsSvCand)) &&
+             dmal(s->d_verdict, R * 4) && dmal(s->d_ent, R * sizeof(DsSvEnt)) && hmal(s->h_ent, R * sizeof(DsSvEnt)) &&
+             dmal(s->d_gap, 2 * R * sizeof(bzx_gap)) && hmal(s->h_gap, 2 * R * sizeof(bzx_gap)) &&
+             dmal(s->d_svrec, sizeof(DsSvRec)) && hmal(s->h_svrec, sizeof(DsSvRec)) &&
+             hipMemset(s->d_ent, 0, R * sizeof(DsSvEnt)) == hipSuccess &&
+             hipMemset(s->d_gap, 0, 2 * R * sizeof(bzx_gap)) == hipSuccess;
+    else if (index)                                          // (zeroed: a pass copies the whole R-entry table back and
         ok = ok && dmal(s->d_meta, R * 4) &&       // writes the entries of the blocks it placed only)
              dmal(s->d_ix, R * sizeof(DsIxRec)) && hmal(s->h_ix, R * sizeof(DsIxRec)) &&
              hipMemset(s->d_ix, 0, R * sizeof(DsIxRec)) == hipSuccess;
@@ -443,6 +726,7 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bzx_dstream **ou
         ctx->err = "bzx_dstream_begin: device or pinned allocation failed";
         return BZX_E_NOMEM;
     }
+    s->salvage = salvage;
     s->info.slabs = s->R;
     s->info.device_bytes = dev;
     s->info.pinned_bytes = pin;
@@ -453,7 +737,7 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bzx_dstream **ou
 
 extern "C" int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **out)
 {
-    return ds_begin(ctx, max_chunk, false, out);
+    return ds_begin(ctx, max_chunk, false, false, out);
 }
 
 extern "C" int bzx_dstream_get_info(const bzx_dstream *s, bzx_dstream_info *out)
@@ -541,11 +825,142 @@ static void ds_round_complete(bzx_dstream *s)
     }
 }
 
+// ---- salvage passes ----------------------------------------------------------------------------------------------------
+// The candidates of the window are used up: the rest of a window whose scan was cut short, the next window, or -- behind
+// the last byte of the input -- the end of the walk.
+static void sv_used_up(bzx_dstream *s)
+{
+    DsSvState &v = s->sv;
+    if (s->scan_to < s->wlen) {                              // (the scan finds every magic that starts before scan_to)
+        v.S = std::max(v.S, (s->wbase + s->scan_to) * 8);
+        s->chain_bit = v.S;
+        s->need_scan = true;
+        return;
+    }
+    const uint64_t end = (s->wbase + s->wlen) * 8;
+    if (!s->wfinal) {                                        // a magic may start in the last 47 bits
+        if (end >= 47) v.S = std::max(v.S, end - 47);
+        s->chain_bit = v.S;
+        s->need_more = true;
+        return;
+    }
+    if (v.gap_open) {
+        v.gap.bit_hi = end;
+        if (!v.between) v.gap.why |= BZX_GAP_TRUNCATED;
+        s->ix->gaps.push_back(v.gap);
+        v.gap_open = 0;
+    } else if (!v.between) {
+        s->ix->gaps.push_back(bzx_gap{v.P, end, v.out_off, 0u, BZX_GAP_TRUNCATED});
+    }
+    s->finished = true;
+}
+
+// ds_pass of the salvage mode: a new round decodes its candidates and sorts them into classes; every pass places, expands
+// and checks the next trials and lets the walk go on over the round's candidates.  ONE synchronisation.
+static int sv_pass(bzx_dstream *s)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    BzxBatch &B = ctx->B;
+    const bool fresh = !s->rd_active;
+    const uint32_t final = s->wfinal ? 1u : 0u;
+    if (fresh) {
+        if (s->need_scan) {
+            const int rc = ds_scan(s);
+            if (rc) return rc;
+        }
+        while (s->ci < s->ncand && (s->h_cand[s->ci] >> 1) < s->chain_bit) s->ci++;
+        if (s->ci == s->ncand) {
+            sv_used_up(s);
+            return BZX_OK;
+        }
+        const uint32_t c0 = s->ci;
+        uint32_t c1 = c0, nb = 0, ne = 0;
+        for (; c1 < s->ncand; c1++) {
+            if (s->h_cand[c1] & 1u) {
+                if (ne == s->R) break;
+                ne++;
+                continue;
+            }
+            if (nb == s->R) break;
+            s->h_svc[c1 - c0].slab = nb;
+            s->h_src[nb++] = BzxDcSrc{s->wptr, s->wlen, (s->h_cand[c1] >> 1) - s->wbase * 8};
+        }
+        s->ci = c1;
+        s->sv_c0 = c0;
+        s->sv_c1 = c1;
+        s->rd_nb = nb;
+        s->sv.k = 0;
+        B.nblk = nb;
+        B.blk_first = 0;
+        B.blk_step = 1;
+        (void)hipEventRecord(ctx->ev[5], st);
+        if (nb) {
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_src, s->h_src, nb * sizeof(BzxDcSrc), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_svc, s->h_svc, (c1 - c0) * sizeof(DsSvCand), hipMemcpyHostToDevice, st));
+            bzx_launch_dc_decode(B, s->d_src, st);
+        }
+        hipLaunchKernelGGL(bzx_sv_trial_kernel, dim3(1), dim3(64), 0, st, B, s->wlen, s->wbase * 8, final, s->d_cand.get(), c0, c1,
+                           s->d_svc.get(), s->d_chain.get(), s->d_verdict.get(), s->d_svrec.get());
+        if (nb) bzx_launch_dc_ibwt(B, ctx->d_in, st);
+    } else {
+        B.nblk = s->rd_nb;
+        B.blk_first = 0;
+        B.blk_step = 1;
+        (void)hipEventRecord(ctx->ev[5], st);
+    }
+    const uint32_t nb = s->rd_nb;
+    if (nb) {
+        hipLaunchKernelGGL(bzx_sv_layout_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_stage[0].get(),
+                           (uint64_t)DS_STAGE_BYTES, s->d_dst.get(), s->d_svrec.get());
+        bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
+        bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
+        hipLaunchKernelGGL(bzx_sv_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_got.get(), s->d_verdict.get(),
+                           s->d_svrec.get());
+    }
+    hipLaunchKernelGGL(bzx_sv_walk_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8, final, s->d_cand.get(),
+                       s->sv_c0, s->sv_c1, s->d_svc.get(), s->d_verdict.get(), s->sv, s->d_ent.get(), s->d_gap.get(), s->d_svrec.get());
+    HIP_TRY(ctx, hipGetLastError());
+    // (tables of fixed size: the host reads the first nent / ngap of them, the rest is what begin zeroed or a pass left)
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_ent, s->d_ent, (size_t)s->R * sizeof(DsSvEnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_gap, s->d_gap, (size_t)2 * s->R * sizeof(bzx_gap), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_svrec, s->d_svrec, sizeof(DsSvRec), hipMemcpyDeviceToHost, st));
+    (void)hipEventRecord(ctx->ev[7], st);
+    HIP_TRY(ctx, hipStreamSynchronize(st));                  // the pass's one synchronisation
+    s->info.rounds++;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[7]) == hipSuccess) s->ms += ms;
+    const DsSvRec &r = *s->h_svrec;
+    for (uint32_t j = 0; j < r.nent; j++) {
+        const DsSvEnt &x = s->h_ent[j];
+        bzx_index_entry e;
+        memset(&e, 0, sizeof(e));
+        e.bit = x.bit;
+        e.out_off = x.out_off;
+        e.out_len = x.out_len;
+        e.crc = x.crc;
+        e.img_bits = x.img_bits;
+        e.stream = x.stream;
+        e.level = (uint8_t)x.level;
+        s->ix->entries.push_back(e);
+    }
+    s->ix->gaps.insert(s->ix->gaps.end(), s->h_gap.get(), s->h_gap.get() + r.ngap);
+    s->sv = r.st;
+    s->chain_bit = r.st.S;
+    s->info.nblk += r.nent;
+    s->info.out_bytes = r.st.out_off;
+    s->info.nstreams = r.st.streams;
+    s->rd_active = !r.round_done;
+    if (r.round_done && r.stop == DS_STOP_WITHHELD) s->need_more = true;
+    return BZX_OK;
+}
+
 // One pass: a new round (decode, chain, inverse BWT) when no decoded chain block waits in the slabs, then layout,
 // expansion, CRCs and verdict into the staging area `q`, the record, ONE synchronisation, and the copy-back of the
 // verified bytes on its own stream.
 static int ds_pass(bzx_dstream *s, uint32_t q)
 {
+    if (s->salvage) return sv_pass(s);
     bzx_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     BzxBatch &B = ctx->B;
@@ -684,6 +1099,20 @@ static int ds_promote(bzx_dstream *s)
     s->acc = a ^ 1u;
     s->acc_fill = 0;
     s->info.windows++;
+    if (!s->started && s->salvage) {                         // the start of the walk (include/bzx.h)
+        s->started = true;
+        s->sv = DsSvState{};
+        s->sv.level = s->info.in_bytes >= 4 ? bzx_bzh_level(s->head) : 0u;
+        if (s->sv.level) {
+            s->sv.P = s->sv.S = 32;
+            s->sv.clean = 1;
+        } else {
+            s->sv.level = 9;
+            s->sv.gap = bzx_gap{0, 0, 0, 0u, BZX_GAP_HEADER};
+            s->sv.gap_open = 1;
+        }
+        s->chain_bit = s->sv.S;
+    }
     if (!s->started) {
         s->started = true;
         if (s->wlen < 14) {
@@ -822,13 +1251,13 @@ extern "C" void bzx_index_end(bzx_index *ix)
     delete ix;
 }
 
-extern "C" int bzx_index_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out)
+static int ix_begin(bzx_ctx *ctx, size_t max_chunk, bool salvage, bzx_index **out)
 {
     if (!ctx || !out) return BZX_E_PARAM;
     *out = nullptr;
     bzx_index *ix = new (std::nothrow) bzx_index();
     if (!ix) return BZX_E_NOMEM;
-    const int rc = ds_begin(ctx, max_chunk, true, &ix->s);
+    const int rc = ds_begin(ctx, max_chunk, true, salvage, &ix->s);
     if (rc) {
         delete ix;
         return rc;
@@ -836,6 +1265,16 @@ extern "C" int bzx_index_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out)
     ix->s->ix = ix;
     *out = ix;
     return BZX_OK;
+}
+
+extern "C" int bzx_index_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out)
+{
+    return ix_begin(ctx, max_chunk, false, out);
+}
+
+extern "C" int bzx_salvage_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out)
+{
+    return ix_begin(ctx, max_chunk, true, out);
 }
 
 extern "C" int bzx_index_feed(bzx_index *ix, const uint8_t *bz2, size_t len, int final, size_t *consumed, int *done)
@@ -924,4 +1363,129 @@ extern "C" int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t l
     bzx_index_end(ix);
     if (rc) ctx->err = why;
     return rc;
+}
+
+// ---- bzx_salvage_*: the calls over a whole buffer ---------------------------------------------------------------------------
+extern "C" int bzx_index_get_gaps(const bzx_index *ix, const bzx_gap **gaps, uint64_t *ngaps)
+{
+    if (!ix || !ix->s || !ix->s->ctx || !gaps || !ngaps) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(ix->s->ctx->api_mu);
+    *gaps = ix->gaps.data();
+    *ngaps = ix->gaps.size();
+    return BZX_OK;
+}
+
+// begin, a loop over feed, and the lists as vectors.
+static int sv_build(bzx_ctx *ctx, const uint8_t *bz2, size_t len, std::vector<bzx_index_entry> &entries, bzx_index_info *info,
+                    std::vector<bzx_gap> &gaps)
+{
+    bzx_index *ix = nullptr;
+    int rc = bzx_salvage_begin(ctx, std::min<size_t>(std::max<size_t>(len, DS_MIN_CHUNK), (size_t)64 << 20), &ix);
+    if (rc) return rc;
+    size_t pos = 0;
+    int done = 0;
+    while (!rc && !(done && pos == len)) {
+        size_t used = 0;
+        rc = bzx_index_feed(ix, bz2 + pos, len - pos, 1, &used, &done);
+        pos += used;
+        if (!rc && !used && !done) {                         // (a final feed consumes or finishes)
+            ctx->err = "bzx_salvage: the feed loop made no progress";
+            rc = BZX_E_STATE;
+        }
+    }
+    const std::string why = ctx->err;
+    if (!rc) {
+        try {
+            const bzx_index_entry *e = nullptr;
+            const bzx_gap *g = nullptr;
+            uint64_t ng = 0;
+            rc = bzx_index_get(ix, &e, info);
+            if (!rc) rc = bzx_index_get_gaps(ix, &g, &ng);
+            if (!rc) {
+                entries.assign(e, e + info->nblk);
+                gaps.assign(g, g + ng);
+            }
+        } catch (const std::bad_alloc &) {
+            rc = BZX_E_NOMEM;
+        }
+    }
+    bzx_index_end(ix);
+    if (rc) ctx->err = rc == BZX_E_NOMEM && why.empty() ? "out of host memory" : why;
+    return rc;
+}
+
+static int sv_gaps_out(bzx_ctx *ctx, const std::vector<bzx_gap> &v, bzx_gap *gaps, uint64_t cap_gaps, uint64_t *ngaps)
+{
+    *ngaps = v.size();
+    const uint64_t k = std::min<uint64_t>(v.size(), cap_gaps);
+    if (k) memcpy(gaps, v.data(), (size_t)k * sizeof(bzx_gap));
+    if (v.size() <= cap_gaps) return BZX_OK;
+    ctx->err = "bzx_salvage: more gaps than cap_gaps";
+    return BZX_E_OUTBUF;
+}
+
+extern "C" int bzx_salvage_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries,
+                                        uint64_t cap_entries, bzx_index_info *info, bzx_gap *gaps, uint64_t cap_gaps,
+                                        uint64_t *ngaps)
+{
+    if (!ctx || !info || !ngaps || (len && !bz2) || (cap_entries && !entries) || (cap_gaps && !gaps)) return BZX_E_PARAM;
+    memset(info, 0, sizeof(*info));
+    *ngaps = 0;
+    std::vector<bzx_index_entry> e;
+    std::vector<bzx_gap> g;
+    int rc = sv_build(ctx, bz2, len, e, info, g);
+    if (rc) return rc;
+    rc = sv_gaps_out(ctx, g, gaps, cap_gaps, ngaps);
+    const uint64_t k = std::min<uint64_t>(e.size(), cap_entries);
+    if (k) memcpy(entries, e.data(), (size_t)k * sizeof(bzx_index_entry));
+    if (e.size() > cap_entries) {
+        ctx->err = "bzx_salvage_build_buffer: more blocks than cap_entries";
+        rc = BZX_E_OUTBUF;
+    }
+    return rc;
+}
+
+extern "C" int bzx_salvage_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len,
+                                  bzx_gap *gaps, uint64_t cap_gaps, uint64_t *ngaps)
+{
+    if (!ctx || !out_len || !ngaps || (len && !bz2) || (cap && !out) || (cap_gaps && !gaps)) return BZX_E_PARAM;
+    *out_len = 0;
+    *ngaps = 0;
+    std::vector<bzx_index_entry> e;
+    std::vector<bzx_gap> g;
+    bzx_index_info info;
+    memset(&info, 0, sizeof(info));
+    int rc = sv_build(ctx, bz2, len, e, &info, g);
+    if (rc) return rc;
+    const int rc_gaps = sv_gaps_out(ctx, g, gaps, cap_gaps, ngaps);
+    *out_len = (size_t)info.out_bytes;
+    const uint64_t want = std::min<uint64_t>(info.out_bytes, cap);
+    if (want) {
+        // The range reader asks for 8 bytes behind a block's image (bzx_index_span); the last blocks of a truncated input
+        // may not have them.  Those are read in a second call, over a copy of the input's tail with 8 zero bytes appended.
+        uint64_t k = e.size();
+        while (k > 0 && (e[k - 1].bit + e[k - 1].img_bits + 7) / 8 + 8 > len) k--;
+        const uint64_t head = k < e.size() ? std::min<uint64_t>(e[k].out_off, want) : want;
+        size_t got = 0;
+        if (head) rc = bzx_decompress_range_buffer(ctx, bz2, len, 0, e.data(), e.size(), 0, head, out, &got);
+        if (!rc && want > head) {
+            const uint64_t base = e[k].bit / 8;
+            std::vector<uint8_t> tail;
+            try {
+                tail.assign(bz2 + base, bz2 + len);
+                tail.resize(tail.size() + 8, 0);
+            } catch (const std::bad_alloc &) {
+                ctx->err = "out of host memory";
+                return BZX_E_NOMEM;
+            }
+            rc = bzx_decompress_range_buffer(ctx, tail.data(), tail.size(), base, e.data(), e.size(), head, want - head, out + head,
+                                             &got);
+        }
+        if (rc) return rc;
+    }
+    if (info.out_bytes > cap) {
+        ctx->err = "bzx_salvage_buffer: the salvaged data needs " + std::to_string(info.out_bytes) + " bytes";
+        return BZX_E_OUTBUF;
+    }
+    return rc_gaps;
 }

@@ -406,6 +406,75 @@ void bzx_index_end(bzx_index *ix);
 int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries, uint64_t cap_entries,
                            bzx_index_info *info);
 /*
+ * Salvage: the index of every intact block of a DAMAGED .bz2 (the counterpart of bzip2recover), and the gaps between
+ * them.  A salvage index is an ordinary entry list: bzx_index_span, bzx_decompress_range_* and _ranges_* read through it
+ * unchanged, and hold every block against its entry again before a byte leaves.  Damage is the expected case: these
+ * calls return BZX_OK whatever the data (an empty input: 0 entries); BZX_E_PARAM / _STATE / _NOMEM / _HIP keep their
+ * meaning, BZX_E_OUTBUF says that cap_entries, cap_gaps or cap is too small (the counts, or *out_len, then hold what is
+ * needed and the first cap items are written).
+ *
+ * A block magic at bit b VERIFIES when the block decoded from b keeps its reader inside the input, has no structural
+ * error, has its randomised bit clear, is no longer than 100000 x level, passes the inverse BWT and expands to bytes
+ * whose CRC is the stored one: the checks of a block of bzx_index_*.
+ *
+ * The walk keeps a position P, a level, a count of end-of-stream markers and at most one open gap:
+ *   start     "BZh1".."BZh9" at byte 0: level = the digit, P = 32.  Otherwise level = 9, P = 0 and a gap opens at bit 0
+ *             with HEADER (a stream is assumed).
+ *   magics    at bits >= P, in ascending order; those below P lie inside an accepted block or a footer and are ignored.
+ *   verifies  an open gap closes at b; with none open and b > P the gap [P, b) is recorded (NO_MAGIC, and HEADER when the
+ *             walk was between streams).  The block becomes an entry (bit = b, out_off = the running sum, stream = markers
+ *             passed, level = the walk's; a block accepted between streams assumes a stream).  P = b + img_bits.
+ *   does not  a gap opens at P unless one is open (with HEADER when the walk is between streams), takes the reason into
+ *             `why` and counts the candidate.  P stays: the end of a block that did not verify is not trusted -- a
+ *             damaged payload usually still decodes, to an end several blocks further on -- so every candidate behind it is
+ *             tried as well, and the only test by position is "behind the last ACCEPTED block".
+ *   marker    an end-of-stream magic at b whose 80 bits lie inside the input: an open gap closes at b, or [P, b) is
+ *             recorded as above.  If the stream's header was read and no gap was opened or recorded since, the stored
+ *             combined CRC is held against the fold of the stream's entries; a mismatch records the zero-length gap
+ *             {b, b, COMBINED_CRC}.  The marker count and nstreams go up, P = the next byte boundary behind the footer.
+ *             "BZh1".."BZh9" there with at least 14 bytes left: level = the digit, P += 32.  Otherwise level = 9 and the
+ *             walk is between streams (trailing bytes without a magic are no gap).  A marker cut off by the end of the
+ *             input counts as not there.
+ *   end       at `final` an open gap closes at 8 x in_bytes and gains TRUNCATED when the walk is inside a stream; with
+ *             none open and the walk inside a stream the gap [P, end) is recorded with TRUNCATED, also when it is empty.
+ * Decisions this leaves open: an input without a header (an empty one included) is inside an assumed stream, so it ends
+ * in a gap with HEADER | TRUNCATED; a block longer than its level allows counts as STRUCTURE even when its CRC matches;
+ * a failed candidate between streams does not assume a stream (no TRUNCATED at the end).  An entry whose image ends
+ * within 8 bytes of the end of a truncated input needs those bytes for a range read (bzx_index_span: byte_hi): give the
+ * range reader the input followed by 8 zero bytes; bzx_salvage_buffer and bzx --recover do (over a copy of the input from
+ * the first such block on: a few blocks at most).
+ * On an undamaged input entries and info are bzx_index_build_buffer's, field for field, and there is no gap.
+ *
+ * bzx_salvage_begin: a third mode of the bzx_dstream_* machine; feed / get / end are bzx_index_feed / _get / _end.
+ * *done becomes 1 only at `final`: the walk goes on looking behind an end-of-stream marker.  Device memory is fixed at
+ * begin: that of bzx_index_begin, plus per-round tables of the candidates' classes, the trials' verdicts, entries and
+ * gaps (a few dozen bytes per slab).  Host synchronisations: one per scan, one per pass, none per block, candidate or
+ * gap.  Every candidate of a round that decodes is a trial: inverse BWT, expansion into the staging area, CRC; the walk
+ * runs on the device behind the CRCs and reads the footer CRC and the next header there.  Only the gap list on the host
+ * grows with the damage.
+ * bzx_salvage_buffer: a salvage index, then bzx_decompress_range_buffer(.., 0, out_bytes, ..) over it: the good blocks
+ * are decoded a second time, and the bytes leave through the range reader's checks.  Delivering bytes in the salvage pass
+ * itself is deliberately not built.
+ */
+#define BZX_GAP_STRUCTURE    1u   /* a block magic in the gap starts a block that does not decode (damage, longer than its
+                                     level allows, inverse BWT refused, reader passes the end of the input) */
+#define BZX_GAP_BLOCK_CRC    2u   /* ... a block that decodes, whose computed CRC is not the stored one */
+#define BZX_GAP_RANDOMISED   4u   /* ... a block with the randomised bit set (refused as everywhere in this library) */
+#define BZX_GAP_NO_MAGIC     8u   /* neither a block nor an end-of-stream marker where the stream continues */
+#define BZX_GAP_TRUNCATED   16u   /* the input ends inside a stream */
+#define BZX_GAP_COMBINED_CRC 32u  /* zero-length gap at an end-of-stream marker: stored combined CRC != the blocks' */
+#define BZX_GAP_HEADER      64u   /* no readable "BZh1".."BZh9" where a stream starts */
+typedef struct { uint64_t bit_lo, bit_hi;   /* input bits [lo, hi) that no entry, header or footer accounts for */
+                 uint64_t out_off;          /* salvaged bytes before the gap (where bytes are missing) */
+                 uint32_t candidates;       /* block magics inside it that did not verify */
+                 uint32_t why; } bzx_gap;   /* 32 bytes */
+int bzx_salvage_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out);   /* feed/get/end: bzx_index_feed/_get/_end */
+int bzx_index_get_gaps(const bzx_index *ix, const bzx_gap **gaps, uint64_t *ngaps);   /* 0 gaps on a plain index */
+int bzx_salvage_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries, uint64_t cap_entries,
+                             bzx_index_info *info, bzx_gap *gaps, uint64_t cap_gaps, uint64_t *ngaps);
+int bzx_salvage_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len,
+                       bzx_gap *gaps, uint64_t cap_gaps, uint64_t *ngaps);
+/*
  * The index straight from compression: with keeping switched on, a compression call leaves the index of the stream it
  * wrote, so the first range read needs no decode pass over the library's own output.
  * The rule: after a successful call of an entry point named below, the entries and the bzx_index_info are identical,

@@ -18,6 +18,12 @@
 // --with-index FILE ... (compression) writes FILE.bz2 and FILE.bz2.bzxi in one pass: the library keeps the index while it
 // compresses (bzx_ctx_keep_index / bzx_mctx_keep_index), on the chunked path, with --devices and on the batched path; the
 // index is written after its .bz2 closed cleanly, in the format --index writes.
+// --recover FILE.bz2 ... (the counterpart of bzip2recover) writes FILE.recovered, or standard output with -c: every intact
+// block of a damaged file.  A salvage index (bzx_salvage_begin, fed as --index feeds) says which blocks verify and where the
+// gaps are; the data then comes from bzx_decompress_range_buffer over that index in pieces of at most 256 MiB of output,
+// reading only the bytes of the file each piece needs.  One line per gap goes to standard error.  The input stays.  With
+// --index it also writes FILE.bz2.bzxi (the gaps are not stored): -dc --range then reads the damaged file.  Exit status
+// 0: nothing was lost, 2: something was, 1: trouble.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -40,6 +46,8 @@ struct Opts {
     std::vector<std::string> files;
     std::vector<int> devices;          // --devices: entries of a bzx_mctx for the chunked compression path
     bool index = false, range = false; // --index; --range OFF:LEN
+    bool recover = false;              // --recover
+    bool mode_set = false;             // -z, -d or -t was given
     bool with_index = false;           // --with-index: FILE.bz2.bzxi beside FILE.bz2, from the compressor
     uint64_t range_off = 0, range_len = 0;
     std::string ranges;                // --ranges LIST
@@ -58,6 +66,9 @@ static void help()
          "  --index           write FILE.bzxi, the block index of every FILE (a .bz2), for --range\n"
          "  --range OFF:LEN   with -dc: decoded bytes [OFF, OFF + LEN) of FILE to standard output, through FILE.bzxi\n"
          "  --ranges LIST     with -dc: the same for every OFF:LEN line of the text file LIST, in one call, back to back\n"
+         "  --recover         write every intact block of a damaged FILE.bz2 to FILE.recovered (-c: standard output) and\n"
+         "                    one line per gap to standard error; with --index also FILE.bz2.bzxi for --range;\n"
+         "                    exit status 0: nothing lost, 2: data lost, 1: trouble\n"
          "  --with-index      compress FILE to FILE.bz2 and write FILE.bz2.bzxi in the same pass (not with -c or standard input)\n"
          "With no file, or when a file is -, reads standard input and writes standard output.");
 }
@@ -277,9 +288,11 @@ static int write_bzxi(const Opts &o, const std::string &oname, const bzx_index_e
     return 0;
 }
 
-// FILE.bz2 -> FILE.bz2.bzxi through bzx_index_feed, 64 MiB chunks in page-locked memory as -d reads them.
-static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
+// FILE.bz2 through bzx_index_feed, 64 MiB chunks in page-locked memory as -d reads them: the index (--index), or the
+// salvage index (--recover).  -> 0 and the open index, or 1 after a message.
+static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool salvage, bzx_index **out)
 {
+    *out = nullptr;
     const char *name = f.c_str();
     FILE *in = fopen(name, "rb");
     if (!in) {
@@ -288,7 +301,7 @@ static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
     }
     const size_t CH = (size_t)64 << 20;
     bzx_index *ix = nullptr;
-    int rc = bzx_index_begin(ctx, CH, &ix);
+    int rc = salvage ? bzx_salvage_begin(ctx, CH, &ix) : bzx_index_begin(ctx, CH, &ix);
     if (rc) {
         fclose(in);
         return fail(o, "cannot start", name, ctx, rc);
@@ -312,18 +325,30 @@ static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
         size_t used = 0;
         rc = bzx_index_feed(ix, ibuf + off, have - off, eof ? 1 : 0, &used, &done);
         if (rc) {
-            ret = fail(o, "indexing failed", name, ctx, rc);
+            ret = fail(o, salvage ? "salvage failed" : "indexing failed", name, ctx, rc);
             break;
         }
         off += used;
     }
     fclose(in);
+    if (ibuf) bzx_host_free(ibuf);
+    if (ret) bzx_index_end(ix);
+    else *out = ix;
+    return ret;
+}
+
+// FILE.bz2 -> FILE.bz2.bzxi
+static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    const char *name = f.c_str();
+    bzx_index *ix = nullptr;
+    if (feed_index(o, ctx, f, false, &ix)) return 1;
     const bzx_index_entry *e = nullptr;
     bzx_index_info info;
-    if (!ret && (rc = bzx_index_get(ix, &e, &info))) ret = fail(o, "indexing failed", name, ctx, rc);
+    int ret = 0, rc;
+    if ((rc = bzx_index_get(ix, &e, &info))) ret = fail(o, "indexing failed", name, ctx, rc);
     if (!ret) ret = write_bzxi(o, f + ".bzxi", e, info);
     bzx_index_end(ix);
-    if (ibuf) bzx_host_free(ibuf);
     return ret;
 }
 
@@ -402,10 +427,11 @@ static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
         if (bzx_index_span(e.data(), nblk, o.range_off, o.range_len, &first, &count, &lo, &hi)) {
             ret = range_refuse(o, f, "the index does not match the file (entries out of order)");
         } else if (count) {
-            if (hi > file_size) hi = file_size;
-            span.resize((size_t)(hi - lo));
+            // (a salvaged block at the end of a truncated file: the 8 bytes behind it that the reader asks for are zeros)
+            const size_t in_file = (size_t)(std::min(hi, file_size) - std::min(lo, file_size));
+            span.assign((size_t)(hi - lo), 0);
             out.resize((size_t)std::min<uint64_t>(o.range_len, out_bytes - o.range_off));
-            if (fseeko(in, (off_t)lo, SEEK_SET) != 0 || fread(span.data(), 1, span.size(), in) != span.size()) {
+            if (fseeko(in, (off_t)lo, SEEK_SET) != 0 || fread(span.data(), 1, in_file, in) != in_file) {
                 ret = fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK);
             } else {
                 const int rc = bzx_decompress_range_buffer(ctx, span.data(), span.size(), lo, e.data(), nblk, o.range_off,
@@ -423,6 +449,120 @@ static int do_range(const Opts &o, bzx_ctx *ctx, const std::string &f)
                                    (unsigned long long)o.range_off, (unsigned long long)(o.range_off + got),
                                    (unsigned long long)count, span.size());
     return ret;
+}
+
+// ---- --recover ---------------------------------------------------------------------------------------------------------
+static std::string gap_words(uint32_t why)
+{
+    static const struct { uint32_t bit; const char *text; } words[] = {
+        {BZX_GAP_HEADER, "no stream header"},         {BZX_GAP_NO_MAGIC, "no block magic"},
+        {BZX_GAP_STRUCTURE, "damaged block"},         {BZX_GAP_BLOCK_CRC, "block CRC mismatch"},
+        {BZX_GAP_RANDOMISED, "randomised block"},     {BZX_GAP_TRUNCATED, "truncated"},
+        {BZX_GAP_COMBINED_CRC, "combined CRC mismatch"}};
+    std::string s;
+    for (const auto &w : words)
+        if (why & w.bit) s += (s.empty() ? "" : ", ") + std::string(w.text);
+    return s;
+}
+
+static const uint64_t RECOVER_PIECE = (uint64_t)256 << 20;   // output bytes of one range read (a block more where one alone is larger)
+static const uint64_t RECOVER_SPAN = (uint64_t)320 << 20;    // ... and the bytes of the file read for it: a piece ends before a long gap
+
+// Every intact block of FILE.bz2 -> FILE.recovered.  -> 0: nothing lost, 2: gaps, 1: trouble (after a message).
+static int do_recover(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    const char *name = f.c_str();
+    // the output's name, checked as -d checks its own, before the salvage pass is paid for
+    std::string oname;
+    if (!o.to_stdout) {
+        oname = (f.size() > 4 && f.compare(f.size() - 4, 4, ".bz2") == 0 ? f.substr(0, f.size() - 4) : f) + ".recovered";
+        struct stat sb;
+        if (!o.force && stat(oname.c_str(), &sb) == 0) {
+            if (!o.quiet) fprintf(stderr, "bzx: %s already exists (use -f)\n", oname.c_str());
+            return 1;
+        }
+    }
+    bzx_index *ix = nullptr;
+    if (feed_index(o, ctx, f, true, &ix)) return 1;
+    const bzx_index_entry *e = nullptr;
+    const bzx_gap *g = nullptr;
+    bzx_index_info info;
+    uint64_t ngaps = 0;
+    int rc = bzx_index_get(ix, &e, &info);
+    if (!rc) rc = bzx_index_get_gaps(ix, &g, &ngaps);
+    if (rc) {
+        bzx_index_end(ix);
+        return fail(o, "salvage failed", name, ctx, rc);
+    }
+    std::vector<bzx_index_entry> ent;
+    try {
+        ent.assign(e, e + info.nblk);
+    } catch (const std::bad_alloc &) {
+        bzx_index_end(ix);
+        return fail(o, "out of memory", name, nullptr, BZX_E_NOMEM);
+    }
+    if (!o.quiet)
+        for (uint64_t k = 0; k < ngaps; k++)
+            fprintf(stderr, "bzx: %s: gap at bits [%llu, %llu): %s; %u candidate block%s did not verify; at output offset %llu\n", name,
+                    (unsigned long long)g[k].bit_lo, (unsigned long long)g[k].bit_hi, gap_words(g[k].why).c_str(), g[k].candidates,
+                    g[k].candidates == 1 ? "" : "s", (unsigned long long)g[k].out_off);
+    bzx_index_end(ix);                                       // (the range reads need the context)
+    FILE *out = stdout;
+    if (!o.to_stdout) {
+        out = fopen(oname.c_str(), "wb");
+        if (!out) {
+            if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
+            return 1;
+        }
+    }
+    FILE *in = fopen(name, "rb");
+    int ret = in ? 0 : fail(o, strerror(errno), name, nullptr, BZX_OK);
+    std::vector<uint8_t> span, buf;
+    const uint64_t n = ent.size();
+    for (uint64_t k0 = 0; !ret && k0 < n;) {
+        // entries [k0, k1): one piece
+        const uint64_t lo = ent[k0].bit / 8;
+        uint64_t k1 = k0, bytes = 0, hi = lo;
+        while (k1 < n) {
+            const uint64_t end = (ent[k1].bit + ent[k1].img_bits + 7) / 8 + 8;
+            if (k1 > k0 && (bytes + ent[k1].out_len > RECOVER_PIECE || end - lo > RECOVER_SPAN)) break;
+            bytes += ent[k1].out_len;
+            hi = end;
+            k1++;
+        }
+        try {
+            const size_t in_file = (size_t)(std::min(hi, info.in_bytes) - lo);
+            span.assign((size_t)(hi - lo), 0);               // (zeros behind the end of a truncated file)
+            buf.resize((size_t)bytes);
+            size_t got = 0;
+            if (fseeko(in, (off_t)lo, SEEK_SET) != 0 || fread(span.data(), 1, in_file, in) != in_file)
+                ret = fail(o, strerror(errno), name, nullptr, BZX_OK);
+            else if ((rc = bzx_decompress_range_buffer(ctx, span.data(), span.size(), lo, ent.data(), n, ent[k0].out_off, bytes, buf.data(),
+                                                       &got)) ||
+                     got != bytes)
+                ret = fail(o, "reading the salvaged blocks failed", name, ctx, rc ? rc : BZX_E_DATA);
+            else if (fwrite(buf.data(), 1, got, out) != got)
+                ret = fail(o, strerror(errno), oname.empty() ? "(stdout)" : oname.c_str(), nullptr, BZX_OK);
+        } catch (const std::bad_alloc &) {
+            ret = fail(o, "out of memory", name, nullptr, BZX_E_NOMEM);
+        }
+        k0 = k1;
+    }
+    if (in) fclose(in);
+    if (out != stdout) {
+        if (fflush(out) != 0 || ferror(out) || fclose(out) != 0) {
+            if (!ret && !o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
+            ret = 1;
+        }
+        if (ret) unlink(oname.c_str());
+    } else if (fflush(out) != 0) {
+        ret = 1;
+    }
+    if (!ret && o.index) ret = write_bzxi(o, f + ".bzxi", ent.data(), info);
+    if (!ret && o.verbose)
+        fprintf(stderr, "  %s: %llu blocks, %llu bytes salvaged, %llu gaps\n", name, (unsigned long long)info.nblk,
+                (unsigned long long)info.out_bytes, (unsigned long long)ngaps);
+    return ret ? 1 : ngaps ? 2 : 0;
 }
 
 // LIST: OFF:LEN lines; blank lines and # comments are skipped.  -> 0, or 1 after a message that names the line.
@@ -691,9 +831,9 @@ int main(int argc, char **argv)
         } else if (a.rfind("--", 0) == 0) {
             if (a == "--help") { help(); return 0; }
             else if (a == "--version" || a == "--license") { printf("bzx, bzip2 block compression on MI355X; %s\n", bzx_version()); return 0; }
-            else if (a == "--decompress") o.mode = UNZIP;
-            else if (a == "--compress") o.mode = ZIP;
-            else if (a == "--test") o.mode = TEST;
+            else if (a == "--decompress") o.mode = UNZIP, o.mode_set = true;
+            else if (a == "--compress") o.mode = ZIP, o.mode_set = true;
+            else if (a == "--test") o.mode = TEST, o.mode_set = true;
             else if (a == "--stdout") o.to_stdout = true;
             else if (a == "--keep") o.keep = true;
             else if (a == "--force") o.force = true;
@@ -703,6 +843,7 @@ int main(int argc, char **argv)
             else if (a == "--fast") o.level = 1;
             else if (a == "--best") o.level = 9;
             else if (a == "--index") o.index = true;
+            else if (a == "--recover") o.recover = true;
             else if (a == "--with-index") o.with_index = true;
             else if (a == "--range" || a.rfind("--range=", 0) == 0) {
                 const std::string v = a == "--range" ? (i + 1 < argc ? argv[++i] : "") : a.substr(8);
@@ -744,9 +885,9 @@ int main(int argc, char **argv)
             for (size_t k = 1; k < a.size(); k++) {
                 const char c = a[k];
                 if (c >= '1' && c <= '9') o.level = c - '0';
-                else if (c == 'd') o.mode = UNZIP;
-                else if (c == 'z') o.mode = ZIP;
-                else if (c == 't') o.mode = TEST;
+                else if (c == 'd') o.mode = UNZIP, o.mode_set = true;
+                else if (c == 'z') o.mode = ZIP, o.mode_set = true;
+                else if (c == 't') o.mode = TEST, o.mode_set = true;
                 else if (c == 'c') o.to_stdout = true;
                 else if (c == 'k') o.keep = true;
                 else if (c == 'f') o.force = true;
@@ -772,6 +913,29 @@ int main(int argc, char **argv)
             fprintf(stderr, "bzx: %s\n", why);
             return 1;
         }
+    }
+    if (o.recover) {
+        if (o.with_index || o.range || !o.ranges.empty() || o.mode_set) {
+            fprintf(stderr, "bzx: --recover goes with --index, -c, -f, -q and -v only (not with -z, -d, -t, --range, --ranges or --with-index)\n");
+            return 1;
+        }
+        if (o.files.empty()) { fprintf(stderr, "bzx: --recover takes files\n"); return 1; }
+        for (const std::string &f : o.files)
+            if (f == "-") { fprintf(stderr, "bzx: --recover needs a file that can be read again, not standard input\n"); return 1; }
+        bzx_ctx *ctx = nullptr;
+        const int rc = bzx_ctx_create(0, UNZIP_SLABS, &ctx);
+        if (rc) {
+            fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
+            return 1;
+        }
+        int lost = 0, trouble = 0;
+        for (const std::string &f : o.files) {
+            const int r = do_recover(o, ctx, f);
+            if (r == 1) trouble = 1;
+            if (r == 2) lost = 2;
+        }
+        bzx_ctx_destroy(ctx);
+        return trouble ? 1 : lost;
     }
     if (!o.ranges.empty()) {
         if (o.index || o.range) { fprintf(stderr, "bzx: --ranges does not go with --index or --range\n"); return 1; }
