@@ -79,6 +79,7 @@ int ensure_blocks(bzx_ctx *ctx, uint32_t nblk, uint32_t nslab)
     if ((rc = dev_alloc(ctx, ctx->slabs, &B.selector, (size_t)cap * BZX_SEL_STRIDE))) return rc;
     if ((rc = dev_alloc(ctx, ctx->slabs, &B.selector_mtf, (size_t)cap * BZX_SEL_STRIDE))) return rc;
     if ((rc = dev_alloc(ctx, ctx->slabs, &B.gbits, (size_t)cap * BZX_SEL_STRIDE))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->slabs, &B.tbits, (size_t)cap * BZX_TILE_STRIDE))) return rc;
     if ((rc = dev_alloc(ctx, ctx->slabs, &B.pk, (size_t)cap * BZX_PK_STRIDE))) return rc;
     if ((rc = dev_alloc(ctx, ctx->slabs, &B.rec_a, (size_t)cap * BZX_MAX_N))) return rc;
     if ((rc = dev_alloc(ctx, ctx->slabs, &B.rec_b, (size_t)cap * BZX_MAX_N))) return rc;
@@ -343,12 +344,12 @@ int run_stages(bzx_ctx *ctx, uint32_t nblk, int stages, int out_level, void *d_s
             B.out = (uint32_t *)d_stream_out;
             bzx_launch_layout(B, 0, 0, ctx->d_scalars, ctx->stream, d_phase);
             HIP_TRY(ctx, hipMemsetAsync(d_stream_out, 0, stream_cap, ctx->stream));
-            if (nblk) bzx_launch_emit(B, grid_for(ctx, nblk, 2), ctx->stream);
+            if (nblk) bzx_launch_emit(B, (uint32_t)ctx->n_cu, ctx->stream);
         } else if (out_level == 0) {
             B.out = ctx->d_outbuf;
             bzx_launch_layout(B, 0, (uint64_t)BZX_OUT_STRIDE * 8, ctx->d_scalars, ctx->stream);
             HIP_TRY(ctx, hipMemsetAsync(ctx->d_outbuf, 0, (size_t)nblk * BZX_OUT_STRIDE, ctx->stream));
-            if (nblk) bzx_launch_emit(B, grid_for(ctx, nblk, 2), ctx->stream);
+            if (nblk) bzx_launch_emit(B, (uint32_t)ctx->n_cu, ctx->stream);
         } else {
             // sizes are known after the Huffman stage: lay the stream out, check it fits, then emit
             B.out = (uint32_t *)d_stream_out;
@@ -364,7 +365,7 @@ int run_stages(bzx_ctx *ctx, uint32_t nblk, int stages, int out_level, void *d_s
                 return BZX_E_OUTBUF;
             }
             HIP_TRY(ctx, hipMemsetAsync(d_stream_out, 0, need, ctx->stream));
-            if (nblk) bzx_launch_emit(B, grid_for(ctx, nblk, 2), ctx->stream);
+            if (nblk) bzx_launch_emit(B, (uint32_t)ctx->n_cu, ctx->stream);
             bzx_launch_stream_frame(B, out_level, ctx->d_scalars, ctx->d_scalars + 1, ctx->stream);
         }
     }
@@ -1058,7 +1059,7 @@ extern "C" int bzx_shard_emit_packed(bzx_ctx *ctx, const long long *d_bits_all, 
     B.blk_first = rank;
     B.blk_step = world;
     B.packed = 1;
-    if (mine) bzx_launch_emit(B, grid_for(ctx, mine, 2), ctx->stream);
+    if (mine) bzx_launch_emit(B, (uint32_t)ctx->n_cu, ctx->stream);
     B.packed = 0;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev[7], ctx->stream));

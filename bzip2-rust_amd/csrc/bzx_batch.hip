@@ -592,7 +592,7 @@ static int batch_run(bzx_ctx *ctx, uint32_t count, const void *const *d_raws, co
         HIP_TRY(ctx, hipEventRecord(ctx->ev_bt[1], st));
         HIP_TRY(ctx, hipMemsetAsync((uint8_t *)d_out + base, 0, end - base, st));
         B.nblk = nb;
-        if (nb) bzx_launch_emit(B, grid_for(ctx, nb, 2), st);
+        if (nb) bzx_launch_emit(B, (uint32_t)ctx->n_cu, st);
         bzx_batch_launch_frame(ws, i0, i1, rb0, B.blk, d_out, level, st);
         HIP_TRY(ctx, hipEventRecord(ctx->ev_bt[2], st));
         HIP_TRY(ctx, hipGetLastError());

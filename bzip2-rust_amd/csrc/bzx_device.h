@@ -4,7 +4,8 @@
 // pulls the next block from an atomic work counter when it is done.  Blocks are independent
 // (reference src/compression/compress_block.rs:3-8), so no stage needs inter-workgroup
 // communication; a batch of >= 256 blocks fills the 256 CUs.  All intermediates of a block
-// stay in HBM slabs addressed from the block descriptor below.
+// stay in HBM slabs addressed from the block descriptor below.  (The bucket sorter and the emit
+// stage deal smaller items -- buckets, runs of payload tiles -- over the workgroups instead.)
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -16,6 +17,10 @@
 #define BZX_N_ITERS 4
 #define BZX_MAX_SEL 18002          // ceil(900001 / 50)
 #define BZX_SEL_STRIDE 18048
+#define BZX_EMIT_TILE 512u         // 50-symbol groups per payload tile of the emit stage (one lane per group)
+#define BZX_MAX_TILES ((BZX_MAX_SEL + BZX_EMIT_TILE - 1) / BZX_EMIT_TILE)
+#define BZX_TILE_STRIDE 40         // per-block stride of the tile prefixes (BzxBatch.tbits)
+static_assert(BZX_MAX_TILES <= BZX_TILE_STRIDE, "a block's tile prefixes fit its stride of BzxBatch.tbits");
 
 #define BZX_IN_RAW (1ull << 63)
 #define BZX_ST_PERIODIC 1u         // block is u^k, k>1: identical rotations exist
@@ -129,6 +134,7 @@ struct BzxBatch {
     uint8_t *selector;      // [nblk][BZX_SEL_STRIDE]
     uint8_t *selector_mtf;  // [nblk][BZX_SEL_STRIDE]
     uint16_t *gbits;        // [nblk][BZX_SEL_STRIDE]  payload bits of every 50-symbol group
+    uint32_t *tbits;        // [nblk][BZX_TILE_STRIDE] payload bits in front of every tile of BZX_EMIT_TILE groups
     uint32_t *out;          // output bit buffer (zeroed), big-endian bit order
     BzxSortWs *sort_ws;     // [n_slots]
     uint8_t *pk;            // [nblk][BZX_PK_STRIDE]   packed blocks (bucket sorter)

@@ -9,11 +9,15 @@
 //
 // Every variable-length item gets its bit offset from an exclusive scan of item sizes, so all
 // items are written independently: one lane per 50-symbol group for the payload, one lane per
-// selector chunk, one lane per coding table.  A lane packs its bits in a 64-bit register and
-// stores whole 32-bit words; only the first and last word of a lane's range can be shared with
-// a neighbour and are merged with atomicOr into the zeroed output buffer.  Because a block's
-// out_bit is its final position in the stream (scan over block sizes, bzx_layout_kernel), no
-// host-side or second-pass bit shifting is needed: the .bz2 is complete in HBM.
+// selector chunk, one lane per coding table.  A lane packs its bits in a 64-bit register into
+// whole 32-bit words; only the first and last word of a lane's range can be shared with a
+// neighbour and are merged with atomicOr into zeroed memory.  Selectors and tables go straight
+// to the output.  The payload is cut into tiles of BZX_EMIT_TILE groups whose start offsets the
+// Huffman stage leaves (BzxBatch.tbits), so a block's tiles are work items of their own: a
+// tile is packed in LDS and leaves as consecutive words from consecutive lanes.  Because a
+// block's out_bit is its final position in the stream (scan over block sizes,
+// bzx_layout_kernel), no host-side or second-pass bit shifting is needed: the .bz2 is complete
+// in HBM.
 #include <hip/hip_runtime.h>
 #include "bzx_host.h"
 #include "bzx_wg.h"
@@ -21,7 +25,21 @@
 #define EMIT_NT 512
 #define EMIT_NW (EMIT_NT / 64)
 
-struct BitW {
+#ifndef EMIT_TPI
+// Tiles per work item.  Measured on the 1,194-block batch: 1 and 2 are slower, 4, 8 and 36 (the
+// whole block) the same within the spread; 4 is the smallest of those, so that a lone block spreads the widest.
+#define EMIT_TPI 4
+#endif
+#define EMIT_SLOTS ((BZX_MAX_TILES + EMIT_TPI - 1) / EMIT_TPI)      // item slots per block (a small block leaves most empty)
+static_assert(EMIT_NT == BZX_EMIT_TILE, "one lane per group of a tile");
+// The staging area takes the largest tile there is (every group fifty 17-bit codes) at any bit phase and any alignment
+// of its first output word: no tile goes another way.
+#define EMIT_STAGE_BITS (EMIT_NT * BZX_G_SIZE * 17u)
+#define EMIT_STAGE_WORDS ((EMIT_STAGE_BITS / 32u + 2u + 3u + 3u) & ~3u)
+
+// MSB-first bit writer of one lane over a zeroed word array.  GLOBAL: the output buffer, words big-endian; otherwise the
+// LDS staging area, words in register order (swapped when the tile is copied out).
+template <bool GLOBAL> struct BitWT {
     uint32_t *out;
     uint64_t wi;      // next 32-bit word index
     uint64_t acc;
@@ -37,7 +55,7 @@ struct BitW {
     }
     __device__ __forceinline__ void flush_word(uint32_t w)
     {
-        const uint32_t be = __builtin_bswap32(w);
+        const uint32_t be = GLOBAL ? __builtin_bswap32(w) : w;
         if (first) {
             if (be) atomicOr(&out[wi], be);
             first = false;
@@ -60,18 +78,19 @@ struct BitW {
     __device__ __forceinline__ void finish()
     {
         if (nacc > 0) {
-            const uint32_t be = __builtin_bswap32((uint32_t)(acc << (32 - nacc)));
+            const uint32_t w = (uint32_t)(acc << (32 - nacc));
+            const uint32_t be = GLOBAL ? __builtin_bswap32(w) : w;
             if (be) atomicOr(&out[wi], be);
         }
     }
 };
+typedef BitWT<true> BitW;
 
 __shared__ uint8_t e_len[6][BZX_MAX_ALPHA + 2];
-__shared__ uint32_t e_code[6][BZX_MAX_ALPHA + 2];
 __shared__ uint32_t e_cl[6][BZX_MAX_ALPHA + 2];     // code | length << 24: one lookup per payload symbol
-// one tile of payload symbols: EMIT_NT groups x 25 words, loaded coalesced, read back by group (stride 25 words: odd,
-// so the lanes of a wave hit different banks)
-__shared__ __attribute__((aligned(16))) uint32_t e_tile[EMIT_NT * (BZX_G_SIZE / 2)];
+// one tile of payload bits, packed by the lanes at tile-relative bit offsets and copied out by the whole workgroup;
+// all zero between tiles (the copy clears what it reads)
+__shared__ __attribute__((aligned(16))) uint32_t e_stage[EMIT_STAGE_WORDS];
 __shared__ uint32_t e_tabbits[8];
 __shared__ uint32_t e_scratch[2 * EMIT_NW];
 __shared__ uint32_t e_bcast[4];
@@ -85,18 +104,57 @@ __shared__ uint32_t e_bcast[4];
         }                                                                     \
     } while (0)
 
+// What a lane needs of tile t: its group's fifty symbols (two per word; the slab is longer than any block's symbols, so
+// a short last group reads past n_mtf -- such symbols are never coded), the group's size and table, and the tile's
+// place in the payload.  All of it is in flight together; nothing here waits.
+__device__ __forceinline__ void emit_load_tile(const uint16_t *__restrict__ V, const uint16_t *__restrict__ GB,
+                                               const uint8_t *__restrict__ SEL, const uint32_t *__restrict__ TB, uint32_t t,
+                                               uint32_t n_sel, uint32_t (&vw)[BZX_G_SIZE / 2], uint32_t &gb, uint32_t &sel,
+                                               uint32_t &tb)
+{
+    const uint32_t g = t * EMIT_NT + threadIdx.x;
+    tb = TB[t];
+    gb = 0;
+    sel = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < BZX_G_SIZE / 2; k++) vw[k] = 0;
+    if (g < n_sel) {
+        const uint32_t *__restrict__ vp = reinterpret_cast<const uint32_t *>(V + (size_t)g * BZX_G_SIZE);
+#pragma unroll
+        for (uint32_t k = 0; k < BZX_G_SIZE / 2; k++) vw[k] = vp[k];
+        gb = GB[g];
+        sel = SEL[g];
+    }
+}
+
+// Work item: EMIT_TPI consecutive tiles of one block (item slot s of block j is item j * EMIT_SLOTS + s, empty slots
+// are skipped by the lane that fetches), so that the tiles of a batch are dealt evenly over the resident workgroups
+// and one block alone still spreads over the chip.  The item with a block's first tile also writes sections (a)-(c).
 __global__ __launch_bounds__(EMIT_NT) void bzx_emit_kernel(BzxBatch B)
 {
     const uint32_t tid = threadIdx.x, lane = bzx_lane(), wave = bzx_wave();
     unsigned long long t_last = 0;
+    const uint32_t n_items = B.nblk * EMIT_SLOTS;
+    uint4 *stage4 = reinterpret_cast<uint4 *>(e_stage);
+    for (uint32_t i = tid; i < EMIT_STAGE_WORDS / 4; i += EMIT_NT) stage4[i] = make_uint4(0u, 0u, 0u, 0u);
 
     for (;;) {
-        if (tid == 0) e_bcast[0] = atomicAdd(&B.counters[3], 1u);
+        if (tid == 0) {
+            uint32_t id;
+            for (;;) {
+                id = atomicAdd(&B.counters[3], 1u);
+                if (id >= n_items || id % EMIT_SLOTS == 0) break;
+                const uint32_t bb = B.blk_first + (id / EMIT_SLOTS) * B.blk_step;
+                if ((id % EMIT_SLOTS) * (EMIT_TPI * EMIT_NT) < B.blk[bb].n_selectors) break;
+            }
+            e_bcast[0] = id;
+        }
         __syncthreads();
-        const uint32_t j_ = e_bcast[0];
+        const uint32_t id = bzx_uni(e_bcast[0]);
         __syncthreads();
-        if (j_ >= B.nblk) break;
-        const uint32_t b = B.blk_first + j_ * B.blk_step;
+        if (id >= n_items) break;
+        const uint32_t slot = id % EMIT_SLOTS;
+        const uint32_t b = B.blk_first + (id / EMIT_SLOTS) * B.blk_step;
 
         if (B.dbg && tid == 0) t_last = wall_clock64();
         const BzxBlock d = B.blk[b];
@@ -105,6 +163,7 @@ __global__ __launch_bounds__(EMIT_NT) void bzx_emit_kernel(BzxBatch B)
         const uint8_t *__restrict__ SEL = B.selector + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
         const uint8_t *__restrict__ SELM = B.selector_mtf + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
         const uint16_t *__restrict__ GB = B.gbits + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
+        const uint32_t *__restrict__ TB = B.tbits + BZX_SLAB(B, b) * BZX_TILE_STRIDE;
         uint32_t *out = B.out;
 
         // final stream position, or (sharded runs) the same bit phase inside this rank's packed buffer
@@ -115,145 +174,175 @@ __global__ __launch_bounds__(EMIT_NT) void bzx_emit_kernel(BzxBatch B)
         const uint64_t o_tab = o_sel + d.sec_bits[0];
         const uint64_t o_pay = o_tab + d.sec_bits[1];
 
+        // the item's tiles; the first one's loads leave before anything waits
+        const uint32_t n_tiles = (n_sel + EMIT_NT - 1) / EMIT_NT;
+        const uint32_t t0 = slot * EMIT_TPI, t1 = t0 + EMIT_TPI < n_tiles ? t0 + EMIT_TPI : n_tiles;
         for (uint32_t i = tid; i < 6 * 260; i += EMIT_NT) {
             const uint32_t t = i / 260, v = i % 260;
             if (v < BZX_MAX_ALPHA + 2) {
-                e_len[t][v] = B.len[BZX_SLAB(B, b) * 6 * 260 + i];
-                e_code[t][v] = B.code[BZX_SLAB(B, b) * 6 * 260 + i];
-                e_cl[t][v] = B.code[BZX_SLAB(B, b) * 6 * 260 + i] | ((uint32_t)B.len[BZX_SLAB(B, b) * 6 * 260 + i] << 24);
+                const uint8_t l = B.len[BZX_SLAB(B, b) * 6 * 260 + i];
+                if (slot == 0) e_len[t][v] = l;
+                e_cl[t][v] = B.code[BZX_SLAB(B, b) * 6 * 260 + i] | ((uint32_t)l << 24);
             }
         }
-        __syncthreads();
+        uint32_t vn[BZX_G_SIZE / 2], gbn, seln, tbn;
+        emit_load_tile(V, GB, SEL, TB, t0, n_sel, vn, gbn, seln, tbn);
+        bzx_lds_barrier();
 
-        // ---- (a) block header, symbol map, nGroups, nSelectors (compress_block.rs:34-48, huffman.rs:209-224)
-        if (tid == 0) {
-            BitW w;
-            w.init(out, ob);
-            w.put(24, 0x314159u);
-            w.put(24, 0x265359u);
-            w.put(32, d.crc);
-            w.put(1, 0);
-            w.put(24, d.orig_ptr);
-            uint32_t l1 = 0, words[16];
-            for (uint32_t i = 0; i < 16; i++) {
-                uint32_t wv = 0;
-                for (uint32_t j = 0; j < 16; j++)
-                    if (B.in_use[BZX_SLAB(B, b) * 256 + i * 16 + j]) wv |= 0x8000u >> j;
-                words[i] = wv;
-                if (wv) l1 |= 0x8000u >> i;
-            }
-            w.put(16, l1);
-            for (uint32_t i = 0; i < 16; i++)
-                if (words[i]) w.put(16, words[i]);
-            w.put(3, n_groups);
-            w.put(15, n_sel);
-            w.finish();
-        }
-
-        EMIT_STAMP(48);
-        // ---- (b) selectors, unary (huffman.rs:237-292)
-        {
-            const uint32_t per = (n_sel + EMIT_NT - 1) / EMIT_NT;
-            const uint32_t lo = tid * per < n_sel ? tid * per : n_sel;
-            const uint32_t hi = lo + per < n_sel ? lo + per : n_sel;
-            uint32_t my_bits = 0;
-            for (uint32_t i = lo; i < hi; i++) my_bits += SELM[i] + 1u;
-            uint32_t tot;
-            const uint32_t ex = bzx_block_excl_sum<EMIT_NT>(my_bits, e_scratch, tot);
-            if (hi > lo) {
+        if (slot == 0) {
+            // ---- (a) block header, symbol map, nGroups, nSelectors (compress_block.rs:34-48, huffman.rs:209-224)
+            if (tid == 0) {
                 BitW w;
-                w.init(out, o_sel + ex);
-                for (uint32_t i = lo; i < hi; i++) {
-                    const uint32_t j = SELM[i];
-                    w.put(j + 1, ((1u << j) - 1u) << 1);
+                w.init(out, ob);
+                w.put(24, 0x314159u);
+                w.put(24, 0x265359u);
+                w.put(32, d.crc);
+                w.put(1, 0);
+                w.put(24, d.orig_ptr);
+                uint32_t l1 = 0, words[16];
+                for (uint32_t i = 0; i < 16; i++) {
+                    uint32_t wv = 0;
+                    for (uint32_t j = 0; j < 16; j++)
+                        if (B.in_use[BZX_SLAB(B, b) * 256 + i * 16 + j]) wv |= 0x8000u >> j;
+                    words[i] = wv;
+                    if (wv) l1 |= 0x8000u >> i;
                 }
+                w.put(16, l1);
+                for (uint32_t i = 0; i < 16; i++)
+                    if (words[i]) w.put(16, words[i]);
+                w.put(3, n_groups);
+                w.put(15, n_sel);
                 w.finish();
             }
-        }
 
-        EMIT_STAMP(49);
-        // ---- (c) coding tables, delta coded (huffman.rs:391-438), one lane per table
-        if (lane == 0 && wave < n_groups) {
-            uint32_t bits = 5;
-            int32_t curr = e_len[wave][0];
-            for (uint32_t i = 0; i < alpha; i++) {
-                const int32_t l = e_len[wave][i];
-                bits += 2u * (uint32_t)(l > curr ? l - curr : curr - l) + 1u;
-                curr = l;
-            }
-            e_tabbits[wave] = bits;
-        }
-        __syncthreads();
-        if (lane == 0 && wave < n_groups) {
-            uint64_t pos = o_tab;
-            for (uint32_t t = 0; t < wave; t++) pos += e_tabbits[t];
-            BitW w;
-            w.init(out, pos);
-            int32_t curr = e_len[wave][0];
-            w.put(5, (uint32_t)curr);
-            for (uint32_t i = 0; i < alpha; i++) {
-                const int32_t l = e_len[wave][i];
-                while (curr < l) {
-                    w.put(2, 2);
-                    curr++;
-                }
-                while (curr > l) {
-                    w.put(2, 3);
-                    curr--;
-                }
-                w.put(1, 0);
-            }
-            w.finish();
-        }
-
-        __syncthreads();
-        EMIT_STAMP(50);
-        // ---- (d) payload (huffman.rs:452-466): one lane per group, offsets from a scan of group sizes
-        {
-            if (tid == 0) e_bcast[1] = 0;
-            __syncthreads();
-            for (uint32_t g0 = 0; g0 < n_sel; g0 += EMIT_NT) {
-                const uint32_t g = g0 + tid;
-                const uint32_t carry = e_bcast[1];
-                const uint32_t gb = g < n_sel ? (uint32_t)GB[g] : 0u;
+            EMIT_STAMP(48);
+            // ---- (b) selectors, unary (huffman.rs:237-292)
+            {
+                const uint32_t per = (n_sel + EMIT_NT - 1) / EMIT_NT;
+                const uint32_t lo = tid * per < n_sel ? tid * per : n_sel;
+                const uint32_t hi = lo + per < n_sel ? lo + per : n_sel;
+                uint32_t my_bits = 0;
+                for (uint32_t i = lo; i < hi; i++) my_bits += SELM[i] + 1u;
                 uint32_t tot;
-                const uint32_t ex = bzx_block_excl_sum<EMIT_NT>(gb, e_scratch, tot);
-                // the tile's symbols: coalesced 16-byte loads into LDS (the slab is longer than any block's symbols,
-                // so the last tile may read past n_mtf; such symbols are never coded)
-                {
-                    const uint4 *__restrict__ src = reinterpret_cast<const uint4 *>(V + (size_t)g0 * BZX_G_SIZE);
-                    uint4 *dst = reinterpret_cast<uint4 *>(e_tile);
-                    const uint32_t ng = n_sel - g0 < EMIT_NT ? n_sel - g0 : EMIT_NT;
-                    const uint32_t nq = (ng * (BZX_G_SIZE / 2) + 3u) / 4u;          // 16-byte pieces
-                    for (uint32_t i = tid; i < nq; i += EMIT_NT) dst[i] = src[i];
-                }
-                __syncthreads();
-                if (g < n_sel) {
-                    const uint32_t gs = g * BZX_G_SIZE;
-                    const uint32_t cnt = (n_mtf - gs < BZX_G_SIZE) ? n_mtf - gs : BZX_G_SIZE;
-                    const uint32_t *vp = e_tile + tid * (BZX_G_SIZE / 2);
-                    const uint32_t *__restrict__ cl = e_cl[SEL[g]];
-                    uint32_t vw[BZX_G_SIZE / 2];
-#pragma unroll
-                    for (uint32_t k = 0; k < BZX_G_SIZE / 2; k++) vw[k] = 2 * k < cnt ? vp[k] : 0u;
+                const uint32_t ex = bzx_block_excl_sum_lds<EMIT_NT>(my_bits, e_scratch, tot);
+                if (hi > lo) {
                     BitW w;
-                    w.init(out, o_pay + carry + ex);
-#pragma unroll
-                    for (uint32_t k = 0; k < BZX_G_SIZE / 2; k++) {
-                        const uint32_t c0 = 2 * k < cnt ? cl[vw[k] & 0xffffu] : 0u;
-                        const uint32_t c1 = 2 * k + 1 < cnt ? cl[vw[k] >> 16] : 0u;
-                        w.put(c0 >> 24, c0 & 0xffffffu);
-                        w.put(c1 >> 24, c1 & 0xffffffu);
+                    w.init(out, o_sel + ex);
+                    for (uint32_t i = lo; i < hi; i++) {
+                        const uint32_t j = SELM[i];
+                        w.put(j + 1, ((1u << j) - 1u) << 1);
                     }
                     w.finish();
                 }
-                if (tid == 0) e_bcast[1] = carry + tot;
-                __syncthreads();
             }
+
+            EMIT_STAMP(49);
+            // ---- (c) coding tables, delta coded (huffman.rs:391-438), one lane per table
+            if (lane == 0 && wave < n_groups) {
+                uint32_t bits = 5;
+                int32_t curr = e_len[wave][0];
+                for (uint32_t i = 0; i < alpha; i++) {
+                    const int32_t l = e_len[wave][i];
+                    bits += 2u * (uint32_t)(l > curr ? l - curr : curr - l) + 1u;
+                    curr = l;
+                }
+                e_tabbits[wave] = bits;
+            }
+            bzx_lds_barrier();
+            if (lane == 0 && wave < n_groups) {
+                uint64_t pos = o_tab;
+                for (uint32_t t = 0; t < wave; t++) pos += e_tabbits[t];
+                BitW w;
+                w.init(out, pos);
+                int32_t curr = e_len[wave][0];
+                w.put(5, (uint32_t)curr);
+                for (uint32_t i = 0; i < alpha; i++) {
+                    const int32_t l = e_len[wave][i];
+                    while (curr < l) {
+                        w.put(2, 2);
+                        curr++;
+                    }
+                    while (curr > l) {
+                        w.put(2, 3);
+                        curr--;
+                    }
+                    w.put(1, 0);
+                }
+                w.finish();
+            }
+            EMIT_STAMP(50);
         }
-        __syncthreads();
+
+        // ---- (d) payload (huffman.rs:452-466): one lane per group.  A group's place in its tile comes from a scan of the
+        // tile's group sizes, the tile's place in the payload from the Huffman stage (TB).  The lanes pack into the
+        // staging area; the workgroup then copies the tile's words out, consecutive lanes consecutive words, 16 bytes
+        // each where all four words are the tile's alone.  Only the first and the last word of a tile can be shared
+        // (with the next tile, the section in front or the next block): those are merged with atomicOr into the zeroed
+        // output.  The next tile's loads are in flight meanwhile.
+        for (uint32_t t = t0; t < t1; t++) {
+            uint32_t vw[BZX_G_SIZE / 2];
+#pragma unroll
+            for (uint32_t k = 0; k < BZX_G_SIZE / 2; k++) vw[k] = vn[k];
+            const uint32_t gb = gbn, sel = seln;
+            const uint64_t start = o_pay + bzx_uni(tbn);
+            if (t + 1 < t1) emit_load_tile(V, GB, SEL, TB, t + 1, n_sel, vn, gbn, seln, tbn);
+
+            uint32_t tot;
+            const uint32_t ex = bzx_block_excl_sum_lds<EMIT_NT>(gb, e_scratch, tot);
+            const uint64_t wbase = start >> 5;
+            const uint32_t phase = (uint32_t)(start & 31u);
+            // the tile's first word sits at staging word `off`, so that 16-byte pieces line up in LDS and in the output
+            const uint32_t off = (uint32_t)((uintptr_t)(out + wbase) >> 2) & 3u;
+            const uint32_t g = t * EMIT_NT + tid;
+            if (g < n_sel) {
+                const uint32_t gs = g * BZX_G_SIZE;
+                const uint32_t cnt = (n_mtf - gs < BZX_G_SIZE) ? n_mtf - gs : BZX_G_SIZE;
+                const uint32_t *__restrict__ cl = e_cl[sel];
+                BitWT<false> w;
+                w.init(e_stage, off * 32u + phase + ex);
+#pragma unroll
+                for (uint32_t k = 0; k < BZX_G_SIZE / 2; k++) {
+                    const uint32_t c0 = 2 * k < cnt ? cl[vw[k] & 0xffffu] : 0u;
+                    const uint32_t c1 = 2 * k + 1 < cnt ? cl[vw[k] >> 16] : 0u;
+                    w.put(c0 >> 24, c0 & 0xffffffu);
+                    w.put(c1 >> 24, c1 & 0xffffffu);
+                }
+                w.finish();
+            }
+            bzx_lds_barrier();
+            const uint32_t end = off + ((phase + tot + 31u) >> 5);          // staging words [off, end) are the tile's
+            uint32_t *gbase = out + wbase - off;                            // 16-byte aligned
+            for (uint32_t i0 = 4 * tid; i0 < end; i0 += 4 * EMIT_NT) {
+                const uint4 v = stage4[i0 / 4];
+                stage4[i0 / 4] = make_uint4(0u, 0u, 0u, 0u);
+                const uint32_t x[4] = {__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z),
+                                       __builtin_bswap32(v.w)};
+                if (i0 > off && i0 + 4 < end) {
+                    *reinterpret_cast<uint4 *>(gbase + i0) = make_uint4(x[0], x[1], x[2], x[3]);
+                } else {
+#pragma unroll
+                    for (uint32_t c = 0; c < 4; c++) {
+                        const uint32_t i = i0 + c;
+                        if (i < off || i >= end) continue;
+                        if (i == off || i + 1 == end) {
+                            if (x[c]) atomicOr(gbase + i, x[c]);
+                        } else {
+                            gbase[i] = x[c];
+                        }
+                    }
+                }
+            }
+            bzx_lds_barrier();
+        }
         EMIT_STAMP(51);
     }
+}
+
+extern "C" void bzx_emit_geometry(uint32_t *tile_groups, uint32_t *tiles_per_item, uint32_t *staging_bits)
+{
+    if (tile_groups) *tile_groups = EMIT_NT;
+    if (tiles_per_item) *tiles_per_item = EMIT_TPI;
+    if (staging_bits) *staging_bits = (EMIT_STAGE_WORDS - 4u) * 32u;
 }
 
 // out_bit of every block: first_bit + exclusive scan of block sizes (stream mode, stride_bits == 0)
@@ -470,8 +559,11 @@ void bzx_launch_bits_import(const BzxBatch &B, const long long *bits, hipStream_
     hipLaunchKernelGGL(bzx_bits_import_kernel, dim3(64), dim3(256), 0, stream, B, bits);
 }
 
-void bzx_launch_emit(const BzxBatch &B, uint32_t grid, hipStream_t stream)
+void bzx_launch_emit(const BzxBatch &B, uint32_t n_cu, hipStream_t stream)
 {
+    // two workgroups fit a compute unit (62 KB of LDS each); fewer when the batch has fewer item slots than that
+    const uint64_t slots = (uint64_t)B.nblk * EMIT_SLOTS;
+    const uint32_t grid = slots < 2ull * n_cu ? (uint32_t)slots : 2u * n_cu;
     hipLaunchKernelGGL(bzx_emit_kernel, dim3(grid), dim3(EMIT_NT), 0, stream, B);
 }
 

@@ -236,7 +236,8 @@ uint32_t bzx_bsort_blocks_per_cu();
 void bzx_launch_periodic(const BzxBatch &B, uint32_t grid, hipStream_t stream);                             // bzx_periodic.hip
 void bzx_launch_mtf(const BzxBatch &B, uint32_t grid, hipStream_t stream);                                  // bzx_mtf.hip
 void bzx_launch_huffman(const BzxBatch &B, uint32_t grid, hipStream_t stream);                              // bzx_huff.hip
-void bzx_launch_emit(const BzxBatch &B, uint32_t grid, hipStream_t stream);                                 // bzx_emit.hip
+// (the emit kernel's work item is a run of tiles of a block, so its grid is sized by residency on n_cu compute units)
+void bzx_launch_emit(const BzxBatch &B, uint32_t n_cu, hipStream_t stream);                                 // bzx_emit.hip
 void bzx_launch_layout(const BzxBatch &B, uint64_t first_bit, uint64_t stride_bits, uint64_t *d_total_bits,
                        hipStream_t stream, uint64_t *d_phase = nullptr);
 void bzx_launch_stream_frame(const BzxBatch &B, int level, const uint64_t *d_total_bits, uint64_t *d_out_bytes,

@@ -42,6 +42,8 @@ __shared__ uint32_t h_part[6][2];   // initial partition [gs, ge] per table
 __shared__ uint32_t h_scratch[2 * HUF_NW];
 __shared__ uint32_t h_bcast[4];
 __shared__ uint32_t h_acc[4];       // [0] selector bits, [1] table bits, [2] payload bits
+__shared__ uint32_t h_tbits[BZX_MAX_TILES];   // payload bits of every emit tile (BZX_EMIT_TILE groups)
+static_assert(BZX_EMIT_TILE % 64 == 0 && BZX_MAX_TILES <= 64, "a wave sums whole 64-group pieces of a tile; one wave scans the tiles");
 
 // libbz2 hbMakeCodeLengths for table t, by ONE WAVE: the heap (whose order decides ties) is built and
 // emptied by lane 0 exactly as libbz2 does it; what has no order -- the initial weights, the depth of every leaf
@@ -171,6 +173,27 @@ __device__ __forceinline__ void huff_load_group(const uint16_t *__restrict__ v, 
         }                                                                     \
     } while (0)
 
+// Payload bits in front of every emit tile (the emit stage deals a block's tiles over many workgroups: each must know
+// where its tile starts): the group sizes the workgroup has just written (behind a barrier), a wave per tile, then a
+// scan over the tiles.  Not inlined: the kernel's register allocation stays what it is without this.
+__device__ __attribute__((noinline)) void huff_tile_prefixes(const uint16_t *GB, uint32_t *TB, uint32_t n_sel)
+{
+    const uint32_t lane = bzx_lane(), wave = bzx_wave();
+    for (uint32_t tl = wave; tl < BZX_MAX_TILES; tl += HUF_NW) {
+        const uint32_t ge = (tl + 1) * BZX_EMIT_TILE < n_sel ? (tl + 1) * BZX_EMIT_TILE : n_sel;
+        uint32_t s = 0;
+        for (uint32_t g = tl * BZX_EMIT_TILE + lane; g < ge; g += 64) s += GB[g];
+        s = bzx_wave_incl_sum(s);
+        if (lane == 63) h_tbits[tl] = s;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const uint32_t tb = lane < BZX_MAX_TILES ? h_tbits[lane] : 0u;
+        const uint32_t incl = bzx_wave_incl_sum(tb);
+        if (lane < BZX_MAX_TILES) TB[lane] = incl - tb;
+    }
+}
+
 #ifndef HUF_WAVES_PER_SIMD
 #define HUF_WAVES_PER_SIMD 6            // three workgroups per compute unit (48 KB of LDS each)
 #endif
@@ -196,6 +219,7 @@ __global__ __launch_bounds__(HUF_NT) __attribute__((amdgpu_waves_per_eu(HUF_WAVE
         uint8_t *__restrict__ SEL = B.selector + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
         uint8_t *__restrict__ SELM = B.selector_mtf + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
         uint16_t *__restrict__ GB = B.gbits + BZX_SLAB(B, b) * BZX_SEL_STRIDE;
+        uint32_t *__restrict__ TB = B.tbits + BZX_SLAB(B, b) * BZX_TILE_STRIDE;
         const uint32_t n_sel = (n_mtf + BZX_G_SIZE - 1) / BZX_G_SIZE;
         const uint32_t n_groups = n_mtf < 200 ? 2u : n_mtf < 600 ? 3u : n_mtf < 1200 ? 4u : n_mtf < 2400 ? 5u : 6u;
 
@@ -373,6 +397,7 @@ __global__ __launch_bounds__(HUF_NT) __attribute__((amdgpu_waves_per_eu(HUF_WAVE
             (void)bzx_block_excl_sum<HUF_NT>(my_bits, h_scratch, tot);
             if (tid == 0) h_acc[2] = tot;
         }
+        huff_tile_prefixes(GB, TB, n_sel);
 
         HUF_STAMP(44);
         // ---- selector MTF (huffman.rs:237-292): chunk per lane, start list rebuilt from earlier chunks

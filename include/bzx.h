@@ -103,6 +103,13 @@ struct bzx_block_info;
 int bzx_stage_encode(bzx_ctx *ctx, const uint16_t *mtfv, uint32_t n_mtf, const uint32_t freq[258],
                      const uint8_t in_use[256], uint32_t orig_ptr, uint32_t crc, uint8_t *out, size_t cap,
                      size_t *out_len, uint8_t *pad_bits, uint8_t *selector_mtf, struct bzx_block_info *info);
+/*
+ * Test/diagnostic: how this build's emit stage cuts a block's payload.  *tile_groups: 50-symbol groups per tile (a tile
+ * is packed in LDS and written out by the whole workgroup); *tiles_per_item: consecutive tiles of one block a workgroup
+ * takes per work item; *staging_bits: payload bits of a tile the LDS staging area holds at any bit phase -- at least
+ * tile_groups * 850, the most a tile can have, so every tile goes through it.  Needs no context and no device.
+ */
+void bzx_emit_geometry(uint32_t *tile_groups, uint32_t *tiles_per_item, uint32_t *staging_bits);
 
 /*
  * RLE1 + block split + per-block CRC (replaces RLE1Block, rle1.rs:33-263, and do_crc,
