@@ -73,62 +73,64 @@ template <int NW> struct SeenSet {
     }
 };
 
-// MTF ranks of my chunk with the WHOLE list in registers (alphabets of <= 8*NWORD symbols, e.g. text):
-// byte k of word k/8 = list entry k.  Branch-free: every lane finds the word and byte that hold the symbol
-// with the zero-byte trick, then every word is either shifted by one entry (words before the hit), patched
-// (the hit word) or left alone -- no LDS traffic and no divergence inside the loop.
-template <int NWORD>
-__device__ __forceinline__ void mtf_ranks_regs(const uint8_t *L, uint8_t *R, uint32_t c_lo,
-                                               uint32_t c_hi, const uint64_t *lst64, const uint8_t *seq)
+// MTF ranks of my chunk with the WHOLE list in registers (alphabets of <= 4 * NR symbols, e.g. text: 28 symbols, NR = 7):
+// byte k & 3 of register k >> 2 = list entry k.  Every entry and the padding are below 0x80 and the padding (0x7f) equals
+// no dense id, so the byte tests below carry nothing from byte to byte.  A head costs 7 vector instructions per register
+// and 6 of its own, all 32 bits wide, and nothing in the loop depends on the data but the values:
+//   search  x = w[t] ^ s4 is zero in the one byte that holds the symbol; (x + 0x7f7f7f7f) & 0x80808080 has 0x80 in every
+//           OTHER byte, and a dot product with the entries' indices sums 128 * index over them: what is missing from the
+//           sum over all indices is 128 * rank.
+//   update  entries 0 .. rank move up by one and the symbol enters in front: register t takes its first
+//           clamp(8 * rank + 8 - 32 * t, 0, 31) bits from the list shifted by a byte (v_alignbyte with the register
+//           before it; s4 stands in before register 0 and brings the symbol) and keeps the rest.  Bit 31 of a register is
+//           never set, so 31 bits do for a register that moves as a whole.  Rank 0 rewrites entry 0 with itself.
+// No guard on i < c_hi: chunks are multiples of 16 heads (csz) and only the last used chunk is short, so its last group
+// runs over up to 15 bytes behind nh.  Those lie in the block's own slab (nh <= 900,000, the slab has 96 bytes more), are
+// loaded and stored as part of the same 16-byte accesses anyway, translate to some id <= n_in_use through seq[] (a symbol
+// the list does not hold counts as rank 0), and nothing reads a rank at or behind nh (pass 6 stops at nh); the list they
+// scramble is dead after the loop.
+template <int NR>
+__device__ __forceinline__ void mtf_ranks_regs(uint8_t *H, uint32_t c_lo, uint32_t c_hi, const uint32_t *lst32, const uint8_t *seq)
 {
-    const uint64_t ones = 0x0101010101010101ull, highs = 0x8080808080808080ull;
-    uint64_t w[NWORD];
+    constexpr uint32_t TOT = 128u * (4 * NR) * (4 * NR - 1) / 2 + 128u;      // 128 * (every index + 1)
+    uint32_t w[NR];
 #pragma unroll
-    for (int i = 0; i < NWORD; i++) w[i] = lst64[i];
-    uint4 nxt = c_lo < c_hi ? *reinterpret_cast<const uint4 *>(L + c_lo) : make_uint4(0, 0, 0, 0);
+    for (int t = 0; t < NR; t++) w[t] = lst32[t] & 0x7f7f7f7fu;              // (the start lists pad with 0xff)
+    const uint32_t i_last = (c_hi - 1) & ~15u;                               // my last group (c_lo < c_hi)
+    uint4 nxt = *reinterpret_cast<const uint4 *>(H + c_lo);
     for (uint32_t i0 = c_lo; i0 < c_hi; i0 += 16) {
         const uint4 v = nxt;
-        if (i0 + 16 < c_hi) nxt = *reinterpret_cast<const uint4 *>(L + i0 + 16);     // in flight during the 16 steps below
+        nxt = *reinterpret_cast<const uint4 *>(H + (i0 + 16 < i_last ? i0 + 16 : i_last));   // in flight during the 16 steps below
         const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-        uint32_t o[4] = {0, 0, 0, 0};
+        uint32_t s4[16];                                                     // the 16 lookups depend on nothing in the chain
+#pragma unroll
+        for (int k = 0; k < 16; k++) s4[k] = bzx_rep4(seq[(wd[k >> 2] >> (8 * (k & 3))) & 255u]);
+        uint32_t o[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
+            uint32_t p = 0;                                                  // rank + 1 of the four heads
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const uint32_t i = i0 + q * 4 + k;
-                if (i < c_hi) {
-                    const uint64_t s = seq[(wd[q] >> (8 * k)) & 255u];
-                    const uint64_t sp = s * ones;
-                    // hit word h and byte j
-                    uint32_t h = NWORD, j = 0;
+                const uint32_t sp = s4[q * 4 + k];
+                uint32_t acc = 0;
 #pragma unroll
-                    for (int t = NWORD - 1; t >= 0; t--) {
-                        const uint64_t x = w[t] ^ sp;
-                        const uint64_t z = (x - ones) & ~x & highs;
-                        if (z) {
-                            h = (uint32_t)t;
-                            j = (uint32_t)(__ffsll((unsigned long long)z) - 1) >> 3;
-                        }
-                    }
-                    const uint32_t rank = 8 * h + j;
-                    if (rank) {
-                        const uint64_t lowmask = j ? ((1ull << (8 * j)) - 1ull) : 0ull;
-                        const uint64_t himask = j == 7 ? 0ull : (~0ull << (8 * (j + 1)));
-                        uint64_t carry = s;
+                for (int t = 0; t < NR; t++)
+                    acc = bzx_udot4(((w[t] ^ sp) + 0x7f7f7f7fu) & 0x80808080u, 0x03020100u + 0x04040404u * (uint32_t)t, acc);
+                const uint32_t e = (TOT - acc) >> 4;                         // 8 * rank + 8: the bits that move
+                uint32_t prev = sp;
 #pragma unroll
-                        for (int t = 0; t < NWORD; t++) {
-                            const uint64_t cur = w[t];
-                            const uint64_t shifted = (cur << 8) | carry;
-                            const uint64_t patched = (cur & himask) | ((cur & lowmask) << 8) | carry;
-                            w[t] = (uint32_t)t < h ? shifted : ((uint32_t)t == h ? patched : cur);
-                            carry = cur >> 56;
-                        }
-                    }
-                    o[q] |= rank << (8 * k);
+                for (int t = 0; t < NR; t++) {
+                    const uint32_t cur = w[t];
+                    const uint32_t sh = bzx_alignbyte(cur, prev, 3);
+                    const uint32_t keep = bzx_keep_from(e, 32u * (uint32_t)t);
+                    w[t] = (cur & keep) | (sh & ~keep);
+                    prev = cur;
                 }
+                p = k ? p | (e << (8 * k - 3)) : e >> 3;
             }
+            o[q] = p - 0x01010101u;
         }
-        *reinterpret_cast<uint4 *>(R + i0) = make_uint4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<uint4 *>(H + i0) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
 
@@ -470,11 +472,17 @@ __global__ __launch_bounds__(MTF_NT) void bzx_mtf_kernel(BzxBatch B)
         // The first 8 list entries live in a register (byte 0 = front); deeper entries in LDS as 8-byte words,
         // searched and shifted one word at a time.
         if (have_chunk && n_in_use <= 32) {
-            const uint64_t *lst64 = reinterpret_cast<const uint64_t *>(lists + tid * stride);
-            if (n_in_use <= 8) mtf_ranks_regs<1>(H, H, c_lo, c_hi, lst64, m_seq);
-            else if (n_in_use <= 16) mtf_ranks_regs<2>(H, H, c_lo, c_hi, lst64, m_seq);
-            else if (n_in_use <= 24) mtf_ranks_regs<3>(H, H, c_lo, c_hi, lst64, m_seq);
-            else mtf_ranks_regs<4>(H, H, c_lo, c_hi, lst64, m_seq);
+            const uint32_t *lst32 = reinterpret_cast<const uint32_t *>(lists + tid * stride);
+            switch ((n_in_use + 3) / 4) {                       // registers of four entries
+            case 1: mtf_ranks_regs<1>(H, c_lo, c_hi, lst32, m_seq); break;
+            case 2: mtf_ranks_regs<2>(H, c_lo, c_hi, lst32, m_seq); break;
+            case 3: mtf_ranks_regs<3>(H, c_lo, c_hi, lst32, m_seq); break;
+            case 4: mtf_ranks_regs<4>(H, c_lo, c_hi, lst32, m_seq); break;
+            case 5: mtf_ranks_regs<5>(H, c_lo, c_hi, lst32, m_seq); break;
+            case 6: mtf_ranks_regs<6>(H, c_lo, c_hi, lst32, m_seq); break;
+            case 7: mtf_ranks_regs<7>(H, c_lo, c_hi, lst32, m_seq); break;
+            default: mtf_ranks_regs<8>(H, c_lo, c_hi, lst32, m_seq); break;
+            }
         } else if (have_chunk) {
             uint64_t *lst64 = reinterpret_cast<uint64_t *>(lists + tid * stride);
             uint64_t w = lst64[0];

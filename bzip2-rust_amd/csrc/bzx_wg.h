@@ -112,6 +112,37 @@ __device__ __forceinline__ uint32_t bzx_lane_prev(uint32_t v)
 }
 #endif
 
+// Byte-wise helpers of the MTF rank loop, one vector instruction each on the device, plain C++ on the emulator.
+// bzx_alignbyte(hi, lo, k): bytes k .. k+3 of the eight bytes hi:lo (k = 0..3; v_alignbyte_b32).
+// bzx_udot4(a, b, acc): acc + the sum of the four byte products a_i * b_i (v_dot4_u32_u8, no clamp).
+// bzx_rep4(s): the low byte of s in all four bytes (v_perm_b32; s * 0x01010101 is a quarter-rate multiply).
+// bzx_keep_from(x, lo): the mask of the bits from clamp(x - lo, 0, 31) upwards, lo a multiple of 32.  The device clamps x
+// to [lo, lo + 31] with one v_med3_u32 and lets the shifter drop the multiple of 32 (it reads five bits of the count);
+// written in C++ the compiler knows lo & 31 = 0 and turns the lower clamp into a compare and a select.
+#ifdef BZX_HIP_EMU
+__device__ inline uint32_t bzx_keep_from(uint32_t x, uint32_t lo) { return ~0u << (x < lo ? 0u : x - lo > 31u ? 31u : x - lo); }
+__device__ inline uint32_t bzx_alignbyte(uint32_t hi, uint32_t lo, uint32_t k)
+{
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (k & 3u)));
+}
+__device__ inline uint32_t bzx_udot4(uint32_t a, uint32_t b, uint32_t acc)
+{
+    for (int i = 0; i < 4; i++) acc += ((a >> (8 * i)) & 255u) * ((b >> (8 * i)) & 255u);
+    return acc;
+}
+__device__ inline uint32_t bzx_rep4(uint32_t s) { return (s & 255u) * 0x01010101u; }
+#else
+__device__ __forceinline__ uint32_t bzx_alignbyte(uint32_t hi, uint32_t lo, uint32_t k) { return __builtin_amdgcn_alignbyte(hi, lo, k); }
+__device__ __forceinline__ uint32_t bzx_udot4(uint32_t a, uint32_t b, uint32_t acc) { return __builtin_amdgcn_udot4(a, b, acc, false); }
+__device__ __forceinline__ uint32_t bzx_rep4(uint32_t s) { return __builtin_amdgcn_perm(s, s, 0u); }
+__device__ __forceinline__ uint32_t bzx_keep_from(uint32_t x, uint32_t lo)
+{
+    uint32_t c;
+    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(c) : "v"(x), "s"(lo), "v"(lo + 31u));
+    return ~0u << (c & 31u);
+}
+#endif
+
 __device__ __forceinline__ uint32_t bzx_lane() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint32_t bzx_wave() { return threadIdx.x >> 6; }
 
