@@ -578,8 +578,11 @@ struct DsSlot {                    // an output staging area: the verified bytes
     bool arrived = false;          // its copy-back has been awaited
 };
 
+enum DsMode { DS_STREAM, DS_INDEX, DS_SALVAGE };         // set once, in ds_begin
+
 struct bzx_dstream {
     bzx_ctx *ctx = nullptr;
+    DsMode mode = DS_STREAM;
     size_t max_chunk = 0, in_cap = 0;
     uint32_t cap_cand = 0, R = 0;
     DevMem<uint8_t> d_in[2], d_stage[2];
@@ -613,8 +616,8 @@ struct bzx_dstream {
     uint32_t comb = 0, level = 0;
     // round
     bool rd_active = false;            // the slabs hold chain blocks that have not been placed yet
-    uint32_t rd_nb = 0;
-    DsRec rd = {};                     // the chain part of the round's record
+    uint32_t rd_nb = 0, rd_c0 = 0, rd_c1 = 0;      // its blocks (slabs), its candidates [rd_c0, rd_c1)
+    DsRec rd = {};                     // the chain part of the round's record (DS_STREAM, DS_INDEX)
     // output: passes in flight or being delivered, oldest first
     DsSlot slot[2];
     uint32_t q_head = 0, q_n = 0;
@@ -624,15 +627,13 @@ struct bzx_dstream {
     std::string pend_text, err_text;
     bzx_dstream_info info = {};
     float ms = 0.f;
-    // index mode (bzx_index_*): nothing is copied back or handed out; the placed blocks' figures come with the record
-    bzx_index *ix = nullptr;
+    // DS_INDEX (bzx_index_*): nothing is copied back or handed out; the placed blocks' figures come with the record
+    bzx_index *ix = nullptr;           // where entries and gaps go (DS_INDEX, DS_SALVAGE)
     DevMem<uint32_t> d_meta;
     DevMem<DsIxRec> d_ix;
     PinMem<DsIxRec> h_ix;
-    // salvage mode (bzx_salvage_*): the index mode's memory, with the tables of the salvage kernels in place of d_meta / d_ix
-    bool salvage = false;
+    // DS_SALVAGE (bzx_salvage_*): the index mode's memory, with the tables of the salvage kernels in place of d_meta / d_ix
     DsSvState sv = {};                 // the walk's state between passes and windows
-    uint32_t sv_c0 = 0, sv_c1 = 0;     // the round's candidates
     DevMem<DsSvCand> d_svc;
     PinMem<DsSvCand> h_svc;
     DevMem<uint32_t> d_verdict;
@@ -667,9 +668,10 @@ extern "C" void bzx_dstream_end(bzx_dstream *s)
     delete s;
 }
 
-// index: the stream of a bzx_index -- one output staging area, none on the host, and the tables of the entries.
-static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bool salvage, bzx_dstream **out)
+// DS_INDEX, DS_SALVAGE: the stream of a bzx_index -- one output staging area, none on the host, and the mode's tables.
+static int ds_begin(bzx_ctx *ctx, size_t max_chunk, DsMode mode, bzx_dstream **out)
 {
+    const bool index = mode != DS_STREAM;
     if (!ctx || !out) return BZX_E_PARAM;
     *out = nullptr;
     std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
@@ -682,6 +684,7 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bool salvage, bz
     bzx_dstream *s = new (std::nothrow) bzx_dstream();
     if (!s) return BZX_E_NOMEM;
     s->ctx = ctx;
+    s->mode = mode;
     s->max_chunk = max_chunk;
     s->R = ctx->cap_slabs;
     s->in_cap = DS_CARRY_MAX + max_chunk + 64;
@@ -701,7 +704,7 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bool salvage, bz
         ok = dmal(s->d_in[i], s->in_cap) && (index && i ? true : dmal(s->d_stage[i], DS_STAGE_BYTES)) &&
              (index || hmal(s->h_stage[i], DS_STAGE_BYTES)) &&
              hipEventCreateWithFlags(&s->ev_d2h[i], hipEventDisableTiming) == hipSuccess;
-    if (salvage)                                             // (zeroed as d_ix below)
+    if (mode == DS_SALVAGE)                                  // (zeroed as d_ix below)
         ok = ok && dmal(s->d_svc, 2 * R * sizeof(DsSvCand)) && hmal(s->h_svc, 2 * R * sizeof(DsSvCand)) &&
              dmal(s->d_verdict, R * 4) && dmal(s->d_ent, R * sizeof(DsSvEnt)) && hmal(s->h_ent, R * sizeof(DsSvEnt)) &&
              dmal(s->d_gap, 2 * R * sizeof(bzx_gap)) && hmal(s->h_gap, 2 * R * sizeof(bzx_gap)) &&
@@ -726,7 +729,6 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bool salvage, bz
         ctx->err = "bzx_dstream_begin: device or pinned allocation failed";
         return BZX_E_NOMEM;
     }
-    s->salvage = salvage;
     s->info.slabs = s->R;
     s->info.device_bytes = dev;
     s->info.pinned_bytes = pin;
@@ -737,7 +739,7 @@ static int ds_begin(bzx_ctx *ctx, size_t max_chunk, bool index, bool salvage, bz
 
 extern "C" int bzx_dstream_begin(bzx_ctx *ctx, size_t max_chunk, bzx_dstream **out)
 {
-    return ds_begin(ctx, max_chunk, false, false, out);
+    return ds_begin(ctx, max_chunk, DS_STREAM, out);
 }
 
 extern "C" int bzx_dstream_get_info(const bzx_dstream *s, bzx_dstream_info *out)
@@ -825,8 +827,7 @@ static void ds_round_complete(bzx_dstream *s)
     }
 }
 
-// ---- salvage passes ----------------------------------------------------------------------------------------------------
-// The candidates of the window are used up: the rest of a window whose scan was cut short, the next window, or -- behind
+// Salvage: the candidates of the window are used up: the rest of a window whose scan was cut short, the next window, or -- behind
 // the last byte of the input -- the end of the walk.
 static void sv_used_up(bzx_dstream *s)
 {
@@ -855,94 +856,99 @@ static void sv_used_up(bzx_dstream *s)
     s->finished = true;
 }
 
-// ds_pass of the salvage mode: a new round decodes its candidates and sorts them into classes; every pass places, expands
-// and checks the next trials and lets the walk go on over the round's candidates.  ONE synchronisation.
-static int sv_pass(bzx_dstream *s)
+// ---- what a mode contributes to a pass: its kernels, its copies back, the digest of its record ------------------------
+static bzx_index_entry ds_entry(uint64_t bit, uint64_t out_off, uint32_t out_len, uint32_t crc, uint32_t img_bits,
+                                uint32_t stream, uint32_t level)
+{
+    bzx_index_entry e;
+    memset(&e, 0, sizeof(e));
+    e.bit = bit;
+    e.out_off = out_off;
+    e.out_len = out_len;
+    e.crc = crc;
+    e.img_bits = img_bits;
+    e.stream = stream;
+    e.level = (uint8_t)level;
+    return e;
+}
+
+// Behind the decode of a new round: the chain walk from the carried bit, or (salvage) every candidate into its class.
+static void ds_launch_chain(bzx_dstream *s)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const uint32_t final = s->wfinal ? 1u : 0u;
+    if (s->mode == DS_SALVAGE)
+        hipLaunchKernelGGL(bzx_sv_trial_kernel, dim3(1), dim3(64), 0, st, ctx->B, s->wlen, s->wbase * 8, final, s->d_cand.get(),
+                           s->rd_c0, s->rd_c1, s->d_svc.get(), s->d_chain.get(), s->d_verdict.get(), s->d_svrec.get());
+    else
+        hipLaunchKernelGGL(bzx_ds_chain_kernel, dim3(1), dim3(64), 0, st, ctx->B, s->wptr, s->wlen, s->wbase * 8, final,
+                           s->d_cand.get(), s->rd_c0, s->rd_c1, s->chain_bit, s->comb, s->level, s->d_chain.get(), s->d_rec.get(),
+                           s->d_meta.get());
+}
+
+static void ds_launch_layout(bzx_dstream *s, uint32_t q)
+{
+    bzx_ctx *ctx = s->ctx;
+    if (s->mode == DS_SALVAGE)
+        hipLaunchKernelGGL(bzx_sv_layout_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->B, s->d_chain.get(), s->d_stage[0].get(),
+                           (uint64_t)DS_STAGE_BYTES, s->d_dst.get(), s->d_svrec.get());
+    else
+        hipLaunchKernelGGL(bzx_ds_layout_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->B, s->d_chain.get(), s->d_stage[q].get(),
+                           (uint64_t)DS_STAGE_BYTES, s->d_dst.get(), s->d_rec.get());
+}
+
+// Behind the CRCs of the nb blocks a pass may place: the verdict, then what the mode leaves for the host next to its
+// record -- the index's entries, or the salvage walk over the round's candidates (which runs without a block too).
+static int ds_launch_verdict(bzx_dstream *s, uint32_t q, uint32_t nb)
 {
     bzx_ctx *ctx = s->ctx;
     hipStream_t st = ctx->stream;
     BzxBatch &B = ctx->B;
-    const bool fresh = !s->rd_active;
-    const uint32_t final = s->wfinal ? 1u : 0u;
-    if (fresh) {
-        if (s->need_scan) {
-            const int rc = ds_scan(s);
-            if (rc) return rc;
-        }
-        while (s->ci < s->ncand && (s->h_cand[s->ci] >> 1) < s->chain_bit) s->ci++;
-        if (s->ci == s->ncand) {
-            sv_used_up(s);
-            return BZX_OK;
-        }
-        const uint32_t c0 = s->ci;
-        uint32_t c1 = c0, nb = 0, ne = 0;
-        for (; c1 < s->ncand; c1++) {
-            if (s->h_cand[c1] & 1u) {
-                if (ne == s->R) break;
-                ne++;
-                continue;
-            }
-            if (nb == s->R) break;
-            s->h_svc[c1 - c0].slab = nb;
-            s->h_src[nb++] = BzxDcSrc{s->wptr, s->wlen, (s->h_cand[c1] >> 1) - s->wbase * 8};
-        }
-        s->ci = c1;
-        s->sv_c0 = c0;
-        s->sv_c1 = c1;
-        s->rd_nb = nb;
-        s->sv.k = 0;
-        B.nblk = nb;
-        B.blk_first = 0;
-        B.blk_step = 1;
-        (void)hipEventRecord(ctx->ev[5], st);
-        if (nb) {
-            HIP_TRY(ctx, hipMemcpyAsync(s->d_src, s->h_src, nb * sizeof(BzxDcSrc), hipMemcpyHostToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(s->d_svc, s->h_svc, (c1 - c0) * sizeof(DsSvCand), hipMemcpyHostToDevice, st));
-            bzx_launch_dc_decode(B, s->d_src, st);
-        }
-        hipLaunchKernelGGL(bzx_sv_trial_kernel, dim3(1), dim3(64), 0, st, B, s->wlen, s->wbase * 8, final, s->d_cand.get(), c0, c1,
-                           s->d_svc.get(), s->d_chain.get(), s->d_verdict.get(), s->d_svrec.get());
-        if (nb) bzx_launch_dc_ibwt(B, ctx->d_in, st);
-    } else {
-        B.nblk = s->rd_nb;
-        B.blk_first = 0;
-        B.blk_step = 1;
-        (void)hipEventRecord(ctx->ev[5], st);
-    }
-    const uint32_t nb = s->rd_nb;
-    if (nb) {
-        hipLaunchKernelGGL(bzx_sv_layout_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_stage[0].get(),
-                           (uint64_t)DS_STAGE_BYTES, s->d_dst.get(), s->d_svrec.get());
-        bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
-        bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
-        hipLaunchKernelGGL(bzx_sv_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_got.get(), s->d_verdict.get(),
+    if (s->mode == DS_SALVAGE) {
+        if (nb)
+            hipLaunchKernelGGL(bzx_sv_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_got.get(), s->d_verdict.get(),
+                               s->d_svrec.get());
+        hipLaunchKernelGGL(bzx_sv_walk_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8, s->wfinal ? 1u : 0u,
+                           s->d_cand.get(), s->rd_c0, s->rd_c1, s->d_svc.get(), s->d_verdict.get(), s->sv, s->d_ent.get(), s->d_gap.get(),
                            s->d_svrec.get());
+        return BZX_OK;
     }
-    hipLaunchKernelGGL(bzx_sv_walk_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8, final, s->d_cand.get(),
-                       s->sv_c0, s->sv_c1, s->d_svc.get(), s->d_verdict.get(), s->sv, s->d_ent.get(), s->d_gap.get(), s->d_svrec.get());
-    HIP_TRY(ctx, hipGetLastError());
+    if (!nb) return BZX_OK;
+    hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_dst.get(), s->d_got.get(), s->d_stage[q].get(),
+                       s->d_rec.get());
+    if (s->mode == DS_INDEX) {
+        hipLaunchKernelGGL(bzx_ds_index_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_meta.get(), s->wbase * 8, s->d_rec.get(),
+                           s->d_ix.get());
+        // (the round's share of the table; the pass wrote its first placed - pass_j0 entries, the host reads
+        // r.good <= that many, the rest is what bzx_index_begin zeroed or an earlier pass left)
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, nb * sizeof(DsIxRec), hipMemcpyDeviceToHost, st));
+    }
+    return BZX_OK;
+}
+
+static int ds_copy_record(bzx_dstream *s)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    if (s->mode != DS_SALVAGE) {
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_rec, s->d_rec, sizeof(DsRec), hipMemcpyDeviceToHost, st));
+        return BZX_OK;
+    }
     // (tables of fixed size: the host reads the first nent / ngap of them, the rest is what begin zeroed or a pass left)
     HIP_TRY(ctx, hipMemcpyAsync(s->h_ent, s->d_ent, (size_t)s->R * sizeof(DsSvEnt), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(s->h_gap, s->d_gap, (size_t)2 * s->R * sizeof(bzx_gap), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(s->h_svrec, s->d_svrec, sizeof(DsSvRec), hipMemcpyDeviceToHost, st));
-    (void)hipEventRecord(ctx->ev[7], st);
-    HIP_TRY(ctx, hipStreamSynchronize(st));                  // the pass's one synchronisation
-    s->info.rounds++;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[7]) == hipSuccess) s->ms += ms;
+    return BZX_OK;
+}
+
+// Salvage: the walk's entries and closed gaps are appended; its state says where the round and the window stand.
+static int sv_digest(bzx_dstream *s)
+{
     const DsSvRec &r = *s->h_svrec;
     for (uint32_t j = 0; j < r.nent; j++) {
         const DsSvEnt &x = s->h_ent[j];
-        bzx_index_entry e;
-        memset(&e, 0, sizeof(e));
-        e.bit = x.bit;
-        e.out_off = x.out_off;
-        e.out_len = x.out_len;
-        e.crc = x.crc;
-        e.img_bits = x.img_bits;
-        e.stream = x.stream;
-        e.level = (uint8_t)x.level;
-        s->ix->entries.push_back(e);
+        s->ix->entries.push_back(ds_entry(x.bit, x.out_off, x.out_len, x.crc, x.img_bits, x.stream, x.level));
     }
     s->ix->gaps.insert(s->ix->gaps.end(), s->h_gap.get(), s->h_gap.get() + r.ngap);
     s->sv = r.st;
@@ -955,94 +961,21 @@ static int sv_pass(bzx_dstream *s)
     return BZX_OK;
 }
 
-// One pass: a new round (decode, chain, inverse BWT) when no decoded chain block waits in the slabs, then layout,
-// expansion, CRCs and verdict into the staging area `q`, the record, ONE synchronisation, and the copy-back of the
-// verified bytes on its own stream.
-static int ds_pass(bzx_dstream *s, uint32_t q)
+// Stream and index: the verified blocks become entries, or their bytes start the way out of staging area `q`; the first
+// block that did not verify ends the stream, the last placed block of the chain ends the round.
+static int ds_digest(bzx_dstream *s, uint32_t q, bool fresh)
 {
-    if (s->salvage) return sv_pass(s);
     bzx_ctx *ctx = s->ctx;
-    hipStream_t st = ctx->stream;
-    BzxBatch &B = ctx->B;
-    const bool fresh = !s->rd_active;
-    if (fresh) {
-        if (s->need_scan) {
-            const int rc = ds_scan(s);
-            if (rc) return rc;
-        }
-        while (s->ci < s->ncand && (s->h_cand[s->ci] >> 1) < s->chain_bit) s->ci++;
-        if (s->ci == s->ncand) {
-            ds_no_magic(s, true);
-            return BZX_OK;
-        }
-        const uint32_t c0 = s->ci;
-        uint32_t c1 = c0, nb = 0;
-        for (; c1 < s->ncand; c1++) {
-            if (s->h_cand[c1] & 1u) continue;
-            if (nb == s->R) break;
-            s->h_src[nb++] = BzxDcSrc{s->wptr, s->wlen, (s->h_cand[c1] >> 1) - s->wbase * 8};
-        }
-        s->ci = c1;
-        s->rd_nb = nb;
-        B.nblk = nb;
-        B.blk_first = 0;
-        B.blk_step = 1;
-        (void)hipEventRecord(ctx->ev[5], st);
-        if (nb) {
-            HIP_TRY(ctx, hipMemcpyAsync(s->d_src, s->h_src, nb * sizeof(BzxDcSrc), hipMemcpyHostToDevice, st));
-            bzx_launch_dc_decode(B, s->d_src, st);
-        }
-        hipLaunchKernelGGL(bzx_ds_chain_kernel, dim3(1), dim3(64), 0, st, B, s->wptr, s->wlen, s->wbase * 8,
-                           s->wfinal ? 1u : 0u, s->d_cand.get(), c0, c1, s->chain_bit, s->comb, s->level, s->d_chain.get(), s->d_rec.get(),
-                           s->d_meta.get());
-        if (nb) bzx_launch_dc_ibwt(B, ctx->d_in, st);
-    } else {
-        B.nblk = s->rd_nb;
-        B.blk_first = 0;
-        B.blk_step = 1;
-        (void)hipEventRecord(ctx->ev[5], st);
-    }
-    const uint32_t nb = s->rd_nb;
-    if (nb) {
-        hipLaunchKernelGGL(bzx_ds_layout_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_stage[q].get(),
-                           (uint64_t)DS_STAGE_BYTES, s->d_dst.get(), s->d_rec.get());
-        bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
-        bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
-        hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_dst.get(), s->d_got.get(), s->d_stage[q].get(),
-                           s->d_rec.get());
-        if (s->ix) {
-            hipLaunchKernelGGL(bzx_ds_index_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_meta.get(), s->wbase * 8, s->d_rec.get(),
-                               s->d_ix.get());
-            // (the round's share of the table; the pass wrote its first placed - pass_j0 entries, the host reads
-            // r.good <= that many, the rest is what bzx_index_begin zeroed or an earlier pass left)
-            HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, nb * sizeof(DsIxRec), hipMemcpyDeviceToHost, st));
-        }
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s->h_rec, s->d_rec, sizeof(DsRec), hipMemcpyDeviceToHost, st));
-    (void)hipEventRecord(ctx->ev[7], st);
-    HIP_TRY(ctx, hipStreamSynchronize(st));                  // the pass's one synchronisation
-    s->info.rounds++;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[7]) == hipSuccess) s->ms += ms;
     const DsRec r = *s->h_rec;
     if (fresh) {
         s->rd = r;
         s->rd_active = true;
     }
-    if (s->ix) {                                             // the verified blocks become entries; their bytes stay
+    if (s->mode == DS_INDEX) {                               // their bytes stay
         for (uint32_t j = 0; j < r.good; j++) {
             const DsIxRec &x = s->h_ix[j];
-            bzx_index_entry e;
-            memset(&e, 0, sizeof(e));
-            e.bit = x.bit;
-            e.out_off = s->info.out_bytes;
-            e.out_len = x.out_len;
-            e.crc = x.crc;
-            e.img_bits = x.img_bits;
-            e.stream = s->info.nstreams + (x.meta >> 4);
-            e.level = (uint8_t)(x.meta & 15u);
-            s->ix->entries.push_back(e);
+            s->ix->entries.push_back(ds_entry(x.bit, s->info.out_bytes, x.out_len, x.crc, x.img_bits,
+                                              s->info.nstreams + (x.meta >> 4), x.meta & 15u));
             s->info.out_bytes += x.out_len;
         }
     } else if (r.good_bytes) {                               // the verified bytes travel beside the next pass
@@ -1055,16 +988,108 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
     }
     const uint32_t first_blk = s->info.nblk;
     s->info.nblk += r.good;
-    if (r.good < r.placed - r.pass_j0) {
-        ds_fail(s, dc_why_text(DC_WHY_BLOCK_CRC, first_blk + r.good));
-        return BZX_OK;
-    }
-    if (r.placed < r.nchain && r.lay_err) {
-        ds_fail(s, dc_why_text(DC_WHY_IBWT));
-        return BZX_OK;
-    }
-    if (r.placed >= r.nchain) ds_round_complete(s);
+    if (r.good < r.placed - r.pass_j0) ds_fail(s, dc_why_text(DC_WHY_BLOCK_CRC, first_blk + r.good));
+    else if (r.placed < r.nchain && r.lay_err) ds_fail(s, dc_why_text(DC_WHY_IBWT));
+    else if (r.placed >= r.nchain) ds_round_complete(s);
     return BZX_OK;
+}
+
+// One pass, in every mode: a new round (scan if the window needs one, decode of the next candidates, chain, inverse BWT)
+// when no decoded block waits in the slabs, then layout, expansion, CRCs and verdict into the staging area `q`, the
+// record, ONE synchronisation, and the host's digest of the record (which starts the copy-back of the verified bytes on
+// its own stream).  A round takes at most R block candidates; salvage, whose kernels look at the end-of-stream
+// candidates too, cuts it at R of those as well and tells the device which slab decodes which candidate.
+static int ds_pass(bzx_dstream *s, uint32_t q)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    BzxBatch &B = ctx->B;
+    const bool sv = s->mode == DS_SALVAGE, fresh = !s->rd_active;
+    if (fresh) {
+        if (s->need_scan) {
+            const int rc = ds_scan(s);
+            if (rc) return rc;
+        }
+        while (s->ci < s->ncand && (s->h_cand[s->ci] >> 1) < s->chain_bit) s->ci++;
+        if (s->ci == s->ncand) {
+            if (sv) sv_used_up(s);
+            else ds_no_magic(s, true);
+            return BZX_OK;
+        }
+        const uint32_t c0 = s->ci;
+        uint32_t c1 = c0, nb = 0, ne = 0;
+        for (; c1 < s->ncand; c1++) {
+            if (s->h_cand[c1] & 1u) {
+                if (sv && ne == s->R) break;
+                ne++;
+                continue;
+            }
+            if (nb == s->R) break;
+            if (sv) s->h_svc[c1 - c0].slab = nb;
+            s->h_src[nb++] = BzxDcSrc{s->wptr, s->wlen, (s->h_cand[c1] >> 1) - s->wbase * 8};
+        }
+        s->ci = c1;
+        s->rd_c0 = c0;
+        s->rd_c1 = c1;
+        s->rd_nb = nb;
+        s->sv.k = 0;                                         // (salvage: the walk stands before the round's first candidate)
+    }
+    const uint32_t nb = s->rd_nb, c0 = s->rd_c0, c1 = s->rd_c1;
+    B.nblk = nb;
+    B.blk_first = 0;
+    B.blk_step = 1;
+    (void)hipEventRecord(ctx->ev[5], st);
+    if (fresh) {
+        if (nb) {
+            HIP_TRY(ctx, hipMemcpyAsync(s->d_src, s->h_src, nb * sizeof(BzxDcSrc), hipMemcpyHostToDevice, st));
+            if (sv) HIP_TRY(ctx, hipMemcpyAsync(s->d_svc, s->h_svc, (c1 - c0) * sizeof(DsSvCand), hipMemcpyHostToDevice, st));
+            bzx_launch_dc_decode(B, s->d_src, st);
+        }
+        ds_launch_chain(s);
+        if (nb) bzx_launch_dc_ibwt(B, ctx->d_in, st);
+    }
+    if (nb) {
+        ds_launch_layout(s, q);
+        bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
+        bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
+    }
+    int rc = ds_launch_verdict(s, q, nb);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipGetLastError());
+    rc = ds_copy_record(s);
+    if (rc) return rc;
+    (void)hipEventRecord(ctx->ev[7], st);
+    HIP_TRY(ctx, hipStreamSynchronize(st));                  // the pass's one synchronisation
+    s->info.rounds++;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[7]) == hipSuccess) s->ms += ms;
+    return sv ? sv_digest(s) : ds_digest(s, q, fresh);
+}
+
+// The first window is there: the stream's header, and where the chain (or the salvage walk: include/bzx.h) starts.
+static void ds_start(bzx_dstream *s)
+{
+    s->started = true;
+    if (s->mode == DS_SALVAGE) {
+        s->sv = DsSvState{};
+        s->sv.level = s->info.in_bytes >= 4 ? bzx_bzh_level(s->head) : 0u;
+        if (s->sv.level) {
+            s->sv.P = s->sv.S = 32;
+            s->sv.clean = 1;
+        } else {
+            s->sv.level = 9;
+            s->sv.gap = bzx_gap{0, 0, 0, 0u, BZX_GAP_HEADER};
+            s->sv.gap_open = 1;
+        }
+        s->chain_bit = s->sv.S;
+    } else if (s->wlen < 14) {
+        ds_fail(s, dc_why_text(DC_WHY_SHORT));
+    } else if (!(s->level = bzx_bzh_level(s->head))) {
+        ds_fail(s, dc_why_text(DC_WHY_NO_HEADER));
+    } else {
+        s->chain_bit = 32;
+        s->comb = 0;
+    }
 }
 
 // The accepted bytes become the window: the carry of the window before moves in front of them.
@@ -1099,31 +1124,7 @@ static int ds_promote(bzx_dstream *s)
     s->acc = a ^ 1u;
     s->acc_fill = 0;
     s->info.windows++;
-    if (!s->started && s->salvage) {                         // the start of the walk (include/bzx.h)
-        s->started = true;
-        s->sv = DsSvState{};
-        s->sv.level = s->info.in_bytes >= 4 ? bzx_bzh_level(s->head) : 0u;
-        if (s->sv.level) {
-            s->sv.P = s->sv.S = 32;
-            s->sv.clean = 1;
-        } else {
-            s->sv.level = 9;
-            s->sv.gap = bzx_gap{0, 0, 0, 0u, BZX_GAP_HEADER};
-            s->sv.gap_open = 1;
-        }
-        s->chain_bit = s->sv.S;
-    }
-    if (!s->started) {
-        s->started = true;
-        if (s->wlen < 14) {
-            ds_fail(s, dc_why_text(DC_WHY_SHORT));
-        } else if (!(s->level = bzx_bzh_level(s->head))) {
-            ds_fail(s, dc_why_text(DC_WHY_NO_HEADER));
-        } else {
-            s->chain_bit = 32;
-            s->comb = 0;
-        }
-    }
+    if (!s->started) ds_start(s);
     return BZX_OK;
 }
 
@@ -1202,10 +1203,11 @@ static int ds_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, si
     }
 }
 
-extern "C" int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, size_t *consumed, uint8_t *out,
-                                size_t cap, size_t *produced, int *done)
+// The feed call of every mode (the callers have checked their arguments): the lock, a latched error again, ds_feed, and
+// the wait that lets the caller reuse its input buffer.
+static int ds_feed_call(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, size_t *consumed, uint8_t *out, size_t cap,
+                        size_t *produced, int *done)
 {
-    if (!s || !s->ctx || !consumed || !produced || !done || (len && !bz2) || (cap && !out)) return BZX_E_PARAM;
     bzx_ctx *ctx = s->ctx;
     std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
     *consumed = 0;
@@ -1215,9 +1217,15 @@ extern "C" int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, 
         ctx->err = s->err_text;
         return s->err_rc;
     }
-    if (s->done) {
+    if (s->done && s->mode == DS_STREAM) {
         ctx->err = "bzx_dstream_feed: the stream is done";
         return BZX_E_STATE;
+    }
+    if (s->done) {                                           // bytes behind the last stream: counted, not looked at
+        s->info.in_bytes += len;
+        *consumed = len;
+        *done = 1;
+        return BZX_OK;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     bool copied = false;
@@ -1240,7 +1248,14 @@ extern "C" int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, 
     return rc;
 }
 
-// ---- bzx_index_*: the same machine with nothing handed out ------------------------------------------------------------
+extern "C" int bzx_dstream_feed(bzx_dstream *s, const uint8_t *bz2, size_t len, int final, size_t *consumed, uint8_t *out,
+                                size_t cap, size_t *produced, int *done)
+{
+    if (!s || !s->ctx || !consumed || !produced || !done || (len && !bz2) || (cap && !out)) return BZX_E_PARAM;
+    return ds_feed_call(s, bz2, len, final, consumed, out, cap, produced, done);
+}
+
+// ---- bzx_index_*, bzx_salvage_*: the same machine with nothing handed out -----------------------------------------------
 extern "C" void bzx_index_end(bzx_index *ix)
 {
     if (!ix) return;
@@ -1251,13 +1266,13 @@ extern "C" void bzx_index_end(bzx_index *ix)
     delete ix;
 }
 
-static int ix_begin(bzx_ctx *ctx, size_t max_chunk, bool salvage, bzx_index **out)
+static int ix_begin(bzx_ctx *ctx, size_t max_chunk, DsMode mode, bzx_index **out)
 {
     if (!ctx || !out) return BZX_E_PARAM;
     *out = nullptr;
     bzx_index *ix = new (std::nothrow) bzx_index();
     if (!ix) return BZX_E_NOMEM;
-    const int rc = ds_begin(ctx, max_chunk, true, salvage, &ix->s);
+    const int rc = ds_begin(ctx, max_chunk, mode, &ix->s);
     if (rc) {
         delete ix;
         return rc;
@@ -1269,51 +1284,19 @@ static int ix_begin(bzx_ctx *ctx, size_t max_chunk, bool salvage, bzx_index **ou
 
 extern "C" int bzx_index_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out)
 {
-    return ix_begin(ctx, max_chunk, false, out);
+    return ix_begin(ctx, max_chunk, DS_INDEX, out);
 }
 
 extern "C" int bzx_salvage_begin(bzx_ctx *ctx, size_t max_chunk, bzx_index **out)
 {
-    return ix_begin(ctx, max_chunk, true, out);
+    return ix_begin(ctx, max_chunk, DS_SALVAGE, out);
 }
 
 extern "C" int bzx_index_feed(bzx_index *ix, const uint8_t *bz2, size_t len, int final, size_t *consumed, int *done)
 {
     if (!ix || !ix->s || !ix->s->ctx || !consumed || !done || (len && !bz2)) return BZX_E_PARAM;
-    bzx_dstream *s = ix->s;
-    bzx_ctx *ctx = s->ctx;
-    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
-    *consumed = 0;
-    *done = 0;
-    if (s->err_rc) {
-        ctx->err = s->err_text;
-        return s->err_rc;
-    }
-    if (s->done) {                                           // bytes behind the last stream: counted, not looked at
-        s->info.in_bytes += len;
-        *consumed = len;
-        *done = 1;
-        return BZX_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    bool copied = false;
     size_t produced = 0;
-    int rc;
-    try {
-        rc = ds_feed(s, bz2, len, final, consumed, nullptr, 0, &produced, done, &copied);
-    } catch (const std::bad_alloc &) {                       // (nothing may unwind across the C ABI)
-        ctx->err = "out of host memory";
-        rc = BZX_E_NOMEM;
-    }
-    if (copied && hipStreamSynchronize(s->s_h2d) != hipSuccess && !rc) {
-        ctx->err = "hipStreamSynchronize(input copy) failed";
-        rc = BZX_E_HIP;
-    }
-    if (rc && !s->err_rc) {
-        s->err_rc = rc;
-        s->err_text = ctx->err;
-    }
-    return rc;
+    return ds_feed_call(ix->s, bz2, len, final, consumed, nullptr, 0, &produced, done);
 }
 
 extern "C" int bzx_index_get(const bzx_index *ix, const bzx_index_entry **entries, bzx_index_info *info)
@@ -1329,43 +1312,6 @@ extern "C" int bzx_index_get(const bzx_index *ix, const bzx_index_entry **entrie
     return BZX_OK;
 }
 
-extern "C" int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries,
-                                      uint64_t cap_entries, bzx_index_info *info)
-{
-    if (!ctx || !info || (len && !bz2) || (cap_entries && !entries)) return BZX_E_PARAM;
-    memset(info, 0, sizeof(*info));
-    bzx_index *ix = nullptr;
-    int rc = bzx_index_begin(ctx, std::min<size_t>(std::max<size_t>(len, DS_MIN_CHUNK), (size_t)64 << 20), &ix);
-    if (rc) return rc;
-    size_t pos = 0;
-    int done = 0;
-    while (!rc && !(done && pos == len)) {
-        size_t used = 0;
-        rc = bzx_index_feed(ix, bz2 + pos, len - pos, 1, &used, &done);
-        pos += used;
-        if (!rc && !used && !done) {                         // (a final feed consumes or finishes)
-            ctx->err = "bzx_index_build_buffer: the feed loop made no progress";
-            rc = BZX_E_STATE;
-        }
-    }
-    const bzx_index_entry *e = nullptr;
-    const std::string why = ctx->err;
-    if (bzx_index_get(ix, &e, info) == BZX_OK) {
-        const uint64_t k = std::min<uint64_t>(info->nblk, cap_entries);
-        if (k) memcpy(entries, e, (size_t)k * sizeof(bzx_index_entry));
-        if (!rc && info->nblk > cap_entries) {
-            rc = BZX_E_OUTBUF;
-            bzx_index_end(ix);
-            ctx->err = "bzx_index_build_buffer: more blocks than cap_entries";
-            return rc;
-        }
-    }
-    bzx_index_end(ix);
-    if (rc) ctx->err = why;
-    return rc;
-}
-
-// ---- bzx_salvage_*: the calls over a whole buffer ---------------------------------------------------------------------------
 extern "C" int bzx_index_get_gaps(const bzx_index *ix, const bzx_gap **gaps, uint64_t *ngaps)
 {
     if (!ix || !ix->s || !ix->s->ctx || !gaps || !ngaps) return BZX_E_PARAM;
@@ -1375,12 +1321,15 @@ extern "C" int bzx_index_get_gaps(const bzx_index *ix, const bzx_gap **gaps, uin
     return BZX_OK;
 }
 
-// begin, a loop over feed, and the lists as vectors.
-static int sv_build(bzx_ctx *ctx, const uint8_t *bz2, size_t len, std::vector<bzx_index_entry> &entries, bzx_index_info *info,
-                    std::vector<bzx_gap> &gaps)
+// ---- the calls over a whole buffer ----------------------------------------------------------------------------------------
+// Begin, a loop over feed, the lists and `info`, end.  The lists leave the handle by swap, so nothing is allocated behind
+// the feed loop.  A run that failed hands nothing out, except in the index mode: there the entries and `info` describe
+// the verified prefix, and the feed's code and text are the call's.
+static int ix_build(bzx_ctx *ctx, DsMode mode, const uint8_t *bz2, size_t len, std::vector<bzx_index_entry> &entries,
+                    bzx_index_info *info, std::vector<bzx_gap> &gaps)
 {
     bzx_index *ix = nullptr;
-    int rc = bzx_salvage_begin(ctx, std::min<size_t>(std::max<size_t>(len, DS_MIN_CHUNK), (size_t)64 << 20), &ix);
+    int rc = ix_begin(ctx, std::min<size_t>(std::max<size_t>(len, DS_MIN_CHUNK), (size_t)64 << 20), mode, &ix);
     if (rc) return rc;
     size_t pos = 0;
     int done = 0;
@@ -1389,39 +1338,43 @@ static int sv_build(bzx_ctx *ctx, const uint8_t *bz2, size_t len, std::vector<bz
         rc = bzx_index_feed(ix, bz2 + pos, len - pos, 1, &used, &done);
         pos += used;
         if (!rc && !used && !done) {                         // (a final feed consumes or finishes)
-            ctx->err = "bzx_salvage: the feed loop made no progress";
+            ctx->err = mode == DS_INDEX ? "bzx_index_build_buffer: the feed loop made no progress"
+                                        : "bzx_salvage: the feed loop made no progress";
             rc = BZX_E_STATE;
         }
     }
     const std::string why = ctx->err;
-    if (!rc) {
-        try {
-            const bzx_index_entry *e = nullptr;
-            const bzx_gap *g = nullptr;
-            uint64_t ng = 0;
-            rc = bzx_index_get(ix, &e, info);
-            if (!rc) rc = bzx_index_get_gaps(ix, &g, &ng);
-            if (!rc) {
-                entries.assign(e, e + info->nblk);
-                gaps.assign(g, g + ng);
-            }
-        } catch (const std::bad_alloc &) {
-            rc = BZX_E_NOMEM;
-        }
+    const bzx_index_entry *e = nullptr;
+    if ((!rc || mode == DS_INDEX) && bzx_index_get(ix, &e, info) == BZX_OK) {
+        entries.swap(ix->entries);
+        gaps.swap(ix->gaps);
     }
     bzx_index_end(ix);
-    if (rc) ctx->err = rc == BZX_E_NOMEM && why.empty() ? "out of host memory" : why;
+    if (rc) ctx->err = why;
     return rc;
 }
 
-static int sv_gaps_out(bzx_ctx *ctx, const std::vector<bzx_gap> &v, bzx_gap *gaps, uint64_t cap_gaps, uint64_t *ngaps)
+// The first min(size, cap) elements of a list go out; a list that did not fit turns a call that succeeded so far (rc)
+// into BZX_E_OUTBUF with `text`.
+template <typename T>
+static int ix_copy_out(bzx_ctx *ctx, int rc, const std::vector<T> &v, T *out, uint64_t cap, const char *text)
 {
-    *ngaps = v.size();
-    const uint64_t k = std::min<uint64_t>(v.size(), cap_gaps);
-    if (k) memcpy(gaps, v.data(), (size_t)k * sizeof(bzx_gap));
-    if (v.size() <= cap_gaps) return BZX_OK;
-    ctx->err = "bzx_salvage: more gaps than cap_gaps";
+    const uint64_t k = std::min<uint64_t>(v.size(), cap);
+    if (k) memcpy(out, v.data(), (size_t)k * sizeof(T));
+    if (rc || v.size() <= cap) return rc;
+    ctx->err = text;
     return BZX_E_OUTBUF;
+}
+
+extern "C" int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries,
+                                      uint64_t cap_entries, bzx_index_info *info)
+{
+    if (!ctx || !info || (len && !bz2) || (cap_entries && !entries)) return BZX_E_PARAM;
+    memset(info, 0, sizeof(*info));
+    std::vector<bzx_index_entry> e;
+    std::vector<bzx_gap> g;
+    const int rc = ix_build(ctx, DS_INDEX, bz2, len, e, info, g);
+    return ix_copy_out(ctx, rc, e, entries, cap_entries, "bzx_index_build_buffer: more blocks than cap_entries");
 }
 
 extern "C" int bzx_salvage_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries,
@@ -1433,16 +1386,12 @@ extern "C" int bzx_salvage_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t
     *ngaps = 0;
     std::vector<bzx_index_entry> e;
     std::vector<bzx_gap> g;
-    int rc = sv_build(ctx, bz2, len, e, info, g);
+    const int rc = ix_build(ctx, DS_SALVAGE, bz2, len, e, info, g);
     if (rc) return rc;
-    rc = sv_gaps_out(ctx, g, gaps, cap_gaps, ngaps);
-    const uint64_t k = std::min<uint64_t>(e.size(), cap_entries);
-    if (k) memcpy(entries, e.data(), (size_t)k * sizeof(bzx_index_entry));
-    if (e.size() > cap_entries) {
-        ctx->err = "bzx_salvage_build_buffer: more blocks than cap_entries";
-        rc = BZX_E_OUTBUF;
-    }
-    return rc;
+    *ngaps = g.size();
+    const int rc_gaps = ix_copy_out(ctx, 0, g, gaps, cap_gaps, "bzx_salvage: more gaps than cap_gaps");
+    const int rc_ent = ix_copy_out(ctx, 0, e, entries, cap_entries, "bzx_salvage_build_buffer: more blocks than cap_entries");
+    return rc_ent ? rc_ent : rc_gaps;                        // (both did not fit: the entries' text)
 }
 
 extern "C" int bzx_salvage_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, uint8_t *out, size_t cap, size_t *out_len,
@@ -1455,9 +1404,10 @@ extern "C" int bzx_salvage_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, 
     std::vector<bzx_gap> g;
     bzx_index_info info;
     memset(&info, 0, sizeof(info));
-    int rc = sv_build(ctx, bz2, len, e, &info, g);
+    int rc = ix_build(ctx, DS_SALVAGE, bz2, len, e, &info, g);
     if (rc) return rc;
-    const int rc_gaps = sv_gaps_out(ctx, g, gaps, cap_gaps, ngaps);
+    *ngaps = g.size();
+    const int rc_gaps = ix_copy_out(ctx, 0, g, gaps, cap_gaps, "bzx_salvage: more gaps than cap_gaps");
     *out_len = (size_t)info.out_bytes;
     const uint64_t want = std::min<uint64_t>(info.out_bytes, cap);
     if (want) {

@@ -4,11 +4,11 @@
 
 Inputs: one stream of 256 MiB of seeded synthetic text at -9, and one file of 64 concatenated streams of 256 KiB
 (DESIGN 5c).  Sides: bzx_dstream_* (everything fed in one call with final, the output taken in one buffer) and
-bzx_decompress_buffer of the same library; with --parent-lib also bzx_decompress_buffer of that library (the parent
-commit built into a second directory), alternated with the stream in one process.  Every side has one context of
+bzx_decompress_buffer of the same library; with --parent-lib also both of that library (the parent commit built into
+a second directory), alternated in one process.  Every side has one context of
 max_blocks = 1024; every shape runs once before it is timed, then the best of --reps; times are host clock around
 calls that return with the bytes in the caller's buffer.  The decoded bytes are checked.  Prints one line per case
-and a JSON line."""
+and a JSON line (all_ms: every run of every side)."""
 import argparse
 import ctypes as C
 import json
@@ -21,7 +21,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from bzx_ctypes import Oracle  # noqa: E402
-from bzx_dbatch_ctypes import DBatchLib  # noqa: E402
 from bzx_dstream_ctypes import DStreamLib  # noqa: E402
 
 MAX_BLOCKS = 1024
@@ -36,7 +35,7 @@ def main():
     torch.cuda.init()
     oracle = Oracle()
     lib = DStreamLib(max_blocks=MAX_BLOCKS)
-    parent = DBatchLib(a.parent_lib, max_blocks=MAX_BLOCKS) if a.parent_lib else None
+    parent = DStreamLib(a.parent_lib, max_blocks=MAX_BLOCKS) if a.parent_lib else None
     text = oracle.synthtext(256 << 20, seed=12345)
     one = lib.compress_buffer(text, 9)
     size = 256 << 10
@@ -48,14 +47,17 @@ def main():
         out = C.create_string_buffer(cap)
         info = {}
 
-        def stream():
-            s = lib.dstream(a.max_chunk)
+        def stream_of(which):
+            return lambda: stream(which)
+
+        def stream(which):
+            s = which.dstream(a.max_chunk)
             try:
                 pos, total, done = 0, 0, 0
                 while not done:
                     rc, used, made, done = s.feed_raw(C.addressof(src) + pos, len(z) - pos, True, C.addressof(out) + total,
                                                       cap - total)
-                    assert rc == 0, lib.last_error()
+                    assert rc == 0, which.last_error()
                     pos += used
                     total += made
                 assert total == len(want)
@@ -72,8 +74,10 @@ def main():
                 assert rc == 0 and n.value == len(want), which.last_error()
             return fn
 
-        sides = [("stream", stream), ("buffer", buffer_of(lib))] + ([("parent_buffer", buffer_of(parent))] if parent else [])
-        best = {}
+        sides = [("stream", stream_of(lib)), ("buffer", buffer_of(lib))]
+        if parent:
+            sides += [("parent_stream", stream_of(parent)), ("parent_buffer", buffer_of(parent))]
+        runs = {label: [] for label, _ in sides}
         for label, fn in sides:                                   # warm-up, bytes checked
             C.memset(out, 0, cap)
             fn()
@@ -83,8 +87,10 @@ def main():
                 t0 = time.perf_counter()
                 fn()
                 dt = time.perf_counter() - t0
-                best[label] = min(best.get(label, dt), dt)
+                runs[label].append(dt)
+        best = {k: min(v) for k, v in runs.items()}
         r = {k + "_ms": v * 1e3 for k, v in best.items()}
+        r["all_ms"] = {k: [round(x * 1e3, 2) for x in v] for k, v in runs.items()}
         ref = best.get("parent_buffer", best["buffer"])
         r["stream_over_one_shot"] = best["stream"] / ref
         r.update(info)

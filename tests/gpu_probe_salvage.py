@@ -5,7 +5,7 @@
 One stream of --mib MiB of seeded synthetic text at -9.  Sides, alternated in one process after a warm-up of every side,
 best of --reps: bzx_index_build_buffer of this build, bzx_salvage_build_buffer of the clean stream, the same of a damaged
 variant (a payload bit of every 50th block flipped), bzx_salvage_buffer of the damaged variant (salvage index + range read of
-everything that survived), and with --parent-lib bzx_index_build_buffer of another build of the library (the parent
+everything that survived), and with --parent-lib the same four calls of another build of the library (the parent
 commit's).  Times are host clock around calls that end in a device synchronise.  Checked on the way: on the clean stream
 the salvage entries are the index's and there is no gap; the damaged variant loses exactly the blocks hit, and its
 salvaged bytes are the surviving blocks' bytes.  Prints one line and a JSON line."""
@@ -45,7 +45,7 @@ def main():
     z = maker.compress_buffer(raw, 9)
     maker.close()
     lib = SalvageLib(max_blocks=MAX_BLOCKS)
-    parent = RangeLib(a.parent_lib, max_blocks=MAX_BLOCKS) if a.parent_lib else None
+    parent = SalvageLib(a.parent_lib, max_blocks=MAX_BLOCKS) if a.parent_lib else None
     cap = len(z) // 2000 + 4096
 
     rc, e, info = lib.index_build(z, cap=cap)
@@ -60,14 +60,17 @@ def main():
     alive = [k for k in range(n) if k not in hit]
     want = b"".join(raw[e[k].out_off:e[k].out_off + e[k].out_len] for k in alive)
 
-    sides = {
-        "index": lambda: lib.index_build(z, cap=cap),
-        "salvage_clean": lambda: lib.salvage_build(z, cap=cap, cap_gaps=4096),
-        "salvage_damaged": lambda: lib.salvage_build(bad, cap=cap, cap_gaps=4096),
-        "salvage_buffer_damaged": lambda: lib.salvage_buffer(bad, len(want)),
-    }
+    def sides_of(which, pre):
+        return {
+            pre + "index": lambda: which.index_build(z, cap=cap),
+            pre + "salvage_clean": lambda: which.salvage_build(z, cap=cap, cap_gaps=4096),
+            pre + "salvage_damaged": lambda: which.salvage_build(bad, cap=cap, cap_gaps=4096),
+            pre + "salvage_buffer_damaged": lambda: which.salvage_buffer(bad, len(want)),
+        }
+
+    sides = sides_of(lib, "")
     if parent:
-        sides["parent_index"] = lambda: parent.index_build(z, cap=cap)
+        sides.update(sides_of(parent, "parent_"))
     # warm-up and checks
     rc, e2, inf2, gaps, ng = sides["salvage_clean"]()
     assert rc == 0 and ng == 0 and bytes(e2)[:40 * n] == bytes(e)[:40 * n] and inf2.nblk == n and inf2.nstreams == info.nstreams
@@ -80,6 +83,8 @@ def main():
     if parent:
         rc, ep, infp = sides["parent_index"]()
         assert rc == 0 and bytes(ep)[:40 * n] == bytes(e)[:40 * n]
+        for k in ("parent_salvage_clean", "parent_salvage_damaged", "parent_salvage_buffer_damaged"):
+            assert sides[k]()[0] == 0, parent.last_error()
     t = {k: [] for k in sides}
     for _ in range(a.reps):                                         # sides alternated
         for k, fn in sides.items():

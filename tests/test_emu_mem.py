@@ -21,6 +21,7 @@ from bzx_ctypes import EMU_PATH, ROOT, BzxError
 from bzx_dstream_ctypes import dstream_decode
 from bzx_mdev_ctypes import MDev
 from bzx_ranges_ctypes import RangesLib
+from bzx_salvage_ctypes import SalvageLib
 from test_range import py_walk
 
 E_NOMEM = -3
@@ -58,10 +59,14 @@ def mem():
     return Mem()
 
 
+class Lib(RangesLib, SalvageLib):
+    """Every call family of this file on one context."""
+
+
 @pytest.fixture(scope="module")
 def index(mem):
     """The index entries of Z, from a context of their own."""
-    lib = RangesLib(EMU_PATH)
+    lib = Lib(EMU_PATH)
     try:
         rc, entries, info = lib.index_build(Z)
         assert rc == 0 and info.nblk >= 1
@@ -119,6 +124,21 @@ def f_index_build(lib, aux):
     return rc
 
 
+def f_salvage_build(lib, aux):
+    """Z is intact: the entries are the index's, and there is no gap."""
+    rc, entries, info, gaps, ngaps = lib.salvage_build(Z)
+    assert rc or [entries[i].key() for i in range(info.nblk)] == [aux[0][i].key() for i in range(aux[1])]
+    assert rc or (gaps == [] and ngaps == 0)
+    assert rc == 0 or (info.nblk == 0 and ngaps == 0)        # a failed run hands nothing out
+    return rc
+
+
+def f_salvage_buffer(lib, aux):
+    rc, got, out_len, gaps, ngaps = lib.salvage_buffer(Z, 4096)
+    assert rc or (got == TEXT and out_len == len(TEXT) and gaps == [] and ngaps == 0)
+    return rc
+
+
 def f_range_buffer(lib, aux):
     rc, got, room, g = lib.range_buffer(Z, 0, aux[0], aux[1], 100, 333)
     assert rc or got == TEXT[100:433]
@@ -163,13 +183,13 @@ def f_split_rle1(lib, aux):
 
 
 FAMILIES = [f_compress_buffer, f_compress_batch_buffer, f_decompress_buffer, f_decompress_batch_buffer, f_dstream,
-            f_index_build, f_range_buffer, f_ranges_buffer, f_stage_gather, f_stage_ibwt, f_split_rle1]
+            f_index_build, f_salvage_build, f_salvage_buffer, f_range_buffer, f_ranges_buffer, f_stage_gather, f_stage_ibwt, f_split_rle1]
 
 
 def create():
     """-> (lib, 0), or (None, the code bzx_ctx_create returned)"""
     try:
-        return RangesLib(EMU_PATH), 0
+        return Lib(EMU_PATH), 0
     except BzxError as e:
         return None, e.code
 
