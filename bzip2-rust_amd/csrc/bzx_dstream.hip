@@ -291,11 +291,13 @@ struct DsIxRec {
 
 __global__ __launch_bounds__(64) void bzx_ds_index_kernel(BzxBatch B, const uint32_t *__restrict__ chain,
                                                          const uint32_t *__restrict__ meta, uint64_t base_bit,
-                                                         const DsRec *__restrict__ rec, DsIxRec *__restrict__ out)
+                                                         const DsRec *__restrict__ rec, DsIxRec *__restrict__ out,
+                                                         const uint32_t *__restrict__ rec_cnt, uint32_t *__restrict__ cnt_out)
 {
     const uint32_t j0 = rec->pass_j0, j1 = rec->placed;
     for (uint32_t j = j0 + threadIdx.x; j < j1; j += 64) {
         const BzxBlock &d = B.blk[chain[j]];
+        if (rec_cnt) cnt_out[j - j0] = rec_cnt[chain[j]];    // (bzx_index_count_records: the block's delimiters)
         DsIxRec r;
         r.bit = base_bit + d.out_bit;
         r.out_len = (uint32_t)d.pack_word;
@@ -571,6 +573,8 @@ struct bzx_index {
     bzx_dstream *s = nullptr;
     std::vector<bzx_index_entry> entries;
     std::vector<bzx_gap> gaps;                             // (salvage)
+    std::vector<uint64_t> rec;                             // (bzx_index_count_records) delimiters before every entry, and T
+    bool fed = false;                                      // bzx_index_feed has been called
 };
 
 struct DsSlot {                    // an output staging area: the verified bytes of one pass
@@ -632,6 +636,9 @@ struct bzx_dstream {
     DevMem<uint32_t> d_meta;
     DevMem<DsIxRec> d_ix;
     PinMem<DsIxRec> h_ix;
+    // ... with bzx_index_count_records: one count per slab, and behind the nb records of a pass's copy its nb counts
+    int rec_delim = -1;
+    DevMem<uint32_t> d_rcnt;
     // DS_SALVAGE (bzx_salvage_*): the index mode's memory, with the tables of the salvage kernels in place of d_meta / d_ix
     DsSvState sv = {};                 // the walk's state between passes and windows
     DevMem<DsSvCand> d_svc;
@@ -918,11 +925,13 @@ static int ds_launch_verdict(bzx_dstream *s, uint32_t q, uint32_t nb)
     hipLaunchKernelGGL(bzx_ds_verdict_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_dst.get(), s->d_got.get(), s->d_stage[q].get(),
                        s->d_rec.get());
     if (s->mode == DS_INDEX) {
+        const bool counting = s->rec_delim >= 0;
         hipLaunchKernelGGL(bzx_ds_index_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_meta.get(), s->wbase * 8, s->d_rec.get(),
-                           s->d_ix.get());
+                           s->d_ix.get(), (const uint32_t *)s->d_rcnt.get(),
+                           counting ? reinterpret_cast<uint32_t *>(s->d_ix.get() + nb) : nullptr);
         // (the round's share of the table; the pass wrote its first placed - pass_j0 entries, the host reads
         // r.good <= that many, the rest is what bzx_index_begin zeroed or an earlier pass left)
-        HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, nb * sizeof(DsIxRec), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, nb * (sizeof(DsIxRec) + (counting ? 4 : 0)), hipMemcpyDeviceToHost, st));
     }
     return BZX_OK;
 }
@@ -972,8 +981,10 @@ static int ds_digest(bzx_dstream *s, uint32_t q, bool fresh)
         s->rd_active = true;
     }
     if (s->mode == DS_INDEX) {                               // their bytes stay
+        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(s->h_ix.get() + s->rd_nb);      // (counting: behind the records)
         for (uint32_t j = 0; j < r.good; j++) {
             const DsIxRec &x = s->h_ix[j];
+            if (s->rec_delim >= 0) s->ix->rec.push_back(s->ix->rec.back() + cnt[j]);
             s->ix->entries.push_back(ds_entry(x.bit, s->info.out_bytes, x.out_len, x.crc, x.img_bits,
                                               s->info.nstreams + (x.meta >> 4), x.meta & 15u));
             s->info.out_bytes += x.out_len;
@@ -1052,6 +1063,8 @@ static int ds_pass(bzx_dstream *s, uint32_t q)
         ds_launch_layout(s, q);
         bzx_launch_dc_expand(B, ctx->d_in, s->d_dst, st);
         bzx_launch_dc_crc(B, s->d_dst, s->d_got, (uint32_t)ctx->n_cu, st);
+        if (s->rec_delim >= 0)
+            bzx_launch_rec_count(B.blk, s->d_dst, nb, (uint32_t)s->rec_delim, s->d_rcnt, (uint32_t)ctx->n_cu, st);
     }
     int rc = ds_launch_verdict(s, q, nb);
     if (rc) return rc;
@@ -1296,7 +1309,58 @@ extern "C" int bzx_index_feed(bzx_index *ix, const uint8_t *bz2, size_t len, int
 {
     if (!ix || !ix->s || !ix->s->ctx || !consumed || !done || (len && !bz2)) return BZX_E_PARAM;
     size_t produced = 0;
+    ix->fed = true;
     return ds_feed_call(ix->s, bz2, len, final, consumed, nullptr, 0, &produced, done);
+}
+
+// Counting switched on: the pass gains bzx_rec_count_kernel behind the CRCs and one word per block in its copy; the
+// tables grow here, between begin and the first feed, so that an index without counting allocates what it always did.
+extern "C" int bzx_index_count_records(bzx_index *ix, int delim)
+{
+    if (!ix || !ix->s || !ix->s->ctx) return BZX_E_PARAM;
+    bzx_dstream *s = ix->s;
+    bzx_ctx *ctx = s->ctx;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    if (s->mode != DS_INDEX) {
+        ctx->err = "bzx_index_count_records: not on a salvage index (its entries come from the device walk)";
+        return BZX_E_STATE;
+    }
+    if (ix->fed) {
+        ctx->err = "bzx_index_count_records: call it before the first bzx_index_feed";
+        return BZX_E_STATE;
+    }
+    if (delim < 0 || delim > 255) return BZX_E_PARAM;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t R = s->R, before_ix = s->d_ix.bytes(), before_pin = s->h_ix.bytes();
+    try {
+        ix->rec.assign(1, 0);
+    } catch (const std::bad_alloc &) {
+        return BZX_E_NOMEM;
+    }
+    if (!s->d_rcnt.reserve(R * 4) || !s->d_ix.reserve(R * (sizeof(DsIxRec) + 4)) || !s->h_ix.reserve(R * (sizeof(DsIxRec) + 4)) ||
+        hipMemset(s->d_ix, 0, R * (sizeof(DsIxRec) + 4)) != hipSuccess || hipMemset(s->d_rcnt, 0, R * 4) != hipSuccess) {
+        ctx->err = "bzx_index_count_records: device or pinned allocation failed";
+        return BZX_E_NOMEM;
+    }
+    if (s->rec_delim < 0) {
+        s->info.device_bytes += R * 4 + s->d_ix.bytes() - before_ix;
+        s->info.pinned_bytes += s->h_ix.bytes() - before_pin;
+    }
+    s->rec_delim = delim;
+    return BZX_OK;
+}
+
+extern "C" int bzx_index_get_records(const bzx_index *ix, const uint64_t **rec_before, uint64_t *n)
+{
+    if (!ix || !ix->s || !ix->s->ctx || !rec_before || !n) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(ix->s->ctx->api_mu);
+    if (ix->s->rec_delim < 0) {
+        ix->s->ctx->err = "bzx_index_get_records: counting was not switched on (bzx_index_count_records)";
+        return BZX_E_STATE;
+    }
+    *rec_before = ix->rec.data();
+    *n = ix->entries.size();
+    return BZX_OK;
 }
 
 extern "C" int bzx_index_get(const bzx_index *ix, const bzx_index_entry **entries, bzx_index_info *info)
@@ -1326,11 +1390,17 @@ extern "C" int bzx_index_get_gaps(const bzx_index *ix, const bzx_gap **gaps, uin
 // the feed loop.  A run that failed hands nothing out, except in the index mode: there the entries and `info` describe
 // the verified prefix, and the feed's code and text are the call's.
 static int ix_build(bzx_ctx *ctx, DsMode mode, const uint8_t *bz2, size_t len, std::vector<bzx_index_entry> &entries,
-                    bzx_index_info *info, std::vector<bzx_gap> &gaps)
+                    bzx_index_info *info, std::vector<bzx_gap> &gaps, int delim = -1, std::vector<uint64_t> *rec = nullptr)
 {
     bzx_index *ix = nullptr;
     int rc = ix_begin(ctx, std::min<size_t>(std::max<size_t>(len, DS_MIN_CHUNK), (size_t)64 << 20), mode, &ix);
     if (rc) return rc;
+    if (rec && (rc = bzx_index_count_records(ix, delim))) {
+        const std::string why = ctx->err;
+        bzx_index_end(ix);
+        ctx->err = why;
+        return rc;
+    }
     size_t pos = 0;
     int done = 0;
     while (!rc && !(done && pos == len)) {
@@ -1348,6 +1418,7 @@ static int ix_build(bzx_ctx *ctx, DsMode mode, const uint8_t *bz2, size_t len, s
     if ((!rc || mode == DS_INDEX) && bzx_index_get(ix, &e, info) == BZX_OK) {
         entries.swap(ix->entries);
         gaps.swap(ix->gaps);
+        if (rec) rec->swap(ix->rec);
     }
     bzx_index_end(ix);
     if (rc) ctx->err = why;
@@ -1375,6 +1446,22 @@ extern "C" int bzx_index_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t l
     std::vector<bzx_gap> g;
     const int rc = ix_build(ctx, DS_INDEX, bz2, len, e, info, g);
     return ix_copy_out(ctx, rc, e, entries, cap_entries, "bzx_index_build_buffer: more blocks than cap_entries");
+}
+
+extern "C" int bzx_index_build_records_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, int delim, bzx_index_entry *entries,
+                                              uint64_t cap_entries, bzx_index_info *info, uint64_t *rec_before)
+{
+    if (!ctx || !info || !rec_before || (len && !bz2) || (cap_entries && !entries) || delim < 0 || delim > 255) return BZX_E_PARAM;
+    memset(info, 0, sizeof(*info));
+    rec_before[0] = 0;
+    std::vector<bzx_index_entry> e;
+    std::vector<bzx_gap> g;
+    std::vector<uint64_t> r;
+    const int rc = ix_build(ctx, DS_INDEX, bz2, len, e, info, g, delim, &r);
+    // (the table of the entries that go out: one value more than they are)
+    const size_t k = (size_t)std::min<uint64_t>(e.size(), cap_entries);
+    if (r.size() > k) memcpy(rec_before, r.data(), (k + 1) * sizeof(uint64_t));
+    return ix_copy_out(ctx, rc, e, entries, cap_entries, "bzx_index_build_records_buffer: more blocks than cap_entries");
 }
 
 extern "C" int bzx_salvage_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries,

@@ -91,6 +91,9 @@ struct bzx_ctx {
     uint32_t range_slabs = 0;                   // blocks the round tables hold
     DevMem<> range_io[2];                       // the _buffer form's span [0] and output [1] on the device, grown on demand
     DevMem<> range_sl;                          // the gather kernel's slice table, grown on demand
+    // record reads (bzx_records_locate_*): a round's queries and answers, grown on demand
+    DevMem<> rec_ws;
+    PinMem<> rec_pin;
 
     // block index kept by the compressor (bzx_ctx_keep_index; off: nothing below is touched but the two flags a
     // compression call clears)
@@ -272,3 +275,32 @@ void bzx_launch_dc_ibwt(const BzxBatch &B, uint8_t *img_slabs, hipStream_t strea
 void bzx_launch_dc_ibwt_wide(const BzxBatch &B, uint8_t *img_slabs, uint32_t n_hint, hipStream_t stream);   // one workgroup per block
 void bzx_launch_dc_expand(const BzxBatch &B, const uint8_t *img_slabs, const BzxDcDst *dst, hipStream_t stream);
 void bzx_launch_dc_crc(const BzxBatch &B, const BzxDcDst *dst, uint32_t *got, uint32_t n_cu, hipStream_t stream);
+
+// ---- bzx_range.hip: what a round of a range read is made of (the record reads of bzx_records.hip decode their blocks
+// through the same round, tables, pool and verdict)
+#define RG_EDGE_BYTES ((size_t)(BZX_MAX_N / 5 * 259 + 16))      // an expanded block: 259/5 x 900,000, rounded up
+#define RG_POOL_BYTES (2 * rg_al(RG_EDGE_BYTES))                // the pool: room for the two edge blocks of one range
+static inline size_t rg_al(size_t x) { return (x + 255) & ~(size_t)255; }
+// The input bytes a block needs: from the byte that holds its magic to its last bit, rounded up to a byte, + 8.
+static inline void rg_block_bytes(const bzx_index_entry &x, uint64_t *lo, uint64_t *hi)
+{
+    *lo = x.bit / 8;
+    *hi = (x.bit + x.img_bits + 7) / 8 + 8;
+}
+struct RgTables {
+    BzxDcSrc *d_src;
+    BzxDcDst *d_dst;
+    uint32_t *d_len, *d_got, *d_flag, *h_got, *h_flag;
+    uint8_t *pool;
+};
+int rg_tables(bzx_ctx *ctx, uint32_t R, RgTables *t);
+int rg_round(bzx_ctx *ctx, const RgTables &t, uint32_t nb, const BzxDcSrc *src, const BzxDcDst *dst, const uint32_t *len,
+             uint32_t n_hint);
+int rg_verdict(bzx_ctx *ctx, const bzx_index_entry &x, uint64_t k, const BzxBlock &d, uint32_t flag, uint32_t got);
+int rg_upload(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const uint8_t *held, const uint8_t **d_pc);
+
+// ---- bzx_records.hip: the delimiter count of every segment (block) of a table, one 32-bit count each
+// blk: the blocks' descriptors (a block with a status is skipped, its length is pack_word) or null (the length is
+// seg[b].cap); a segment without a pointer is skipped.
+void bzx_launch_rec_count(const BzxBlock *blk, const BzxDcDst *seg, uint32_t nseg, uint32_t delim, uint32_t *counts,
+                          uint32_t n_cu, hipStream_t stream);

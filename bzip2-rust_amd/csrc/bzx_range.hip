@@ -22,8 +22,6 @@
 #include <new>
 #include "bzx_host.h"
 
-#define RG_EDGE_BYTES ((size_t)(BZX_MAX_N / 5 * 259 + 16))      // an expanded block: 259/5 x 900,000, rounded up
-#define RG_POOL_BYTES (2 * rg_al(RG_EDGE_BYTES))                // the pool: room for the two edge blocks of one range
 #define RG_NO_MAGIC 1u
 #define RG_LENGTH 2u
 
@@ -44,13 +42,6 @@ __global__ __launch_bounds__(64) void bzx_rg_check_kernel(BzxBatch B, const BzxD
 }
 
 static uint64_t rg_total(const bzx_index_entry *e, uint64_t n) { return n ? e[n - 1].out_off + e[n - 1].out_len : 0; }
-
-// The input bytes a block needs: from the byte that holds its magic to its last bit, rounded up to a byte, + 8.
-static void rg_block_bytes(const bzx_index_entry &x, uint64_t *lo, uint64_t *hi)
-{
-    *lo = x.bit / 8;
-    *hi = (x.bit + x.img_bits + 7) / 8 + 8;
-}
 
 extern "C" int bzx_index_span(const bzx_index_entry *e, uint64_t n, uint64_t off, uint64_t want, uint64_t *first,
                               uint64_t *count, uint64_t *byte_lo, uint64_t *byte_hi)
@@ -78,16 +69,8 @@ extern "C" int bzx_index_span(const bzx_index_entry *e, uint64_t n, uint64_t off
 
 // Round tables: device [src R][dst R][want_len R][got R][flag R], pinned [got R][flag R]; behind them on the device the
 // pool.
-struct RgTables {
-    BzxDcSrc *d_src;
-    BzxDcDst *d_dst;
-    uint32_t *d_len, *d_got, *d_flag, *h_got, *h_flag;
-    uint8_t *pool;
-};
-
-static size_t rg_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static int rg_tables(bzx_ctx *ctx, uint32_t R, RgTables *t)
+// (RgTables: bzx_host.h -- the record reads of bzx_records.hip run their rounds through the same tables)
+int rg_tables(bzx_ctx *ctx, uint32_t R, RgTables *t)
 {
     if (R < ctx->range_slabs) R = ctx->range_slabs;          // (the tables are laid out for the blocks they hold)
     const bool ok = carved(ctx->range_ws, 256, [&](Carver &c) {
@@ -124,6 +107,25 @@ static int rg_io(bzx_ctx *ctx, int k, size_t bytes, void **p)
     return BZX_OK;
 }
 
+// The _buffer forms' upload: the pieces with held[j] set go, back to back, into the span buffer the context keeps;
+// d_pc[j]: where piece j lies on the device (untouched for the others).  Enqueued on the context's stream.
+int rg_upload(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const uint8_t *held, const uint8_t **d_pc)
+{
+    size_t bytes = 0;
+    for (uint32_t j = 0; j < npc; j++) bytes += held[j] ? (size_t)pc[j].len : 0;
+    void *d_z = nullptr;
+    const int rc = rg_io(ctx, 0, bytes + 64, &d_z);
+    if (rc) return rc;
+    size_t at = 0;
+    for (uint32_t j = 0; j < npc; j++) {
+        if (!held[j]) continue;
+        d_pc[j] = (const uint8_t *)d_z + at;
+        HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)d_z + at, pc[j].p, (size_t)pc[j].len, hipMemcpyHostToDevice, ctx->stream));
+        at += (size_t)pc[j].len;
+    }
+    return BZX_OK;
+}
+
 static int rg_refuse(bzx_ctx *ctx, const std::string &why)
 {
     ctx->err = why;
@@ -131,7 +133,7 @@ static int rg_refuse(bzx_ctx *ctx, const std::string &why)
 }
 
 // A decoded block held against its entry: BZX_OK, or BZX_E_DATA and the text.  k: the entry's number.
-static int rg_verdict(bzx_ctx *ctx, const bzx_index_entry &x, uint64_t k, const BzxBlock &d, uint32_t flag, uint32_t got)
+int rg_verdict(bzx_ctx *ctx, const bzx_index_entry &x, uint64_t k, const BzxBlock &d, uint32_t flag, uint32_t got)
 {
     const std::string blk = " (block " + std::to_string(k) + ")";
     if (flag & RG_NO_MAGIC)
@@ -150,7 +152,7 @@ static int rg_verdict(bzx_ctx *ctx, const bzx_index_entry &x, uint64_t k, const 
 
 // One round on the device: nb blocks through decode, inverse BWT, check, expand and CRC; descriptors (ctx->h_blk), CRCs
 // and flags (t.h_got, t.h_flag) are on the host when it returns.  The round's one synchronisation.
-static int rg_round(bzx_ctx *ctx, const RgTables &t, uint32_t nb, const BzxDcSrc *src, const BzxDcDst *dst, const uint32_t *len,
+int rg_round(bzx_ctx *ctx, const RgTables &t, uint32_t nb, const BzxDcSrc *src, const BzxDcDst *dst, const uint32_t *len,
                     uint32_t n_hint)
 {
     hipStream_t st = ctx->stream;
@@ -496,18 +498,9 @@ static int ranges_call(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const bz
         uint8_t *d_out = out;
         if (host) {                                          // the pieces that hold a touched block, back to back
             std::vector<uint8_t> held(npc, 0);
-            size_t bytes = 0;
             for (const RgBlk &b : P.blk) held[b.piece] = 1;
-            for (uint32_t j = 0; j < npc; j++) bytes += held[j] ? (size_t)pc[j].len : 0;
-            void *d_z = nullptr, *d_o = nullptr;
-            if ((rc = rg_io(ctx, 0, bytes + 64, &d_z)) || (rc = rg_io(ctx, 1, (size_t)P.need + 64, &d_o))) return rc;
-            size_t at = 0;
-            for (uint32_t j = 0; j < npc; j++) {
-                if (!held[j]) continue;
-                d_pc[j] = (const uint8_t *)d_z + at;
-                HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)d_z + at, pc[j].p, (size_t)pc[j].len, hipMemcpyHostToDevice, ctx->stream));
-                at += (size_t)pc[j].len;
-            }
+            void *d_o = nullptr;
+            if ((rc = rg_upload(ctx, pc, npc, held.data(), d_pc.data())) || (rc = rg_io(ctx, 1, (size_t)P.need + 64, &d_o))) return rc;
             d_out = (uint8_t *)d_o;
         } else {
             for (uint32_t j = 0; j < npc; j++) d_pc[j] = (const uint8_t *)pc[j].p;

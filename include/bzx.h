@@ -616,6 +616,107 @@ int bzx_stage_gather_time(bzx_ctx *ctx, const uint8_t *src, size_t src_len, uint
                           const uint64_t *dst_offs, const uint64_t *lens, uint8_t *out, size_t out_len, uint32_t reps,
                           float *ms_best);
 /*
+ * Records: "records [a, a + c) of what this .bz2 decodes to" -- lines of a text or JSONL dump -- on top of the block index
+ * and the range reads.
+ * The rule.  D[0, N) is what bzx_decompress_buffer returns for the whole input; delim is one byte value, 0..255; T is the
+ * number of bytes of D equal to delim.
+ *   rec_start(0) = 0;  rec_start(r) = the position of the r-th delimiter + 1 for 1 <= r <= T;  rec_start(r) = N for r > T.
+ *   Records [a, a + c) are the bytes [rec_start(a), rec_start(a + c)): terminating delimiters are included, record T is the
+ *   unterminated tail and may be empty, a + c saturates at 2^64 - 1.
+ *   The record table of an index of n entries is uint64_t rec_before[n + 1]: rec_before[k] = delimiters in
+ *   D[0, entries[k].out_off), rec_before[n] = T.  An empty index has the table {0}.
+ *
+ * The table from the index pass.  bzx_index_count_records(ix, delim): between bzx_index_begin and the first
+ * bzx_index_feed; BZX_E_STATE after a feed and on an object from bzx_salvage_begin (its entries come from the device
+ * walk: salvage is not covered), BZX_E_PARAM for a delim outside 0..255.  Off is the default and off means off: the index
+ * pass launches, copies, allocates and synchronises as it did.  On, a pass gains one launch (bzx_rec_count_kernel, behind
+ * the block CRCs, over the expanded bytes of the blocks the pass placed) and one 32-bit word per block in the copy that
+ * brings its entries back; it gains no synchronisation.  The tables for that are allocated by this call.
+ * bzx_index_get_records: the table of the entries bzx_index_get returns now, *n = their number (the table has *n + 1
+ * values); valid as long as bzx_index_get's pointer; BZX_E_STATE when counting was not switched on.  After BZX_E_DATA it
+ * describes the verified prefix, as the entries do.
+ * bzx_index_build_records_buffer: bzx_index_build_buffer with counting on; rec_before has room for cap_entries + 1 values
+ * and receives the table of the entries written (after BZX_E_OUTBUF: of the first cap_entries).
+ *
+ * The table from the raw side, for a stream this library compressed: bzx_records_count_device / _buffer count delim in
+ * raw[e[k].out_off, + out_len) for every entry (the same kernel over pointer-and-length segments, sums on the host).
+ * BZX_E_PARAM unless the entries tile [0, len): out_off is the running sum of out_len and the last one ends at len.  For
+ * the index a compression call kept (bzx_compress_get_index and its siblings) the result equals what
+ * bzx_index_build_records_buffer returns for the stream that call wrote.  _buffer holds the raw bytes on the device for
+ * the call.
+ *
+ * Planners (host only, no context).  bzx_records_span: the entry that holds the r-th delimiter -- the smallest k with
+ * rec_before[k + 1] >= r, so blocks without a delimiter are stepped over -- and *j = r - rec_before[k], in 1..the block's
+ * count.  r == 0: *entry = 0, *j = 0.  r > T: *entry = n, *j = 0.  BZX_E_PARAM: NULL, rec_before[0] != 0, a table that
+ * descends.
+ * bzx_records_pieces: the byte intervals of the file that locating and reading the record ranges [rec_los[i], +
+ * rec_cnts[i]) need, as bzx_index_spans names them for byte ranges: per range the entries from the one that holds
+ * delimiter lo (entry 0 for lo == 0) to the one that holds delimiter lo + cnt, clipped to the index -- none when lo > T or
+ * the range is [0, 0) -- each with its bytes [bit / 8, (bit + img_bits + 7) / 8 + 8), merged; BZX_E_OUTBUF with *npieces =
+ * pieces needed.
+ *
+ * bzx_records_locate_device / _buffer: byte_offs[i] = rec_start(recs[i]).  The host resolves every query with
+ * bzx_records_span; a query with j == 0 needs no device.  Every distinct touched block is decoded once, into the staging
+ * pool of the range reads and through their checks against the entry, by the same code; then one launch per round of
+ * bzx_rec_select_kernel answers all queries of the round: for (block, j) the position of the j-th delimiter and the
+ * block's count.  A block whose count is not rec_before[k + 1] - rec_before[k] fails its queries: BZX_E_DATA, "record table
+ * does not match the input: block K holds X delimiters, the table says Y".  A damaged block or a stale entry fails exactly
+ * the queries that touch it, with the range reader's texts; status[i] is BZX_OK or BZX_E_DATA (byte_offs[i] = 0), the call
+ * returns the status of the lowest failing query and bzx_last_error reads "query k: " and the text.  Errors of the whole
+ * call (BZX_E_PARAM -- NULL arrays, pieces not ascending and disjoint, a touched block not inside one piece, a bad table
+ * --, BZX_E_NOMEM, BZX_E_HIP, BZX_E_STATE) are set into every status.  Pieces as in bzx_decompress_ranges_*; _buffer
+ * uploads the pieces that hold a touched block.  Rounds as there (as many blocks as the context has slabs, or as fit
+ * the pool).  Host synchronisations: at most two per round (the blocks' verdicts, the answers), none per query.
+ * Only decoded blocks are held against the table: a stale count in a block that no query decodes can select the wrong
+ * records.  It can never select unverified bytes.
+ *
+ * bzx_decompress_records_device / _buffer.  The rule: range i leaves D[rec_start(lo_i), rec_start(lo_i + cnt_i)) at
+ * out[out_offs[i], + gots[i]); the ranges may come in any order, overlap, repeat, be empty or lie beyond T.  One locate
+ * call for all 2 x count boundaries, then one call of bzx_decompress_ranges_* with the byte ranges found: the output is
+ * packed in list order, *need and BZX_E_OUTBUF as there.  A range whose boundary failed is BZX_E_DATA with gots[i] = 0;
+ * the others are still delivered.  bzx_last_error reads "range k: " and the text.  At most 2^31 - 1 ranges.
+ * Cost: the boundary blocks are decoded twice, once by the locate call and once by the ranges call, and _buffer uploads
+ * the pieces twice -- the trade of bzx_salvage_buffer.  A fused pass with the layout on the device is deliberately not
+ * built.
+ */
+int bzx_index_count_records(bzx_index *ix, int delim);
+int bzx_index_get_records(const bzx_index *ix, const uint64_t **rec_before, uint64_t *n);
+int bzx_index_build_records_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, int delim, bzx_index_entry *entries,
+                                   uint64_t cap_entries, bzx_index_info *info, uint64_t *rec_before);
+int bzx_records_count_device(bzx_ctx *ctx, const void *d_raw, size_t len, int delim, const bzx_index_entry *e, uint64_t n,
+                             uint64_t *rec_before);
+int bzx_records_count_buffer(bzx_ctx *ctx, const uint8_t *raw, size_t len, int delim, const bzx_index_entry *e, uint64_t n,
+                             uint64_t *rec_before);
+int bzx_records_span(const uint64_t *rec_before, uint64_t n, uint64_t r, uint64_t *entry, uint64_t *j);
+int bzx_records_pieces(const bzx_index_entry *e, uint64_t n, const uint64_t *rec_before, uint32_t count,
+                       const uint64_t *rec_los, const uint64_t *rec_cnts, uint64_t *bases, uint64_t *lens,
+                       uint32_t cap_pieces, uint32_t *npieces);
+int bzx_records_locate_device(bzx_ctx *ctx, const bzx_piece *pieces, uint32_t npieces, const bzx_index_entry *e, uint64_t n,
+                              const uint64_t *rec_before, int delim, uint32_t count, const uint64_t *recs,
+                              uint64_t *byte_offs, int *status);
+int bzx_records_locate_buffer(bzx_ctx *ctx, const bzx_piece *pieces, uint32_t npieces, const bzx_index_entry *e, uint64_t n,
+                              const uint64_t *rec_before, int delim, uint32_t count, const uint64_t *recs,
+                              uint64_t *byte_offs, int *status);
+int bzx_decompress_records_device(bzx_ctx *ctx, const bzx_piece *pieces, uint32_t npieces, const bzx_index_entry *e,
+                                  uint64_t n, const uint64_t *rec_before, int delim, uint32_t count,
+                                  const uint64_t *rec_los, const uint64_t *rec_cnts, void *d_out, size_t cap,
+                                  size_t *out_offs, size_t *gots, int *status, size_t *need);
+int bzx_decompress_records_buffer(bzx_ctx *ctx, const bzx_piece *pieces, uint32_t npieces, const bzx_index_entry *e,
+                                  uint64_t n, const uint64_t *rec_before, int delim, uint32_t count,
+                                  const uint64_t *rec_los, const uint64_t *rec_cnts, uint8_t *out, size_t cap,
+                                  size_t *out_offs, size_t *gots, int *status, size_t *need);
+/*
+ * The two record kernels alone, for the parity tests (host pointers), over segments [seg_offs[i], + seg_lens[i]) of buf.
+ * The device copy of buf starts on a 256-byte boundary, so seg_offs[i] mod 16 is the alignment the kernel sees.
+ * _count: counts_out[i] = bytes of segment i equal to delim.  _select: pos_out[i] = the position, relative to the
+ * segment, of its js[i]-th delimiter (counted from 1), UINT32_MAX when js[i] is 0 or above the count; cnt_out[i] = the
+ * segment's count either way.  BZX_E_PARAM when a segment leaves buf or is 2^32 bytes or longer.
+ */
+int bzx_stage_rec_count(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nseg, const uint64_t *seg_offs,
+                        const uint64_t *seg_lens, int delim, uint32_t *counts_out);
+int bzx_stage_rec_select(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nq, const uint64_t *seg_offs,
+                         const uint64_t *seg_lens, const uint32_t *js, int delim, uint32_t *pos_out, uint32_t *cnt_out);
+/*
  * The inverse BWT alone, for the parity tests (host pointers): L[0, n) and orig_ptr < n -> the RLE1 image img_out[0, n)
  * and its expansion raw_out (at most raw_cap bytes are written; *raw_len is the whole expanded length).  wide = 0 runs
  * the one-lane walk of the one-shot, batch and stream decoders, wide = 1 the many-lane walk of the range reads; both

@@ -24,6 +24,11 @@
 // reading only the bytes of the file each piece needs.  One line per gap goes to standard error.  The input stays.  With
 // --index it also writes FILE.bz2.bzxi (the gaps are not stored): -dc --range then reads the damaged file.  Exit status
 // 0: nothing was lost, 2: something was, 1: trouble.
+// --index --lines FILE.bz2 ... also writes FILE.bz2.bzxr, the record table of bzx_index_count_records for the delimiter '\n'
+// (little-endian: a 32-byte header -- "BZXR", version 1 (u32), delimiter (u32), zero (u32), nblk (u64), T (u64) -- and
+// nblk + 1 u64 values); -dc --lines FIRST:COUNT FILE.bz2 reads .bzxi and .bzxr (and refuses when either is missing or they
+// describe different block counts), reads only the bytes of the file that bzx_records_pieces names and writes lines
+// [FIRST, FIRST + COUNT), numbered from 0, to standard output through bzx_decompress_records_buffer.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -51,6 +56,8 @@ struct Opts {
     bool with_index = false;           // --with-index: FILE.bz2.bzxi beside FILE.bz2, from the compressor
     uint64_t range_off = 0, range_len = 0;
     std::string ranges;                // --ranges LIST
+    bool lines = false, lines_range = false;       // --lines; --lines FIRST:COUNT
+    uint64_t lines_first = 0, lines_count = 0;
 };
 
 static void help()
@@ -66,6 +73,8 @@ static void help()
          "  --index           write FILE.bzxi, the block index of every FILE (a .bz2), for --range\n"
          "  --range OFF:LEN   with -dc: decoded bytes [OFF, OFF + LEN) of FILE to standard output, through FILE.bzxi\n"
          "  --ranges LIST     with -dc: the same for every OFF:LEN line of the text file LIST, in one call, back to back\n"
+         "  --lines           with --index: also write FILE.bzxr, the table of lines per block\n"
+         "  --lines FIRST:COUNT  with -dc: lines [FIRST, FIRST + COUNT) of FILE, numbered from 0, through FILE.bzxi and FILE.bzxr\n"
          "  --recover         write every intact block of a damaged FILE.bz2 to FILE.recovered (-c: standard output) and\n"
          "                    one line per gap to standard error; with --index also FILE.bz2.bzxi for --range;\n"
          "                    exit status 0: nothing lost, 2: data lost, 1: trouble\n"
@@ -290,7 +299,7 @@ static int write_bzxi(const Opts &o, const std::string &oname, const bzx_index_e
 
 // FILE.bz2 through bzx_index_feed, 64 MiB chunks in page-locked memory as -d reads them: the index (--index), or the
 // salvage index (--recover).  -> 0 and the open index, or 1 after a message.
-static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool salvage, bzx_index **out)
+static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool salvage, bzx_index **out, int delim = -1)
 {
     *out = nullptr;
     const char *name = f.c_str();
@@ -302,6 +311,7 @@ static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool sa
     const size_t CH = (size_t)64 << 20;
     bzx_index *ix = nullptr;
     int rc = salvage ? bzx_salvage_begin(ctx, CH, &ix) : bzx_index_begin(ctx, CH, &ix);
+    if (!rc && delim >= 0 && (rc = bzx_index_count_records(ix, delim))) bzx_index_end(ix);
     if (rc) {
         fclose(in);
         return fail(o, "cannot start", name, ctx, rc);
@@ -337,17 +347,50 @@ static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool sa
     return ret;
 }
 
-// FILE.bz2 -> FILE.bz2.bzxi
+static const size_t BZXR_HEADER = 32;
+static const int LINE_DELIM = '\n';
+
+// The stored form of a record table into oname; after a failure: a message, the partial file removed, 1.
+static int write_bzxr(const Opts &o, const std::string &oname, const uint64_t *rec_before, uint64_t nblk)
+{
+    FILE *out = fopen(oname.c_str(), "wb");
+    uint8_t head[BZXR_HEADER] = {'B', 'Z', 'X', 'R'}, v[8];
+    put_le(head + 4, 1, 4);
+    put_le(head + 8, LINE_DELIM, 4);
+    put_le(head + 16, nblk, 8);
+    put_le(head + 24, rec_before[nblk], 8);
+    bool ok = out && fwrite(head, 1, sizeof head, out) == sizeof head;
+    for (uint64_t k = 0; ok && k <= nblk; k++) {
+        put_le(v, rec_before[k], 8);
+        ok = fwrite(v, 1, sizeof v, out) == sizeof v;
+    }
+    if (out && fclose(out) != 0) ok = false;
+    if (!ok) {
+        if (!o.quiet) fprintf(stderr, "bzx: %s: %s\n", oname.c_str(), strerror(errno));
+        unlink(oname.c_str());
+        return 1;
+    }
+    if (o.verbose)
+        fprintf(stderr, "  %s: %llu lines end in %llu blocks\n", oname.c_str(), (unsigned long long)rec_before[nblk],
+                (unsigned long long)nblk);
+    return 0;
+}
+
+// FILE.bz2 -> FILE.bz2.bzxi, and with --lines FILE.bz2.bzxr
 static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
 {
     const char *name = f.c_str();
     bzx_index *ix = nullptr;
-    if (feed_index(o, ctx, f, false, &ix)) return 1;
+    if (feed_index(o, ctx, f, false, &ix, o.lines ? LINE_DELIM : -1)) return 1;
     const bzx_index_entry *e = nullptr;
     bzx_index_info info;
+    const uint64_t *rb = nullptr;
+    uint64_t nrb = 0;
     int ret = 0, rc;
     if ((rc = bzx_index_get(ix, &e, &info))) ret = fail(o, "indexing failed", name, ctx, rc);
+    if (!ret && o.lines && (rc = bzx_index_get_records(ix, &rb, &nrb))) ret = fail(o, "indexing failed", name, ctx, rc);
     if (!ret) ret = write_bzxi(o, f + ".bzxi", e, info);
+    if (!ret && o.lines) ret = write_bzxr(o, f + ".bzxr", rb, nrb);
     bzx_index_end(ix);
     return ret;
 }
@@ -673,6 +716,88 @@ static int do_ranges(const Opts &o, bzx_ctx *ctx, const std::string &f)
     return ret;
 }
 
+// Lines [first, first + count) of FILE.bz2 to standard output, from FILE.bz2.bzxi, FILE.bz2.bzxr and the byte intervals of
+// the file that bzx_records_pieces names.
+static int do_lines(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    std::vector<bzx_index_entry> e;
+    uint64_t out_bytes = 0, file_size = 0;
+    FILE *in = nullptr;
+    if (load_index(o, f, e, &out_bytes, &in, &file_size)) return 1;
+    const uint64_t nblk = e.size();
+    int ret = 0;
+    size_t need = 0, read_bytes = 0;
+    uint32_t np = 0;
+    std::vector<uint8_t> out;
+    try {
+        const std::string rname = f + ".bzxr";
+        std::vector<uint8_t> x;
+        std::vector<uint64_t> rb;
+        FILE *rf = fopen(rname.c_str(), "rb");
+        const bool rok = rf && read_all(rf, x);
+        if (rf) fclose(rf);
+        if (!rf) {
+            ret = range_refuse(o, f, ("no record table " + rname + " (write it with bzx --index --lines " + f + ")").c_str());
+        } else if (!rok || x.size() < BZXR_HEADER || memcmp(x.data(), "BZXR", 4) != 0 || get_le(x.data() + 4, 4) != 1 ||
+                   get_le(x.data() + 8, 4) != (uint64_t)LINE_DELIM) {
+            ret = range_refuse(o, f, ("not a bzx line table of version 1: " + rname).c_str());
+        } else if (get_le(x.data() + 16, 8) != nblk || (x.size() - BZXR_HEADER) % 8 || (x.size() - BZXR_HEADER) / 8 != nblk + 1) {
+            ret = range_refuse(o, f, "the record table and the index describe different block counts: write both again with bzx --index --lines");
+        } else {
+            rb.resize(nblk + 1);
+            for (uint64_t k = 0; k <= nblk; k++) rb[k] = get_le(x.data() + BZXR_HEADER + 8 * k, 8);
+            if (bzx_records_pieces(e.data(), nblk, rb.data(), 1, &o.lines_first, &o.lines_count, nullptr, nullptr, 0, &np) == BZX_E_PARAM)
+                ret = range_refuse(o, f, "the record table is damaged (it descends)");
+        }
+        if (!ret) {
+            std::vector<uint64_t> bases(np), lens(np);
+            std::vector<std::vector<uint8_t>> held(np);
+            std::vector<bzx_piece> pieces(np);
+            if (np && bzx_records_pieces(e.data(), nblk, rb.data(), 1, &o.lines_first, &o.lines_count, bases.data(), lens.data(), np, &np))
+                ret = fail(o, "out of memory", f.c_str(), nullptr, BZX_E_NOMEM);
+            for (uint32_t j = 0; !ret && j < np; j++) {
+                if (bases[j] + lens[j] > file_size) {
+                    ret = range_refuse(o, f, "the index does not match the file (a block ends behind it)");
+                    break;
+                }
+                held[j].resize((size_t)lens[j]);
+                if (fseeko(in, (off_t)bases[j], SEEK_SET) != 0 || fread(held[j].data(), 1, held[j].size(), in) != held[j].size())
+                    ret = fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK);
+                pieces[j] = bzx_piece{held[j].data(), bases[j], lens[j]};
+                read_bytes += held[j].size();
+            }
+            // room: the decoded bytes of the blocks from the one that holds the first line's start to the one that holds
+            // the last line's end
+            uint64_t a = 0, z = 0, j = 0, room = 0;
+            const uint64_t hi = o.lines_count > ~0ull - o.lines_first ? ~0ull : o.lines_first + o.lines_count;
+            if (o.lines_first) bzx_records_span(rb.data(), nblk, o.lines_first, &a, &j);
+            bzx_records_span(rb.data(), nblk, hi, &z, &j);
+            if (a < nblk && hi) {
+                z = std::min(z, nblk - 1);
+                room = e[z].out_off + e[z].out_len - e[a].out_off;
+            }
+            if (!ret) {
+                size_t out_off = 0, got = 0;
+                int status = 0;
+                out.resize(room ? (size_t)room : 1);
+                const int rc = bzx_decompress_records_buffer(ctx, pieces.data(), np, e.data(), nblk, rb.data(), LINE_DELIM, 1,
+                                                             &o.lines_first, &o.lines_count, out.data(), (size_t)room, &out_off, &got,
+                                                             &status, &need);
+                if (rc) ret = fail(o, "line read failed", f.c_str(), ctx, rc);
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        ret = fail(o, "out of memory", f.c_str(), nullptr, BZX_E_NOMEM);
+    }
+    fclose(in);
+    if (!ret && need && fwrite(out.data(), 1, need, stdout) != need) ret = fail(o, strerror(errno), f.c_str(), nullptr, BZX_OK);
+    if (!ret && fflush(stdout) != 0) ret = 1;
+    if (!ret && o.verbose)
+        fprintf(stderr, "  %s: lines [%llu, +%llu): %zu bytes, %u pieces (%zu bytes) of the file read\n", f.c_str(),
+                (unsigned long long)o.lines_first, (unsigned long long)o.lines_count, need, np, read_bytes);
+    return ret;
+}
+
 // The end of one file's work: output flushed and closed (or removed after a failure), input removed unless -k.
 static int finish_file(const Opts &o, FILE *out, const std::string &oname, const std::string &f, int r)
 {
@@ -858,6 +983,19 @@ int main(int argc, char **argv)
                 o.range_off = strtoull(x.c_str(), nullptr, 10);
                 o.range_len = strtoull(y.c_str(), nullptr, 10);
             }
+            else if (a == "--lines") {                      // alone with --index; FIRST:COUNT behind it with -dc
+                o.lines = true;
+                const std::string v = i + 1 < argc ? argv[i + 1] : "";
+                const size_t c = v.find(':');
+                const std::string x = v.substr(0, c), y = c == std::string::npos ? "" : v.substr(c + 1);
+                if (!x.empty() && !y.empty() && x.size() <= 19 && y.size() <= 19 && x.find_first_not_of("0123456789") == std::string::npos &&
+                    y.find_first_not_of("0123456789") == std::string::npos) {
+                    i++;
+                    o.lines_range = true;
+                    o.lines_first = strtoull(x.c_str(), nullptr, 10);
+                    o.lines_count = strtoull(y.c_str(), nullptr, 10);
+                }
+            }
             else if (a == "--ranges" || a.rfind("--ranges=", 0) == 0) {
                 o.ranges = a == "--ranges" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
                 if (o.ranges.empty()) { fprintf(stderr, "bzx: --ranges takes a file of OFF:LEN lines\n"); return 1; }
@@ -936,6 +1074,30 @@ int main(int argc, char **argv)
         }
         bzx_ctx_destroy(ctx);
         return trouble ? 1 : lost;
+    }
+    if (o.lines) {
+        const char *why = o.with_index || o.recover || o.range || !o.ranges.empty()
+                              ? "--lines does not go with --with-index, --recover, --range or --ranges"
+                          : o.index && o.lines_range ? "--index --lines takes no FIRST:COUNT"
+                          : !o.index && !o.lines_range ? "--lines goes with --index, or as -dc --lines FIRST:COUNT FILE.bz2"
+                          : !o.index && (o.mode != UNZIP || !o.to_stdout) ? "--lines FIRST:COUNT goes with -dc"
+                          : !o.index && (o.files.size() != 1 || o.files[0] == "-") ? "--lines FIRST:COUNT takes one file, not standard input"
+                                                                                   : nullptr;
+        if (why) {
+            fprintf(stderr, "bzx: %s\n", why);
+            return 1;
+        }
+        if (!o.index) {
+            bzx_ctx *ctx = nullptr;
+            const int rc = bzx_ctx_create(0, 0, &ctx);
+            if (rc) {
+                fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
+                return 2;
+            }
+            const int ret = do_lines(o, ctx, o.files[0]);
+            bzx_ctx_destroy(ctx);
+            return ret;
+        }
     }
     if (!o.ranges.empty()) {
         if (o.index || o.range) { fprintf(stderr, "bzx: --ranges does not go with --index or --range\n"); return 1; }
