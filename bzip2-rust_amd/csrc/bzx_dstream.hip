@@ -574,6 +574,8 @@ struct bzx_index {
     std::vector<bzx_index_entry> entries;
     std::vector<bzx_gap> gaps;                             // (salvage)
     std::vector<uint64_t> rec;                             // (bzx_index_count_records) delimiters before every entry, and T
+    std::vector<uint64_t> hits;                            // (bzx_index_find) the first max_hits hits, ascending
+    uint64_t hit_total = 0;                                // ... and how many there are
     bool fed = false;                                      // bzx_index_feed has been called
 };
 
@@ -639,6 +641,16 @@ struct bzx_dstream {
     // ... with bzx_index_count_records: one count per slab, and behind the nb records of a pass's copy its nb counts
     int rec_delim = -1;
     DevMem<uint32_t> d_rcnt;
+    // ... with bzx_index_find: a BzxFindOut in front of the pass's records in d_ix / h_ix (find_off bytes of both), the
+    // sections' counts, one emit window, and the last m - 1 verified bytes, in which the next pass's straddling hits start
+    bool find_on = false;
+    size_t find_off = 0;
+    BzxFindPat find_pat = {};
+    uint64_t find_max = 0;
+    uint32_t find_inline = 0;          // room of the pass's inline emit
+    DevMem<uint32_t> d_fsec, d_fwin;
+    PinMem<uint32_t> h_fwin;
+    std::vector<uint8_t> find_carry;
     // DS_SALVAGE (bzx_salvage_*): the index mode's memory, with the tables of the salvage kernels in place of d_meta / d_ix
     DsSvState sv = {};                 // the walk's state between passes and windows
     DevMem<DsSvCand> d_svc;
@@ -905,6 +917,8 @@ static void ds_launch_layout(bzx_dstream *s, uint32_t q)
                            (uint64_t)DS_STAGE_BYTES, s->d_dst.get(), s->d_rec.get());
 }
 
+static void ds_launch_find(bzx_dstream *s, uint32_t q);     // (bzx_index_find: below)
+
 // Behind the CRCs of the nb blocks a pass may place: the verdict, then what the mode leaves for the host next to its
 // record -- the index's entries, or the salvage walk over the round's candidates (which runs without a block too).
 static int ds_launch_verdict(bzx_dstream *s, uint32_t q, uint32_t nb)
@@ -926,12 +940,70 @@ static int ds_launch_verdict(bzx_dstream *s, uint32_t q, uint32_t nb)
                        s->d_rec.get());
     if (s->mode == DS_INDEX) {
         const bool counting = s->rec_delim >= 0;
+        DsIxRec *tab = reinterpret_cast<DsIxRec *>(s->d_ix.get<uint8_t>() + s->find_off);
         hipLaunchKernelGGL(bzx_ds_index_kernel, dim3(1), dim3(64), 0, st, B, s->d_chain.get(), s->d_meta.get(), s->wbase * 8, s->d_rec.get(),
-                           s->d_ix.get(), (const uint32_t *)s->d_rcnt.get(),
-                           counting ? reinterpret_cast<uint32_t *>(s->d_ix.get() + nb) : nullptr);
+                           tab, (const uint32_t *)s->d_rcnt.get(), counting ? reinterpret_cast<uint32_t *>(tab + nb) : nullptr);
+        if (s->find_on) ds_launch_find(s, q);
         // (the round's share of the table; the pass wrote its first placed - pass_j0 entries, the host reads
         // r.good <= that many, the rest is what bzx_index_begin zeroed or an earlier pass left)
-        HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, nb * (sizeof(DsIxRec) + (counting ? 4 : 0)), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_ix, s->d_ix, s->find_off + nb * (sizeof(DsIxRec) + (counting ? 4 : 0)), hipMemcpyDeviceToHost, st));
+    }
+    return BZX_OK;
+}
+
+// bzx_index_find, behind the verdict of a pass: count, scan and the emit of the first hits over the verified bytes of the
+// staging area (rec->good_bytes, read on the device), all next to the pass's index records.
+static void ds_launch_find(bzx_dstream *s, uint32_t q)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    BzxFindOut *fo = s->d_ix.get<BzxFindOut>();
+    const uint64_t *len = &s->d_rec.get()->good_bytes;
+    const uint8_t *stage = s->d_stage[q].get();
+    const uint32_t grid = bzx_find_grid(DS_STAGE_BYTES, (uint32_t)ctx->n_cu);
+    const uint64_t have = s->ix->hits.size();
+    s->find_inline = (uint32_t)std::min<uint64_t>(FIND_INLINE_HITS, s->find_max > have ? s->find_max - have : 0);
+    bzx_launch_find_count(stage, len, s->find_pat, s->d_fsec.get(), grid, st);
+    bzx_launch_find_scan(stage, len, s->find_pat.m, s->d_fsec.get(), nullptr, &fo->count, fo, st);
+    bzx_launch_find_emit(stage, len, s->find_pat, s->d_fsec.get(), nullptr, &fo->count, 0, s->find_inline, fo->hits, grid, st);
+}
+
+// ... and behind the pass's synchronisation: the hits that straddle into the pass (found here, in the carried bytes and
+// the pass's first ones: both parts are shorter than the pattern, so every match there straddles), then the pass's own
+// -- the inline ones, and while the list has room the rest in windows of FIND_WINDOW_HITS, one emit launch, one copy and
+// one synchronisation each (the staging bytes and the sections' sums stay until the next pass).  base: the decoded
+// bytes before the pass.
+static int ds_find_digest(bzx_dstream *s, uint32_t q, uint64_t base)
+{
+    bzx_ctx *ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    bzx_index *ix = s->ix;
+    const BzxFindOut &fo = *s->h_ix.get<BzxFindOut>();
+    const uint32_t m = s->find_pat.m;
+    const uint8_t *pat = reinterpret_cast<const uint8_t *>(s->find_pat.w);
+    std::vector<uint8_t> &c = s->find_carry;
+    const size_t nc = c.size();
+    c.insert(c.end(), fo.head, fo.head + fo.nedge);
+    for (size_t i = 0; i < nc && i + m <= c.size(); i++) {
+        if (memcmp(c.data() + i, pat, m)) continue;
+        ix->hit_total++;
+        if (ix->hits.size() < s->find_max) ix->hits.push_back(base - nc + i);
+    }
+    if (fo.nedge == m - 1) c.assign(fo.tail, fo.tail + fo.nedge);       // (a shorter pass extends the carry)
+    else if (c.size() > m - 1) c.erase(c.begin(), c.end() - (m - 1));
+    ix->hit_total += fo.count;
+    uint64_t skip = std::min<uint64_t>(fo.count, s->find_inline);
+    for (uint64_t i = 0; i < skip && ix->hits.size() < s->find_max; i++) ix->hits.push_back(base + fo.hits[i]);
+    const uint32_t grid = bzx_find_grid(DS_STAGE_BYTES, (uint32_t)ctx->n_cu);
+    while (skip < fo.count && ix->hits.size() < s->find_max) {
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(FIND_WINDOW_HITS, std::min<uint64_t>(fo.count - skip, s->find_max - ix->hits.size()));
+        bzx_launch_find_emit(s->d_stage[q].get(), &s->d_rec.get()->good_bytes, s->find_pat, s->d_fsec.get(), nullptr,
+                             &s->d_ix.get<BzxFindOut>()->count, skip, cap, s->d_fwin.get(), grid, st);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_fwin, s->d_fwin, (size_t)cap * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));              // a window's synchronisation
+        for (uint32_t i = 0; i < cap; i++) ix->hits.push_back(base + s->h_fwin[i]);
+        skip += cap;
     }
     return BZX_OK;
 }
@@ -981,13 +1053,19 @@ static int ds_digest(bzx_dstream *s, uint32_t q, bool fresh)
         s->rd_active = true;
     }
     if (s->mode == DS_INDEX) {                               // their bytes stay
-        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(s->h_ix.get() + s->rd_nb);      // (counting: behind the records)
+        const DsIxRec *tab = reinterpret_cast<const DsIxRec *>(s->h_ix.get<uint8_t>() + s->find_off);
+        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(tab + s->rd_nb);                // (counting: behind the records)
+        const uint64_t pass_base = s->info.out_bytes;
         for (uint32_t j = 0; j < r.good; j++) {
-            const DsIxRec &x = s->h_ix[j];
+            const DsIxRec &x = tab[j];
             if (s->rec_delim >= 0) s->ix->rec.push_back(s->ix->rec.back() + cnt[j]);
             s->ix->entries.push_back(ds_entry(x.bit, s->info.out_bytes, x.out_len, x.crc, x.img_bits,
                                               s->info.nstreams + (x.meta >> 4), x.meta & 15u));
             s->info.out_bytes += x.out_len;
+        }
+        if (s->find_on && s->rd_nb) {                        // (a round without a block copies nothing back)
+            const int rc = ds_find_digest(s, q, pass_base);
+            if (rc) return rc;
         }
     } else if (r.good_bytes) {                               // the verified bytes travel beside the next pass
         HIP_TRY(ctx, hipMemcpyAsync(s->h_stage[q], s->d_stage[q], r.good_bytes, hipMemcpyDeviceToHost, s->s_d2h));
@@ -1337,8 +1415,9 @@ extern "C" int bzx_index_count_records(bzx_index *ix, int delim)
     } catch (const std::bad_alloc &) {
         return BZX_E_NOMEM;
     }
-    if (!s->d_rcnt.reserve(R * 4) || !s->d_ix.reserve(R * (sizeof(DsIxRec) + 4)) || !s->h_ix.reserve(R * (sizeof(DsIxRec) + 4)) ||
-        hipMemset(s->d_ix, 0, R * (sizeof(DsIxRec) + 4)) != hipSuccess || hipMemset(s->d_rcnt, 0, R * 4) != hipSuccess) {
+    const size_t tab = s->find_off + R * (sizeof(DsIxRec) + 4);
+    if (!s->d_rcnt.reserve(R * 4) || !s->d_ix.reserve(tab) || !s->h_ix.reserve(tab) ||
+        hipMemset(s->d_ix, 0, tab) != hipSuccess || hipMemset(s->d_rcnt, 0, R * 4) != hipSuccess) {
         ctx->err = "bzx_index_count_records: device or pinned allocation failed";
         return BZX_E_NOMEM;
     }
@@ -1360,6 +1439,70 @@ extern "C" int bzx_index_get_records(const bzx_index *ix, const uint64_t **rec_b
     }
     *rec_before = ix->rec.data();
     *n = ix->entries.size();
+    return BZX_OK;
+}
+
+// Find switched on: the pass gains the three kernels of bzx_find.hip behind its verdict and a BzxFindOut in front of the
+// records in the copy that brings its entries back; everything the device side needs is allocated here, between begin
+// and the first feed, so that an index without find allocates what it always did.
+static_assert(sizeof(BzxFindOut) % 8 == 0, "the index records behind it hold 64-bit values");
+extern "C" int bzx_index_find(bzx_index *ix, const uint8_t *pat, size_t m, uint64_t max_hits)
+{
+    if (!ix || !ix->s || !ix->s->ctx) return BZX_E_PARAM;
+    bzx_dstream *s = ix->s;
+    bzx_ctx *ctx = s->ctx;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    if (s->mode != DS_INDEX) {
+        ctx->err = "bzx_index_find: not on a salvage index (its entries come from the device walk)";
+        return BZX_E_STATE;
+    }
+    if (ix->fed) {
+        ctx->err = "bzx_index_find: call it before the first bzx_index_feed";
+        return BZX_E_STATE;
+    }
+    BzxFindPat fp;
+    if (!bzx_find_pattern(pat, m, &fp)) {
+        ctx->err = "bzx_index_find: the pattern is NULL, empty or longer than BZX_FIND_MAX_PATTERN bytes";
+        return BZX_E_PARAM;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t R = s->R, before_dev = s->d_ix.bytes() + s->d_fsec.bytes() + s->d_fwin.bytes(),
+                 before_pin = s->h_ix.bytes() + s->h_fwin.bytes();
+    const size_t tab = sizeof(BzxFindOut) + R * (sizeof(DsIxRec) + (s->rec_delim >= 0 ? 4 : 0));
+    try {
+        ix->hits.clear();
+        s->find_carry.clear();
+        s->find_carry.reserve(2 * BZX_FIND_MAX_PATTERN);
+    } catch (const std::bad_alloc &) {
+        return BZX_E_NOMEM;
+    }
+    if (!s->d_fsec.reserve(bzx_find_sections(DS_STAGE_BYTES) * 4) || !s->d_fwin.reserve((size_t)FIND_WINDOW_HITS * 4) ||
+        !s->h_fwin.reserve((size_t)FIND_WINDOW_HITS * 4) || !s->d_ix.reserve(tab) || !s->h_ix.reserve(tab) ||
+        hipMemset(s->d_ix, 0, tab) != hipSuccess) {
+        ctx->err = "bzx_index_find: device or pinned allocation failed";
+        return BZX_E_NOMEM;
+    }
+    s->info.device_bytes += s->d_ix.bytes() + s->d_fsec.bytes() + s->d_fwin.bytes() - before_dev;
+    s->info.pinned_bytes += s->h_ix.bytes() + s->h_fwin.bytes() - before_pin;
+    s->find_on = true;
+    s->find_off = sizeof(BzxFindOut);
+    s->find_pat = fp;
+    s->find_max = max_hits;
+    ix->hit_total = 0;
+    return BZX_OK;
+}
+
+extern "C" int bzx_index_get_hits(const bzx_index *ix, const uint64_t **hits, uint64_t *nlisted, uint64_t *total)
+{
+    if (!ix || !ix->s || !ix->s->ctx || !hits || !nlisted || !total) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(ix->s->ctx->api_mu);
+    if (!ix->s->find_on) {
+        ix->s->ctx->err = "bzx_index_get_hits: find was not switched on (bzx_index_find)";
+        return BZX_E_STATE;
+    }
+    *hits = ix->hits.data();
+    *nlisted = ix->hits.size();
+    *total = ix->hit_total;
     return BZX_OK;
 }
 
@@ -1390,12 +1533,14 @@ extern "C" int bzx_index_get_gaps(const bzx_index *ix, const bzx_gap **gaps, uin
 // the feed loop.  A run that failed hands nothing out, except in the index mode: there the entries and `info` describe
 // the verified prefix, and the feed's code and text are the call's.
 static int ix_build(bzx_ctx *ctx, DsMode mode, const uint8_t *bz2, size_t len, std::vector<bzx_index_entry> &entries,
-                    bzx_index_info *info, std::vector<bzx_gap> &gaps, int delim = -1, std::vector<uint64_t> *rec = nullptr)
+                    bzx_index_info *info, std::vector<bzx_gap> &gaps, int delim = -1, std::vector<uint64_t> *rec = nullptr,
+                    const uint8_t *pat = nullptr, size_t m = 0, uint64_t max_hits = 0, std::vector<uint64_t> *hits = nullptr,
+                    uint64_t *hit_total = nullptr)
 {
     bzx_index *ix = nullptr;
     int rc = ix_begin(ctx, std::min<size_t>(std::max<size_t>(len, DS_MIN_CHUNK), (size_t)64 << 20), mode, &ix);
     if (rc) return rc;
-    if (rec && (rc = bzx_index_count_records(ix, delim))) {
+    if ((rec && (rc = bzx_index_count_records(ix, delim))) || (hits && (rc = bzx_index_find(ix, pat, m, max_hits)))) {
         const std::string why = ctx->err;
         bzx_index_end(ix);
         ctx->err = why;
@@ -1419,6 +1564,10 @@ static int ix_build(bzx_ctx *ctx, DsMode mode, const uint8_t *bz2, size_t len, s
         entries.swap(ix->entries);
         gaps.swap(ix->gaps);
         if (rec) rec->swap(ix->rec);
+        if (hits) {
+            hits->swap(ix->hits);
+            *hit_total = ix->hit_total;
+        }
     }
     bzx_index_end(ix);
     if (rc) ctx->err = why;
@@ -1462,6 +1611,26 @@ extern "C" int bzx_index_build_records_buffer(bzx_ctx *ctx, const uint8_t *bz2, 
     const size_t k = (size_t)std::min<uint64_t>(e.size(), cap_entries);
     if (r.size() > k) memcpy(rec_before, r.data(), (k + 1) * sizeof(uint64_t));
     return ix_copy_out(ctx, rc, e, entries, cap_entries, "bzx_index_build_records_buffer: more blocks than cap_entries");
+}
+
+extern "C" int bzx_find_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, const uint8_t *pat, size_t m, uint64_t *hits,
+                               uint64_t cap_hits, uint64_t *nlisted, uint64_t *total, bzx_index_entry *entries,
+                               uint64_t cap_entries, bzx_index_info *info)
+{
+    BzxFindPat fp;
+    if (!ctx || !nlisted || !total || !info || (len && !bz2) || (cap_hits && !hits) || (cap_entries && !entries) ||
+        !bzx_find_pattern(pat, m, &fp))
+        return BZX_E_PARAM;
+    memset(info, 0, sizeof(*info));
+    *nlisted = *total = 0;
+    std::vector<bzx_index_entry> e;
+    std::vector<bzx_gap> g;
+    std::vector<uint64_t> h;
+    const int rc = ix_build(ctx, DS_INDEX, bz2, len, e, info, g, -1, nullptr, pat, m, cap_hits, &h, total);
+    *nlisted = h.size();
+    if (!h.empty()) memcpy(hits, h.data(), h.size() * sizeof(uint64_t));
+    if (!entries && !cap_entries) return rc;                 // (the index is not wanted)
+    return ix_copy_out(ctx, rc, e, entries, cap_entries, "bzx_find_buffer: more blocks than cap_entries");
 }
 
 extern "C" int bzx_salvage_build_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, bzx_index_entry *entries,

@@ -304,3 +304,32 @@ int rg_upload(bzx_ctx *ctx, const bzx_piece *pc, uint32_t npc, const uint8_t *he
 // seg[b].cap); a segment without a pointer is skipped.
 void bzx_launch_rec_count(const BzxBlock *blk, const BzxDcDst *seg, uint32_t nseg, uint32_t delim, uint32_t *counts,
                           uint32_t n_cu, hipStream_t stream);
+
+// ---- bzx_find.hip: the hits of a pattern in a run of device bytes [p, p + *len), *len read on the device
+// Three launches: count (hits per section, a wave's 4 KiB of a tile), scan (sec[] becomes the exclusive sum, *after =
+// *before + the run's count; with `edges` also the run's first and last min(m - 1, *len) bytes) and emit (hit number k of
+// the numbering that starts at *before goes to out[k - skip] when skip <= k < skip + cap, as a position relative to p).
+#define FIND_TILE_BYTES 16384u               // start positions of a workgroup's tile, cut on 16-byte boundaries of the address
+#define FIND_SEC_BYTES (FIND_TILE_BYTES / 4) // ... of one wave's section of it
+#define FIND_INLINE_HITS 1024u               // hits of a pass that travel with its record
+#define FIND_WINDOW_HITS (1u << 20)          // hits per emit window behind them
+struct BzxFindPat {                          // the pattern, a kernel argument: bytes 0 .. m - 1 of w, zeros behind
+    uint32_t w[BZX_FIND_MAX_PATTERN / 4];
+    uint32_t m;
+};
+struct BzxFindOut {                          // what a pass leaves for the host in front of its index records
+    uint64_t count;                          // hits of the pass
+    uint32_t nedge, pad_;                    // min(m - 1, verified bytes of the pass)
+    uint8_t head[BZX_FIND_MAX_PATTERN], tail[BZX_FIND_MAX_PATTERN];      // its first and last nedge verified bytes
+    uint32_t hits[FIND_INLINE_HITS];         // its first hits, relative to the staging area
+};
+static inline size_t bzx_find_sections(uint64_t len) { return (size_t)((len + 15 + FIND_SEC_BYTES - 1) / FIND_SEC_BYTES) + 1; }
+uint32_t bzx_find_grid(uint64_t len, uint32_t n_cu);
+bool bzx_find_pattern(const uint8_t *pat, size_t m, BzxFindPat *out);
+void bzx_launch_find_count(const uint8_t *p, const uint64_t *len, const BzxFindPat &pat, uint32_t *sec, uint32_t grid,
+                           hipStream_t stream);
+void bzx_launch_find_scan(const uint8_t *p, const uint64_t *len, uint32_t m, uint32_t *sec, const uint64_t *before,
+                          uint64_t *after, BzxFindOut *edges, hipStream_t stream);
+void bzx_launch_find_emit(const uint8_t *p, const uint64_t *len, const BzxFindPat &pat, const uint32_t *sec,
+                          const uint64_t *before, const uint64_t *after, uint64_t skip, uint32_t cap, uint32_t *out,
+                          uint32_t grid, hipStream_t stream);

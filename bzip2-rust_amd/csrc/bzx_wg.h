@@ -35,6 +35,7 @@
 // bzx_uni(): a value every lane of the workgroup loaded from the same address, kept in a scalar register (values live
 // across calls would otherwise be spilled around every call: only 24 of 80 VGPRs are callee-saved).
 // bzx_bcast0(): lane 0's value to the whole wave (all lanes active).
+// bzx_bcast63(): lane 63's value to the whole wave (all lanes active): the wave total behind an inclusive scan.
 // bzx_tid_here(): the lane id, opaque to the optimiser: re-read at the top of a loop body it keeps address arithmetic
 // derived from it from being hoisted out of the loop, where dozens of such values would be spilled and reloaded from
 // scratch (global memory) inside the hot loops.
@@ -70,12 +71,14 @@ __device__ __forceinline__ uint32_t bzx_lds_ticket(uint32_t *ctr, bool valid) { 
 #define lds_order() hipemu::wave_sync()
 __device__ __forceinline__ uint32_t bzx_uni(uint32_t v) { return v; }
 __device__ __forceinline__ uint32_t bzx_bcast0(uint32_t v) { return __shfl(v, 0); }
+__device__ __forceinline__ uint32_t bzx_bcast63(uint32_t v) { return __shfl(v, 63); }
 __device__ __forceinline__ uint32_t bzx_tid_here() { return threadIdx.x; }
 #define bzx_drain_stores() do {} while (0)
 #else
 #define lds_order() asm volatile("" ::: "memory")
 __device__ __forceinline__ uint32_t bzx_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint32_t bzx_bcast0(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint32_t bzx_bcast63(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
 __device__ __forceinline__ uint32_t bzx_tid_here()
 {
     uint32_t t = threadIdx.x;

@@ -717,6 +717,56 @@ int bzx_stage_rec_count(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t n
 int bzx_stage_rec_select(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nq, const uint64_t *seg_offs,
                          const uint64_t *seg_lens, const uint32_t *js, int delim, uint32_t *pos_out, uint32_t *cnt_out);
 /*
+ * Find: "where does this byte string occur in what this .bz2 decodes to", answered by the index pass, which holds every
+ * verified block expanded on the device anyway.  Offsets come back, not data; the index the same pass leaves reads the
+ * surroundings of a hit (bzx_decompress_range_*, bzx_decompress_records_*).
+ * The rule.  D[0, N) is what bzx_decompress_buffer returns for the whole input, all streams of a concatenated file;
+ * pat[0, m) is 1..BZX_FIND_MAX_PATTERN bytes of any value.  A hit is a p with p + m <= N and D[p, p + m) == pat.  The hits
+ * are all such p in ascending order, overlapping ones included ("aa" in "aaaa": 0, 1, 2); the borders of blocks, streams,
+ * passes, rounds and windows do not exist for a hit.  total is their exact number; the list holds the first
+ * min(total, max_hits) of them.  Only verified bytes count: after BZX_E_DATA list and total describe the verified prefix,
+ * p + m <= the out_bytes of the entries bzx_index_get returns.
+ *
+ * bzx_index_find(ix, pat, m, max_hits): between bzx_index_begin and the first bzx_index_feed, as
+ * bzx_index_count_records, and in any order with it on the same object; BZX_E_STATE after a feed and on an object from
+ * bzx_salvage_begin, BZX_E_PARAM for NULL, m == 0 or m > BZX_FIND_MAX_PATTERN.  A second call replaces the pattern.  Off
+ * is the default and off means off: the index pass launches, copies, allocates and synchronises as it did.  On, a pass
+ * gains three launches behind its verdict (bzx_find.hip: count, scan, emit, over the verified bytes of its staging area) and,
+ * in the copy that brings its entries back, its hit count, its first inline_hits hits and its first and last m - 1
+ * verified bytes; a pass with at most inline_hits hits gains no synchronisation.  A pass with more launches emit again in
+ * windows of window_hits hits -- one launch, one copy and one synchronisation each -- until the list holds max_hits;
+ * beyond that hits are only counted.  A hit that straddles two passes is found on the host, in the carried last m - 1
+ * verified bytes and the first ones of the new pass.  Device memory is allocated by this call and fixed; only the host
+ * list grows, up to max_hits.
+ * bzx_index_get_hits: what has been found so far -- a hit becomes visible with the pass that verifies its last byte, and
+ * mid-stream an earlier result is a prefix of every later one; the pointer is valid as long as bzx_index_get's;
+ * BZX_E_STATE when find was not switched on.
+ * bzx_find_buffer: begin, find with max_hits = cap_hits, a loop over feed, end.  hits has room for cap_hits values;
+ * *nlisted of them are written, *total may be larger, which is no error.  entries / cap_entries / info as in
+ * bzx_index_build_buffer, BZX_E_OUTBUF and BZX_E_DATA included (after BZX_E_DATA the hits, the entries and info describe
+ * the verified prefix); entries may be NULL with cap_entries == 0: then the index is not returned and too many blocks is
+ * no error.
+ * bzx_find_geometry (no context, no device): how the kernels cut a run of bytes -- the tile of start positions one
+ * workgroup takes, on 16-byte boundaries of the address (a wave takes a quarter of it in steps of 64 lanes x 16 bytes) --
+ * and the two list sizes above.
+ * bzx_stage_find: the three kernels alone, for the parity tests (host pointers), over segments [seg_offs[i], +
+ * seg_lens[i]) of buf.  The device copy of buf starts on a 256-byte boundary, so seg_offs[i] mod 16 is the alignment the
+ * kernels see.  Segment i is searched on its own -- a hit lies wholly inside it, whatever bytes of buf follow --
+ * and counts_out[i] is its count.  The hits of all segments are numbered in segment order and ascending within a segment;
+ * numbers [skip, skip + cap) are written to hits_out as positions relative to their segment, *nwritten of them.
+ * BZX_E_PARAM when a segment leaves buf or is 2^32 bytes or longer, and for a pattern as above.
+ */
+#define BZX_FIND_MAX_PATTERN 256
+int bzx_index_find(bzx_index *ix, const uint8_t *pat, size_t m, uint64_t max_hits);
+int bzx_index_get_hits(const bzx_index *ix, const uint64_t **hits, uint64_t *nlisted, uint64_t *total);
+int bzx_find_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, const uint8_t *pat, size_t m, uint64_t *hits,
+                    uint64_t cap_hits, uint64_t *nlisted, uint64_t *total, bzx_index_entry *entries, uint64_t cap_entries,
+                    bzx_index_info *info);
+void bzx_find_geometry(uint32_t *tile_bytes, uint32_t *inline_hits, uint32_t *window_hits);
+int bzx_stage_find(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nseg, const uint64_t *seg_offs,
+                   const uint64_t *seg_lens, const uint8_t *pat, size_t m, uint64_t skip, uint32_t cap, uint32_t *counts_out,
+                   uint64_t *hits_out, uint32_t *nwritten);
+/*
  * The inverse BWT alone, for the parity tests (host pointers): L[0, n) and orig_ptr < n -> the RLE1 image img_out[0, n)
  * and its expansion raw_out (at most raw_cap bytes are written; *raw_len is the whole expanded length).  wide = 0 runs
  * the one-lane walk of the one-shot, batch and stream decoders, wide = 1 the many-lane walk of the range reads; both

@@ -29,6 +29,11 @@
 // nblk + 1 u64 values); -dc --lines FIRST:COUNT FILE.bz2 reads .bzxi and .bzxr (and refuses when either is missing or they
 // describe different block counts), reads only the bytes of the file that bzx_records_pieces names and writes lines
 // [FIRST, FIRST + COUNT), numbered from 0, to standard output through bzx_decompress_records_buffer.
+// --find STRING / --find-hex HEX FILE.bz2 ... prints where the byte string occurs in what every FILE decodes to: one decimal
+// offset per line, FILE:OFFSET with several files, through bzx_index_find on the index pass (nothing decoded leaves the
+// device); --count prints the total only; --max-hits N (default 1000000) bounds the list, and one line on standard error
+// says how many more hits there were.  With --index, and with --index --lines, the same pass writes .bzxi and .bzxr.  Exit
+// status as grep's: 0 a hit, 1 none, 2 an error or a damaged file (whose verified prefix is still searched and printed).
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,6 +63,9 @@ struct Opts {
     std::string ranges;                // --ranges LIST
     bool lines = false, lines_range = false;       // --lines; --lines FIRST:COUNT
     uint64_t lines_first = 0, lines_count = 0;
+    bool find = false, count = false;  // --find STRING or --find-hex HEX; --count
+    std::string find_pat;
+    uint64_t max_hits = 1000000;       // --max-hits N
 };
 
 static void help()
@@ -75,6 +83,10 @@ static void help()
          "  --ranges LIST     with -dc: the same for every OFF:LEN line of the text file LIST, in one call, back to back\n"
          "  --lines           with --index: also write FILE.bzxr, the table of lines per block\n"
          "  --lines FIRST:COUNT  with -dc: lines [FIRST, FIRST + COUNT) of FILE, numbered from 0, through FILE.bzxi and FILE.bzxr\n"
+         "  --find STRING     print the offsets at which STRING occurs in what every FILE (a .bz2) decodes to, one per line\n"
+         "  --find-hex HEX    the same for the bytes HEX names (1 to 256 of them), e.g. 0d0a00ff\n"
+         "                    --count: the total only; --max-hits N: list at most N (default 1000000); with --index (and\n"
+         "                    --lines) the same pass writes the index; exit status 0: a hit, 1: none, 2: error or damage\n"
          "  --recover         write every intact block of a damaged FILE.bz2 to FILE.recovered (-c: standard output) and\n"
          "                    one line per gap to standard error; with --index also FILE.bz2.bzxi for --range;\n"
          "                    exit status 0: nothing lost, 2: data lost, 1: trouble\n"
@@ -299,7 +311,15 @@ static int write_bzxi(const Opts &o, const std::string &oname, const bzx_index_e
 
 // FILE.bz2 through bzx_index_feed, 64 MiB chunks in page-locked memory as -d reads them: the index (--index), or the
 // salvage index (--recover).  -> 0 and the open index, or 1 after a message.
-static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool salvage, bzx_index **out, int delim = -1)
+// find (--find): the pattern and the list size of bzx_index_find; then a file that does not verify leaves the index of
+// its verified prefix open, after the message, and *damaged says so.
+struct FindReq {
+    const std::string *pat;
+    uint64_t max_hits;
+    bool damaged = false;
+};
+static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool salvage, bzx_index **out, int delim = -1,
+                      FindReq *find = nullptr)
 {
     *out = nullptr;
     const char *name = f.c_str();
@@ -312,6 +332,8 @@ static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool sa
     bzx_index *ix = nullptr;
     int rc = salvage ? bzx_salvage_begin(ctx, CH, &ix) : bzx_index_begin(ctx, CH, &ix);
     if (!rc && delim >= 0 && (rc = bzx_index_count_records(ix, delim))) bzx_index_end(ix);
+    if (!rc && find && (rc = bzx_index_find(ix, (const uint8_t *)find->pat->data(), find->pat->size(), find->max_hits)))
+        bzx_index_end(ix);
     if (rc) {
         fclose(in);
         return fail(o, "cannot start", name, ctx, rc);
@@ -336,6 +358,10 @@ static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool sa
         rc = bzx_index_feed(ix, ibuf + off, have - off, eof ? 1 : 0, &used, &done);
         if (rc) {
             ret = fail(o, salvage ? "salvage failed" : "indexing failed", name, ctx, rc);
+            if (rc == BZX_E_DATA && find) {
+                find->damaged = true;
+                ret = 0;
+            }
             break;
         }
         off += used;
@@ -393,6 +419,45 @@ static int do_index(const Opts &o, bzx_ctx *ctx, const std::string &f)
     if (!ret && o.lines) ret = write_bzxr(o, f + ".bzxr", rb, nrb);
     bzx_index_end(ix);
     return ret;
+}
+
+// --find: the hits of FILE.bz2 to standard output; with --index also what do_index writes, from the same pass (not for a
+// damaged file).  -> 0: a hit, 1: none, 2: an error or a damaged file.
+static int do_find(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    const char *name = f.c_str();
+    const bool multi = o.files.size() > 1;
+    bzx_index *ix = nullptr;
+    FindReq req{&o.find_pat, o.count ? 0 : o.max_hits};
+    if (feed_index(o, ctx, f, false, &ix, o.index && o.lines ? LINE_DELIM : -1, &req)) return 2;
+    const bool damaged = req.damaged;
+    const uint64_t *hits = nullptr, *rb = nullptr;
+    uint64_t nlisted = 0, total = 0, nrb = 0;
+    const bzx_index_entry *e = nullptr;
+    bzx_index_info info;
+    int rc, ret = 0;
+    if ((rc = bzx_index_get_hits(ix, &hits, &nlisted, &total))) ret = fail(o, "find failed", name, ctx, rc);
+    if (!ret && o.count) {
+        if (multi) printf("%s:", name);
+        printf("%llu\n", (unsigned long long)total);
+    } else if (!ret) {
+        for (uint64_t i = 0; i < nlisted; i++) {
+            if (multi) printf("%s:", name);
+            printf("%llu\n", (unsigned long long)hits[i]);
+        }
+        if (total > nlisted && !o.quiet)
+            fprintf(stderr, "bzx: %s: %llu more hits not listed (--max-hits %llu)\n", name, (unsigned long long)(total - nlisted),
+                    (unsigned long long)o.max_hits);
+    }
+    if (!ret && fflush(stdout) != 0) ret = fail(o, strerror(errno), "standard output", nullptr, BZX_OK);
+    if (!ret && o.index && !damaged) {
+        if ((rc = bzx_index_get(ix, &e, &info))) ret = fail(o, "indexing failed", name, ctx, rc);
+        if (!ret && o.lines && (rc = bzx_index_get_records(ix, &rb, &nrb))) ret = fail(o, "indexing failed", name, ctx, rc);
+        if (!ret) ret = write_bzxi(o, f + ".bzxi", e, info);
+        if (!ret && o.lines) ret = write_bzxr(o, f + ".bzxr", rb, nrb);
+    }
+    bzx_index_end(ix);
+    return ret || damaged ? 2 : total ? 0 : 1;
 }
 
 static int range_refuse(const Opts &o, const std::string &f, const char *why)
@@ -949,6 +1014,9 @@ static int flush_batch(const Opts &o, bzx_ctx *ctx, std::vector<Pending> &pend, 
 int main(int argc, char **argv)
 {
     Opts o;
+    int bad = 1;                                             // a usage error; 2, as grep's, when the command line asks for a find
+    for (int i = 1; i < argc; i++)
+        if (!strncmp(argv[i], "--find", 6) || !strcmp(argv[i], "--count") || !strncmp(argv[i], "--max-hits", 10)) bad = 2;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "-" || a[0] != '-') {
@@ -977,7 +1045,7 @@ int main(int argc, char **argv)
                 if (x.empty() || y.empty() || x.size() > 19 || y.size() > 19 || x.find_first_not_of("0123456789") != std::string::npos ||
                     y.find_first_not_of("0123456789") != std::string::npos) {
                     fprintf(stderr, "bzx: --range takes OFF:LEN in bytes, e.g. 41000000000:65536 (got \"%s\")\n", v.c_str());
-                    return 1;
+                    return bad;
                 }
                 o.range = true;
                 o.range_off = strtoull(x.c_str(), nullptr, 10);
@@ -996,9 +1064,33 @@ int main(int argc, char **argv)
                     o.lines_count = strtoull(y.c_str(), nullptr, 10);
                 }
             }
+            else if (a == "--find" || a.rfind("--find=", 0) == 0) {
+                if (a == "--find" && i + 1 >= argc) { fprintf(stderr, "bzx: --find takes a string\n"); return bad; }
+                o.find = true;
+                o.find_pat = a == "--find" ? argv[++i] : a.substr(7);
+            }
+            else if (a == "--find-hex" || a.rfind("--find-hex=", 0) == 0) {
+                const std::string v = a == "--find-hex" ? (i + 1 < argc ? argv[++i] : "") : a.substr(11);
+                if (v.empty() || v.size() % 2 || v.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos) {
+                    fprintf(stderr, "bzx: --find-hex takes an even number of hex digits, e.g. 0d0a00ff (got \"%s\")\n", v.c_str());
+                    return 2;
+                }
+                o.find = true;
+                o.find_pat.clear();
+                for (size_t k = 0; k < v.size(); k += 2) o.find_pat.push_back((char)strtoul(v.substr(k, 2).c_str(), nullptr, 16));
+            }
+            else if (a == "--count") o.count = true;
+            else if (a == "--max-hits" || a.rfind("--max-hits=", 0) == 0) {
+                const std::string v = a == "--max-hits" ? (i + 1 < argc ? argv[++i] : "") : a.substr(11);
+                if (v.empty() || v.size() > 19 || v.find_first_not_of("0123456789") != std::string::npos) {
+                    fprintf(stderr, "bzx: --max-hits takes a number (got \"%s\")\n", v.c_str());
+                    return 2;
+                }
+                o.max_hits = strtoull(v.c_str(), nullptr, 10);
+            }
             else if (a == "--ranges" || a.rfind("--ranges=", 0) == 0) {
                 o.ranges = a == "--ranges" ? (i + 1 < argc ? argv[++i] : "") : a.substr(9);
-                if (o.ranges.empty()) { fprintf(stderr, "bzx: --ranges takes a file of OFF:LEN lines\n"); return 1; }
+                if (o.ranges.empty()) { fprintf(stderr, "bzx: --ranges takes a file of OFF:LEN lines\n"); return bad; }
             }
             else if (a == "--devices" || a.rfind("--devices=", 0) == 0) {
                 std::string list = a == "--devices" ? (i + 1 < argc ? argv[++i] : "") : a.substr(10);
@@ -1008,17 +1100,17 @@ int main(int argc, char **argv)
                     const std::string t = list.substr(p, q - p);
                     if (t.empty() || t.size() > 4 || t.find_first_not_of("0123456789") != std::string::npos) {
                         fprintf(stderr, "bzx: --devices takes ordinals separated by commas, e.g. 0,1 (got \"%s\")\n", list.c_str());
-                        return 1;
+                        return bad;
                     }
                     o.devices.push_back(atoi(t.c_str()));
                     p = q + 1;
                 }
                 if (o.devices.size() > BZX_MAX_DEVICES) {
                     fprintf(stderr, "bzx: --devices takes at most %d entries\n", BZX_MAX_DEVICES);
-                    return 1;
+                    return bad;
                 }
             }
-            else { fprintf(stderr, "bzx: unexpected argument %s\n", a.c_str()); return 1; }
+            else { fprintf(stderr, "bzx: unexpected argument %s\n", a.c_str()); return bad; }
         } else {
             for (size_t k = 1; k < a.size(); k++) {
                 const char c = a[k];
@@ -1034,9 +1126,37 @@ int main(int argc, char **argv)
                 else if (c == 's') {}
                 else if (c == 'h') { help(); return 0; }
                 else if (c == 'V' || c == 'L') { printf("bzx, bzip2 block compression on MI355X; %s\n", bzx_version()); return 0; }
-                else { fprintf(stderr, "bzx: unexpected flag -%c\n", c); return 1; }
+                else { fprintf(stderr, "bzx: unexpected flag -%c\n", c); return bad; }
             }
         }
+    }
+    if (o.find || o.count) {                                 // (exit status 2 for every error, as grep's)
+        const char *why = !o.find ? "--count goes with --find or --find-hex"
+                          : o.find_pat.empty() || o.find_pat.size() > BZX_FIND_MAX_PATTERN ? "--find takes 1 to 256 bytes"
+                          : o.with_index || o.recover || o.range || !o.ranges.empty() || o.lines_range || o.mode_set || o.to_stdout
+                              ? "--find goes with --index, --index --lines, --count, --max-hits, -q and -v only"
+                          : o.lines && !o.index ? "--lines goes with --index"
+                          : o.files.empty()     ? "--find takes files"
+                                                : nullptr;
+        for (const std::string &f : o.files)
+            if (!why && f == "-") why = "--find needs a file, not standard input";
+        if (why) {
+            fprintf(stderr, "bzx: %s\n", why);
+            return 2;
+        }
+        bzx_ctx *ctx = nullptr;
+        const int rc = bzx_ctx_create(0, UNZIP_SLABS, &ctx);
+        if (rc) {
+            fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
+            return 2;
+        }
+        int worst = 1;
+        for (const std::string &f : o.files) {
+            const int r = do_find(o, ctx, f);
+            worst = r == 2 || worst == 2 ? 2 : r == 0 ? 0 : worst;
+        }
+        bzx_ctx_destroy(ctx);
+        return worst;
     }
     if (o.with_index) {
         const char *why = o.index || o.range || !o.ranges.empty() ? "--with-index does not go with --index, --range or --ranges"
