@@ -576,6 +576,7 @@ struct bzx_index {
     std::vector<uint64_t> rec;                             // (bzx_index_count_records) delimiters before every entry, and T
     std::vector<uint64_t> hits;                            // (bzx_index_find) the first max_hits hits, ascending
     uint64_t hit_total = 0;                                // ... and how many there are
+    std::vector<uint64_t> lines;                           // (bzx_index_find_lines) lines[i] = delimiters of D before hits[i]
     bool fed = false;                                      // bzx_index_feed has been called
 };
 
@@ -651,6 +652,12 @@ struct bzx_dstream {
     DevMem<uint32_t> d_fsec, d_fwin;
     PinMem<uint32_t> h_fwin;
     std::vector<uint8_t> find_carry;
+    // ... with bzx_index_find_lines: a BzxFindLines behind the BzxFindOut (find_off covers both), the sections' delimiter
+    // counts, a second emit window, and the delimiters of the passes digested so far
+    int lines_delim = -1;
+    uint64_t dbase = 0;
+    DevMem<uint32_t> d_dsec, d_lwin;
+    PinMem<uint32_t> h_lwin;
     // DS_SALVAGE (bzx_salvage_*): the index mode's memory, with the tables of the salvage kernels in place of d_meta / d_ix
     DsSvState sv = {};                 // the walk's state between passes and windows
     DevMem<DsSvCand> d_svc;
@@ -963,6 +970,15 @@ static void ds_launch_find(bzx_dstream *s, uint32_t q)
     const uint32_t grid = bzx_find_grid(DS_STAGE_BYTES, (uint32_t)ctx->n_cu);
     const uint64_t have = s->ix->hits.size();
     s->find_inline = (uint32_t)std::min<uint64_t>(FIND_INLINE_HITS, s->find_max > have ? s->find_max - have : 0);
+    if (s->lines_delim >= 0) {                               // the lines forms in place of the plain ones
+        BzxFindLines *fl = reinterpret_cast<BzxFindLines *>(fo + 1);
+        const uint32_t delim = (uint32_t)s->lines_delim;
+        bzx_launch_find_count_lines(stage, len, s->find_pat, delim, s->d_fsec.get(), s->d_dsec.get(), grid, st);
+        bzx_launch_find_scan_lines(stage, len, s->find_pat.m, s->d_fsec.get(), s->d_dsec.get(), nullptr, &fo->count, &fl->dcount, fo, st);
+        bzx_launch_find_emit_lines(stage, len, s->find_pat, delim, s->d_fsec.get(), s->d_dsec.get(), nullptr, &fo->count, 0,
+                                   s->find_inline, fo->hits, fl->lines, grid, st);
+        return;
+    }
     bzx_launch_find_count(stage, len, s->find_pat, s->d_fsec.get(), grid, st);
     bzx_launch_find_scan(stage, len, s->find_pat.m, s->d_fsec.get(), nullptr, &fo->count, fo, st);
     bzx_launch_find_emit(stage, len, s->find_pat, s->d_fsec.get(), nullptr, &fo->count, 0, s->find_inline, fo->hits, grid, st);
@@ -973,6 +989,8 @@ static void ds_launch_find(bzx_dstream *s, uint32_t q)
 // -- the inline ones, and while the list has room the rest in windows of FIND_WINDOW_HITS, one emit launch, one copy and
 // one synchronisation each (the staging bytes and the sections' sums stay until the next pass).  base: the decoded
 // bytes before the pass.
+// With lines on every hit comes with its line: a device hit's is dbase (the delimiters of the passes before this one)
+// plus what the emit kernel left; a straddling hit's is dbase minus the delimiters in the carry at or behind its start.
 static int ds_find_digest(bzx_dstream *s, uint32_t q, uint64_t base)
 {
     bzx_ctx *ctx = s->ctx;
@@ -983,28 +1001,43 @@ static int ds_find_digest(bzx_dstream *s, uint32_t q, uint64_t base)
     const uint8_t *pat = reinterpret_cast<const uint8_t *>(s->find_pat.w);
     std::vector<uint8_t> &c = s->find_carry;
     const size_t nc = c.size();
+    const bool lines = s->lines_delim >= 0;
+    const BzxFindLines *fl = lines ? reinterpret_cast<const BzxFindLines *>(&fo + 1) : nullptr;
     c.insert(c.end(), fo.head, fo.head + fo.nedge);
     for (size_t i = 0; i < nc && i + m <= c.size(); i++) {
         if (memcmp(c.data() + i, pat, m)) continue;
         ix->hit_total++;
-        if (ix->hits.size() < s->find_max) ix->hits.push_back(base - nc + i);
+        if (ix->hits.size() >= s->find_max) continue;
+        ix->hits.push_back(base - nc + i);
+        if (lines) ix->lines.push_back(s->dbase - (uint64_t)std::count(c.begin() + i, c.begin() + nc, (uint8_t)s->lines_delim));
     }
     if (fo.nedge == m - 1) c.assign(fo.tail, fo.tail + fo.nedge);       // (a shorter pass extends the carry)
     else if (c.size() > m - 1) c.erase(c.begin(), c.end() - (m - 1));
     ix->hit_total += fo.count;
     uint64_t skip = std::min<uint64_t>(fo.count, s->find_inline);
-    for (uint64_t i = 0; i < skip && ix->hits.size() < s->find_max; i++) ix->hits.push_back(base + fo.hits[i]);
+    for (uint64_t i = 0; i < skip && ix->hits.size() < s->find_max; i++) {
+        ix->hits.push_back(base + fo.hits[i]);
+        if (lines) ix->lines.push_back(s->dbase + fl->lines[i]);
+    }
     const uint32_t grid = bzx_find_grid(DS_STAGE_BYTES, (uint32_t)ctx->n_cu);
     while (skip < fo.count && ix->hits.size() < s->find_max) {
         const uint32_t cap = (uint32_t)std::min<uint64_t>(FIND_WINDOW_HITS, std::min<uint64_t>(fo.count - skip, s->find_max - ix->hits.size()));
-        bzx_launch_find_emit(s->d_stage[q].get(), &s->d_rec.get()->good_bytes, s->find_pat, s->d_fsec.get(), nullptr,
-                             &s->d_ix.get<BzxFindOut>()->count, skip, cap, s->d_fwin.get(), grid, st);
+        if (lines)
+            bzx_launch_find_emit_lines(s->d_stage[q].get(), &s->d_rec.get()->good_bytes, s->find_pat, (uint32_t)s->lines_delim,
+                                       s->d_fsec.get(), s->d_dsec.get(), nullptr, &s->d_ix.get<BzxFindOut>()->count, skip, cap,
+                                       s->d_fwin.get(), s->d_lwin.get(), grid, st);
+        else
+            bzx_launch_find_emit(s->d_stage[q].get(), &s->d_rec.get()->good_bytes, s->find_pat, s->d_fsec.get(), nullptr,
+                                 &s->d_ix.get<BzxFindOut>()->count, skip, cap, s->d_fwin.get(), grid, st);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(s->h_fwin, s->d_fwin, (size_t)cap * 4, hipMemcpyDeviceToHost, st));
+        if (lines) HIP_TRY(ctx, hipMemcpyAsync(s->h_lwin, s->d_lwin, (size_t)cap * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));              // a window's synchronisation
         for (uint32_t i = 0; i < cap; i++) ix->hits.push_back(base + s->h_fwin[i]);
+        for (uint32_t i = 0; lines && i < cap; i++) ix->lines.push_back(s->dbase + s->h_lwin[i]);
         skip += cap;
     }
+    if (lines) s->dbase += fl->dcount;
     return BZX_OK;
 }
 
@@ -1468,9 +1501,11 @@ extern "C" int bzx_index_find(bzx_index *ix, const uint8_t *pat, size_t m, uint6
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t R = s->R, before_dev = s->d_ix.bytes() + s->d_fsec.bytes() + s->d_fwin.bytes(),
                  before_pin = s->h_ix.bytes() + s->h_fwin.bytes();
-    const size_t tab = sizeof(BzxFindOut) + R * (sizeof(DsIxRec) + (s->rec_delim >= 0 ? 4 : 0));
+    const size_t off = sizeof(BzxFindOut) + (s->lines_delim >= 0 ? sizeof(BzxFindLines) : 0);   // (lines stay on)
+    const size_t tab = off + R * (sizeof(DsIxRec) + (s->rec_delim >= 0 ? 4 : 0));
     try {
         ix->hits.clear();
+        ix->lines.clear();
         s->find_carry.clear();
         s->find_carry.reserve(2 * BZX_FIND_MAX_PATTERN);
     } catch (const std::bad_alloc &) {
@@ -1485,7 +1520,8 @@ extern "C" int bzx_index_find(bzx_index *ix, const uint8_t *pat, size_t m, uint6
     s->info.device_bytes += s->d_ix.bytes() + s->d_fsec.bytes() + s->d_fwin.bytes() - before_dev;
     s->info.pinned_bytes += s->h_ix.bytes() + s->h_fwin.bytes() - before_pin;
     s->find_on = true;
-    s->find_off = sizeof(BzxFindOut);
+    s->find_off = off;
+    s->dbase = 0;
     s->find_pat = fp;
     s->find_max = max_hits;
     ix->hit_total = 0;
@@ -1503,6 +1539,65 @@ extern "C" int bzx_index_get_hits(const bzx_index *ix, const uint64_t **hits, ui
     *hits = ix->hits.data();
     *nlisted = ix->hits.size();
     *total = ix->hit_total;
+    return BZX_OK;
+}
+
+// Lines switched on: the pass launches the lines forms of the three kernels in place of the plain ones and its copy
+// grows by a BzxFindLines behind the BzxFindOut; what that takes is allocated here, so that a find without lines
+// allocates, launches and copies what it always did.
+static_assert(sizeof(BzxFindLines) % 8 == 0, "the index records behind it hold 64-bit values");
+extern "C" int bzx_index_find_lines(bzx_index *ix, int delim)
+{
+    if (!ix || !ix->s || !ix->s->ctx) return BZX_E_PARAM;
+    bzx_dstream *s = ix->s;
+    bzx_ctx *ctx = s->ctx;
+    std::unique_lock<std::recursive_mutex> api_lock_(ctx->api_mu);
+    if (s->mode != DS_INDEX) {
+        ctx->err = "bzx_index_find_lines: not on a salvage index (its entries come from the device walk)";
+        return BZX_E_STATE;
+    }
+    if (ix->fed) {
+        ctx->err = "bzx_index_find_lines: call it before the first bzx_index_feed";
+        return BZX_E_STATE;
+    }
+    if (!s->find_on) {
+        ctx->err = "bzx_index_find_lines: call it after bzx_index_find";
+        return BZX_E_STATE;
+    }
+    if (delim < 0 || delim > 255) {
+        ctx->err = "bzx_index_find_lines: the delimiter is one byte value, 0..255";
+        return BZX_E_PARAM;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t R = s->R, before_dev = s->d_ix.bytes() + s->d_dsec.bytes() + s->d_lwin.bytes(),
+                 before_pin = s->h_ix.bytes() + s->h_lwin.bytes();
+    const size_t off = sizeof(BzxFindOut) + sizeof(BzxFindLines);
+    const size_t tab = off + R * (sizeof(DsIxRec) + (s->rec_delim >= 0 ? 4 : 0));
+    ix->lines.clear();
+    if (!s->d_dsec.reserve(bzx_find_sections(DS_STAGE_BYTES) * 4) || !s->d_lwin.reserve((size_t)FIND_WINDOW_HITS * 4) ||
+        !s->h_lwin.reserve((size_t)FIND_WINDOW_HITS * 4) || !s->d_ix.reserve(tab) || !s->h_ix.reserve(tab) ||
+        hipMemset(s->d_ix, 0, tab) != hipSuccess) {
+        ctx->err = "bzx_index_find_lines: device or pinned allocation failed";
+        return BZX_E_NOMEM;
+    }
+    s->info.device_bytes += s->d_ix.bytes() + s->d_dsec.bytes() + s->d_lwin.bytes() - before_dev;
+    s->info.pinned_bytes += s->h_ix.bytes() + s->h_lwin.bytes() - before_pin;
+    s->find_off = off;
+    s->lines_delim = delim;
+    s->dbase = 0;
+    return BZX_OK;
+}
+
+extern "C" int bzx_index_get_hit_lines(const bzx_index *ix, const uint64_t **lines, uint64_t *nlisted)
+{
+    if (!ix || !ix->s || !ix->s->ctx || !lines || !nlisted) return BZX_E_PARAM;
+    std::unique_lock<std::recursive_mutex> api_lock_(ix->s->ctx->api_mu);
+    if (ix->s->lines_delim < 0) {
+        ix->s->ctx->err = "bzx_index_get_hit_lines: lines were not switched on (bzx_index_find_lines)";
+        return BZX_E_STATE;
+    }
+    *lines = ix->lines.data();
+    *nlisted = ix->lines.size();
     return BZX_OK;
 }
 

@@ -31,6 +31,19 @@
 //           the hits that straddle two passes in them)
 //   emit    every wave whose section's numbers meet [skip, skip + cap) walks it again; a wave scan per step gives every
 //           lane the number of its first hit, and hit k goes to out[k - skip].  The list is ascending by construction.
+//
+// The lines forms (bzx_index_find_lines, bzx_stage_find_lines): the same three kernels with the delimiters of the run
+// counted in the same walk, so that every hit comes with line(hit) = the delimiters of the run in front of its first
+// byte.  The test is find_match against bzx_rep4(delim) on the four words the lane holds anyway, under a validity mask
+// for 0 <= s < L (a zero that stands for a byte outside the run never counts, also for delim == 0).
+//   count   also leaves the delimiters of every section in dsec[]; these sections cover the WHOLE run, frame bytes
+//           [a, a + L): ceil((a + L) / FIND_SEC_BYTES) of them, one more than nsec where the last m - 1 bytes open a
+//           section of their own, and all there are when L < m
+//   scan    also turns dsec[] into its exclusive sum and leaves the run's delimiter total
+//   emit    a second wave scan per step, over the popcounts of the lanes' delimiter masks: hit k at bit j of a chunk
+//           writes lines_out[k - skip] = dsec[s] + the delimiters of the section's earlier steps + those of the lower
+//           lanes + popc(dmask & ((1 << j) - 1)), a 32-bit count relative to the run
+// The plain forms keep their kernels and their launches; find_mask16<false> is the code they always ran.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
@@ -90,15 +103,24 @@ __device__ __forceinline__ uint32_t find_word_bytes(const FindRun &R, int64_t s)
 }
 
 // The 16-bit mask of the hits that start in chunk c (frame bytes [16 c, 16 c + 16)); *lo = the position of its first byte.
-__device__ __forceinline__ uint32_t find_mask16(const FindRun &R, const uint8_t *s_pat8, uint32_t c, int64_t *lo_out)
+// LINES: also *dmask_out = the 16-bit mask of the chunk's bytes that lie in the run and equal the byte repeated in drep.
+template <bool LINES>
+__device__ __forceinline__ uint32_t find_mask16(const FindRun &R, const uint8_t *s_pat8, uint32_t c, int64_t *lo_out,
+                                                uint32_t drep = 0u, uint32_t *dmask_out = nullptr)
 {
     const int64_t lo = (int64_t)c * 16 - R.a;
     *lo_out = lo;
     const int64_t last = R.len - (int64_t)R.m - lo;          // the last valid start, relative to lo
-    if (last < 0 || lo + 16 <= 0) return 0u;
+    if constexpr (LINES) {                                   // (a chunk without a valid start can still hold delimiters)
+        *dmask_out = 0u;
+        if (lo >= R.len || lo + 16 <= 0) return 0u;
+    } else {
+        if (last < 0 || lo + 16 <= 0) return 0u;
+    }
     uint32_t valid = 0xFFFFu;
     if (lo < 0) valid &= 0xFFFFu << (uint32_t)(-lo);
-    if (last < 15) valid &= 0xFFFFu >> (uint32_t)(15 - last);
+    if (LINES && last < 0) valid = 0u;
+    else if (last < 15) valid &= 0xFFFFu >> (uint32_t)(15 - last);
     uint32_t w0, w1, w2, w3, w4;
     if (lo >= 0 && lo + 16 <= R.len) {
         const uint4 v = *reinterpret_cast<const uint4 *>(R.p + lo);
@@ -111,6 +133,14 @@ __device__ __forceinline__ uint32_t find_mask16(const FindRun &R, const uint8_t 
         w1 = find_word_bytes(R, lo + 4);
         w2 = find_word_bytes(R, lo + 8);
         w3 = find_word_bytes(R, lo + 12);
+    }
+    if constexpr (LINES) {
+        const int64_t dlast = R.len - 1 - lo;                // the run's last byte, relative to lo (>= 0 here)
+        uint32_t dvalid = 0xFFFFu;
+        if (lo < 0) dvalid &= 0xFFFFu << (uint32_t)(-lo);
+        if (dlast < 15) dvalid &= 0xFFFFu >> (uint32_t)(15 - dlast);
+        *dmask_out = (find_bits4(find_match(w0, drep)) | (find_bits4(find_match(w1, drep)) << 4) |
+                      (find_bits4(find_match(w2, drep)) << 8) | (find_bits4(find_match(w3, drep)) << 12)) & dvalid;
     }
     uint32_t hit = find_bits4(find_match(w0, R.rep)) | (find_bits4(find_match(w1, R.rep)) << 4) |
                    (find_bits4(find_match(w2, R.rep)) << 8) | (find_bits4(find_match(w3, R.rep)) << 12);
@@ -159,7 +189,7 @@ __global__ __launch_bounds__(FIND_NT) void bzx_find_count_kernel(const uint8_t *
         uint32_t acc = 0;
         for (uint32_t step = 0; step < FIND_STEPS; step++) {
             int64_t lo;
-            acc += (uint32_t)__popc(find_mask16(R, reinterpret_cast<const uint8_t *>(s_pat), (s * FIND_STEPS + step) * 64u + lane, &lo));
+            acc += (uint32_t)__popc(find_mask16<false>(R, reinterpret_cast<const uint8_t *>(s_pat), (s * FIND_STEPS + step) * 64u + lane, &lo));
         }
         const uint32_t incl = bzx_wave_incl_sum(acc);
         if (lane == 63) sec[s] = incl;
@@ -219,7 +249,7 @@ __global__ __launch_bounds__(FIND_NT) void bzx_find_emit_kernel(const uint8_t *_
         if (k == kend || kend <= skip || (k >= skip && k - skip >= cap)) continue;
         for (uint32_t step = 0; step < FIND_STEPS; step++) {
             int64_t lo;
-            uint32_t mask = find_mask16(R, reinterpret_cast<const uint8_t *>(s_pat), (s * FIND_STEPS + step) * 64u + lane, &lo);
+            uint32_t mask = find_mask16<false>(R, reinterpret_cast<const uint8_t *>(s_pat), (s * FIND_STEPS + step) * 64u + lane, &lo);
             const uint32_t mine = (uint32_t)__popc(mask);
             const uint32_t incl = bzx_wave_incl_sum(mine);
             const uint32_t tot = bzx_bcast63(incl);
@@ -227,6 +257,123 @@ __global__ __launch_bounds__(FIND_NT) void bzx_find_emit_kernel(const uint8_t *_
             for (; mask; mask &= mask - 1u, kk++)
                 if (kk >= skip && kk - skip < cap) out[kk - skip] = (uint32_t)(lo + ((uint32_t)__ffs(mask) - 1u));
             k += tot;
+        }
+    }
+}
+
+// ---- the lines forms ---------------------------------------------------------------------------------------------------------
+// Sections of the delimiter counts: the whole run, frame bytes [a, a + L).
+__device__ __forceinline__ uint32_t find_dsections(uint32_t a, uint64_t len)
+{
+    return (uint32_t)((a + len + FIND_SEC_BYTES - 1) / FIND_SEC_BYTES);
+}
+
+__global__ __launch_bounds__(FIND_NT) void bzx_find_count_lines_kernel(const uint8_t *__restrict__ p, const uint64_t *__restrict__ len,
+                                                                       BzxFindPat pat, uint32_t delim, uint32_t *__restrict__ sec,
+                                                                       uint32_t *__restrict__ dsec)
+{
+    __shared__ uint32_t s_pat[BZX_FIND_MAX_PATTERN / 4];
+    find_stage_pattern(pat, s_pat);
+    const FindRun R = find_run(p, *len, pat.m, s_pat);
+    const uint32_t ndsec = find_dsections(R.a, (uint64_t)R.len), drep = bzx_rep4(delim);
+    const uint32_t lane = bzx_lane(), wave = bzx_wave();
+    for (uint32_t t = blockIdx.x; t * 4u < ndsec; t += gridDim.x) {
+        const uint32_t s = t * 4u + wave;
+        if (s >= ndsec) continue;                            // (uniform over the wave)
+        uint32_t acc = 0, dacc = 0;
+        for (uint32_t step = 0; step < FIND_STEPS; step++) {
+            int64_t lo;
+            uint32_t dmask;
+            acc += (uint32_t)__popc(find_mask16<true>(R, reinterpret_cast<const uint8_t *>(s_pat), (s * FIND_STEPS + step) * 64u + lane,
+                                                      &lo, drep, &dmask));
+            dacc += (uint32_t)__popc(dmask);
+        }
+        const uint32_t incl = bzx_wave_incl_sum(acc), dincl = bzx_wave_incl_sum(dacc);
+        if (lane == 63) {
+            if (s < R.nsec) sec[s] = incl;
+            dsec[s] = dincl;
+        }
+    }
+}
+
+// One workgroup: the plain scan, then the same over dsec[]; *dafter = the run's delimiters.
+__global__ __launch_bounds__(FIND_NT) void bzx_find_scan_lines_kernel(const uint8_t *__restrict__ p, const uint64_t *__restrict__ len,
+                                                                      uint32_t m, uint32_t *__restrict__ sec, uint32_t *__restrict__ dsec,
+                                                                      const uint64_t *__restrict__ before, uint64_t *__restrict__ after,
+                                                                      uint64_t *__restrict__ dafter, BzxFindOut *__restrict__ edges)
+{
+    __shared__ uint32_t s_scr[FIND_NT / 64];
+    const uint64_t L = *len;
+    const uint32_t a = (uint32_t)((uintptr_t)p & 15u);
+    const uint32_t nsec = L >= m ? (uint32_t)((a + (L - m + 1) + FIND_SEC_BYTES - 1) / FIND_SEC_BYTES) : 0u;
+    const uint32_t ndsec = find_dsections(a, L);
+    uint64_t carry = 0, dcarry = 0;
+    for (uint32_t base = 0; base < ndsec; base += FIND_NT) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < nsec ? sec[i] : 0u, dv = i < ndsec ? dsec[i] : 0u;
+        uint32_t total, dtotal;
+        const uint32_t excl = bzx_block_excl_sum<FIND_NT>(v, s_scr, total);
+        const uint32_t dexcl = bzx_block_excl_sum<FIND_NT>(dv, s_scr, dtotal);
+        if (i < nsec) sec[i] = (uint32_t)carry + excl;      // (a run is shorter than 2^32 bytes, and so are its counts)
+        if (i < ndsec) dsec[i] = (uint32_t)dcarry + dexcl;
+        carry += total;
+        dcarry += dtotal;
+    }
+    if (threadIdx.x == 0) {
+        *after = (before ? *before : 0ull) + carry;
+        *dafter = dcarry;
+    }
+    if (edges) {
+        const uint32_t nb = (uint32_t)(L < m - 1u ? L : m - 1u);     // (at most 255: one lane each)
+        if (threadIdx.x < nb) {
+            edges->head[threadIdx.x] = p[threadIdx.x];
+            edges->tail[threadIdx.x] = p[L - nb + threadIdx.x];
+        }
+        if (threadIdx.x == 0) {
+            edges->nedge = nb;
+            edges->pad_ = 0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(FIND_NT) void bzx_find_emit_lines_kernel(const uint8_t *__restrict__ p, const uint64_t *__restrict__ len,
+                                                                      BzxFindPat pat, uint32_t delim, const uint32_t *__restrict__ sec,
+                                                                      const uint32_t *__restrict__ dsec,
+                                                                      const uint64_t *__restrict__ before,
+                                                                      const uint64_t *__restrict__ after, uint64_t skip, uint32_t cap,
+                                                                      uint32_t *__restrict__ out, uint32_t *__restrict__ lines_out)
+{
+    __shared__ uint32_t s_pat[BZX_FIND_MAX_PATTERN / 4];
+    find_stage_pattern(pat, s_pat);
+    const FindRun R = find_run(p, *len, pat.m, s_pat);
+    const uint32_t drep = bzx_rep4(delim);
+    const uint32_t lane = bzx_lane(), wave = bzx_wave();
+    const uint64_t k0 = before ? *before : 0ull, k1 = *after;
+    for (uint32_t t = blockIdx.x; t * 4u < R.nsec; t += gridDim.x) {
+        const uint32_t s = t * 4u + wave;
+        if (s >= R.nsec) continue;                           // (uniform over the wave, as is everything up to the walk)
+        uint64_t k = k0 + sec[s];
+        const uint64_t kend = s + 1u < R.nsec ? k0 + sec[s + 1u] : k1;
+        if (k == kend || kend <= skip || (k >= skip && k - skip >= cap)) continue;
+        uint32_t d = dsec[s];                                // the run's delimiters in front of the section, then of the step
+        for (uint32_t step = 0; step < FIND_STEPS; step++) {
+            int64_t lo;
+            uint32_t dmask;
+            uint32_t mask = find_mask16<true>(R, reinterpret_cast<const uint8_t *>(s_pat), (s * FIND_STEPS + step) * 64u + lane, &lo,
+                                              drep, &dmask);
+            const uint32_t mine = (uint32_t)__popc(mask), dmine = (uint32_t)__popc(dmask);
+            const uint32_t incl = bzx_wave_incl_sum(mine), dincl = bzx_wave_incl_sum(dmine);
+            const uint32_t tot = bzx_bcast63(incl), dtot = bzx_bcast63(dincl);
+            const uint32_t dd = d + (dincl - dmine);         // ... in front of the lane's chunk
+            uint64_t kk = k + (incl - mine);
+            for (; mask; mask &= mask - 1u, kk++)
+                if (kk >= skip && kk - skip < cap) {
+                    const uint32_t j = (uint32_t)__ffs(mask) - 1u;
+                    out[kk - skip] = (uint32_t)(lo + j);
+                    lines_out[kk - skip] = dd + (uint32_t)__popc(dmask & ((1u << j) - 1u));
+                }
+            k += tot;
+            d += dtot;
         }
     }
 }
@@ -259,6 +406,27 @@ void bzx_launch_find_emit(const uint8_t *p, const uint64_t *len, const BzxFindPa
     hipLaunchKernelGGL(bzx_find_emit_kernel, dim3(grid), dim3(FIND_NT), 0, stream, p, len, pat, sec, before, after, skip, cap, out);
 }
 
+void bzx_launch_find_count_lines(const uint8_t *p, const uint64_t *len, const BzxFindPat &pat, uint32_t delim, uint32_t *sec,
+                                 uint32_t *dsec, uint32_t grid, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bzx_find_count_lines_kernel, dim3(grid), dim3(FIND_NT), 0, stream, p, len, pat, delim, sec, dsec);
+}
+
+void bzx_launch_find_scan_lines(const uint8_t *p, const uint64_t *len, uint32_t m, uint32_t *sec, uint32_t *dsec,
+                                const uint64_t *before, uint64_t *after, uint64_t *dafter, BzxFindOut *edges, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bzx_find_scan_lines_kernel, dim3(1), dim3(FIND_NT), 0, stream, p, len, m, sec, dsec, before, after, dafter, edges);
+}
+
+void bzx_launch_find_emit_lines(const uint8_t *p, const uint64_t *len, const BzxFindPat &pat, uint32_t delim, const uint32_t *sec,
+                                const uint32_t *dsec, const uint64_t *before, const uint64_t *after, uint64_t skip, uint32_t cap,
+                                uint32_t *out, uint32_t *lines_out, uint32_t grid, hipStream_t stream)
+{
+    if (!cap) return;
+    hipLaunchKernelGGL(bzx_find_emit_lines_kernel, dim3(grid), dim3(FIND_NT), 0, stream, p, len, pat, delim, sec, dsec, before, after,
+                       skip, cap, out, lines_out);
+}
+
 extern "C" void bzx_find_geometry(uint32_t *tile_bytes, uint32_t *inline_hits, uint32_t *window_hits)
 {
     if (tile_bytes) *tile_bytes = FIND_TILE_BYTES;
@@ -268,15 +436,18 @@ extern "C" void bzx_find_geometry(uint32_t *tile_bytes, uint32_t *inline_hits, u
 
 // ---- the kernels alone, for the parity tests (host pointers) -----------------------------------------------------------------
 // Segment i is a run of its own; d_run[i] = the hits of the segments before it, so the numbering of the emit kernel runs
-// through all segments.  Everything is enqueued without a synchronisation in between.
+// through all segments.  Everything is enqueued without a synchronisation in between.  delim >= 0: the lines forms;
+// d_dtot[i] = the delimiters of segment i, and a hit's line counts those of its own segment only.
 static int stage_find(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nseg, const uint64_t *seg_offs,
                       const uint64_t *seg_lens, const BzxFindPat &pat, uint64_t skip, uint32_t cap, uint32_t *counts_out,
-                      uint64_t *hits_out, uint32_t *nwritten)
+                      uint64_t *hits_out, uint32_t *nwritten, int delim = -1, uint32_t *dcounts_out = nullptr,
+                      uint64_t *lines_out = nullptr)
 {
+    const bool lines = delim >= 0;
     uint64_t longest = 0;
     for (uint32_t i = 0; i < nseg; i++) {
         if (seg_offs[i] > len || seg_lens[i] > len - seg_offs[i] || seg_lens[i] > 0xFFFFFFFFull) {
-            ctx->err = "bzx_stage_find: segment " + std::to_string(i) + " leaves the buffer";
+            ctx->err = std::string(lines ? "bzx_stage_find_lines" : "bzx_stage_find") + ": segment " + std::to_string(i) + " leaves the buffer";
             return BZX_E_PARAM;
         }
         longest = std::max(longest, seg_lens[i]);
@@ -286,13 +457,18 @@ static int stage_find(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nse
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevMem<> d_buf, d_tab;                       // (freed on return: every path below ends behind a synchronisation)
-    uint64_t *d_len = nullptr, *d_run = nullptr;
-    uint32_t *d_sec = nullptr, *d_out = nullptr;
+    uint64_t *d_len = nullptr, *d_run = nullptr, *d_dtot = nullptr;
+    uint32_t *d_sec = nullptr, *d_out = nullptr, *d_dsec = nullptr, *d_lout = nullptr;
     const bool ok = d_buf.reserve(len + 512) && carved(d_tab, 256, [&](Carver &c) {
         d_len = c.take<uint64_t>(nseg);
         d_run = c.take<uint64_t>((size_t)nseg + 1);
         d_sec = c.take<uint32_t>(bzx_find_sections(longest));
         d_out = c.take<uint32_t>(std::max<uint32_t>(cap, 1));
+        if (lines) {
+            d_dtot = c.take<uint64_t>(nseg);
+            d_dsec = c.take<uint32_t>(bzx_find_sections(longest));
+            d_lout = c.take<uint32_t>(std::max<uint32_t>(cap, 1));
+        }
     });
     if (!ok) {
         ctx->err = "bzx_stage_find: device allocation failed";
@@ -301,13 +477,23 @@ static int stage_find(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nse
     uint8_t *d = (uint8_t *)rg_al((size_t)(uintptr_t)d_buf.get());
     auto run = [&]() -> int {
         std::vector<uint64_t> total((size_t)nseg + 1);
-        std::vector<uint32_t> got(cap);
+        std::vector<uint32_t> got(cap), lgot(lines ? cap : 0);
+        std::vector<uint64_t> dtot(lines ? nseg : 0);
         if (len) HIP_TRY(ctx, hipMemcpyAsync(d, buf, len, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(d_len, seg_lens, (size_t)nseg * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemsetAsync(d_run, 0, 8, st));
         if (cap) HIP_TRY(ctx, hipMemsetAsync(d_out, 0xEE, (size_t)cap * 4, st));
+        if (cap && lines) HIP_TRY(ctx, hipMemsetAsync(d_lout, 0xEE, (size_t)cap * 4, st));
         for (uint32_t i = 0; i < nseg; i++) {
             const uint32_t grid = bzx_find_grid(seg_lens[i], (uint32_t)ctx->n_cu);
+            if (lines) {
+                bzx_launch_find_count_lines(d + seg_offs[i], d_len + i, pat, (uint32_t)delim, d_sec, d_dsec, grid, st);
+                bzx_launch_find_scan_lines(d + seg_offs[i], d_len + i, pat.m, d_sec, d_dsec, d_run + i, d_run + i + 1, d_dtot + i,
+                                           nullptr, st);
+                bzx_launch_find_emit_lines(d + seg_offs[i], d_len + i, pat, (uint32_t)delim, d_sec, d_dsec, d_run + i, d_run + i + 1,
+                                           skip, cap, d_out, d_lout, grid, st);
+                continue;
+            }
             bzx_launch_find_count(d + seg_offs[i], d_len + i, pat, d_sec, grid, st);
             bzx_launch_find_scan(d + seg_offs[i], d_len + i, pat.m, d_sec, d_run + i, d_run + i + 1, nullptr, st);
             bzx_launch_find_emit(d + seg_offs[i], d_len + i, pat, d_sec, d_run + i, d_run + i + 1, skip, cap, d_out, grid, st);
@@ -315,11 +501,15 @@ static int stage_find(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nse
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(total.data(), d_run, ((size_t)nseg + 1) * 8, hipMemcpyDeviceToHost, st));
         if (cap) HIP_TRY(ctx, hipMemcpyAsync(got.data(), d_out, (size_t)cap * 4, hipMemcpyDeviceToHost, st));
+        if (lines) HIP_TRY(ctx, hipMemcpyAsync(dtot.data(), d_dtot, (size_t)nseg * 8, hipMemcpyDeviceToHost, st));
+        if (cap && lines) HIP_TRY(ctx, hipMemcpyAsync(lgot.data(), d_lout, (size_t)cap * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         for (uint32_t i = 0; i < nseg; i++) counts_out[i] = (uint32_t)(total[i + 1] - total[i]);
+        for (uint32_t i = 0; lines && i < nseg; i++) dcounts_out[i] = (uint32_t)dtot[i];
         const uint64_t all = total[nseg];
         const uint32_t n = (uint32_t)(all > skip ? std::min<uint64_t>(all - skip, cap) : 0);
         for (uint32_t i = 0; i < n; i++) hits_out[i] = got[i];
+        for (uint32_t i = 0; lines && i < n; i++) lines_out[i] = lgot[i];
         *nwritten = n;
         return BZX_OK;
     };
@@ -355,4 +545,19 @@ extern "C" int bzx_stage_find(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint
         !bzx_find_pattern(pat, m, &fp))
         return BZX_E_PARAM;
     return stage_find(ctx, buf, len, nseg, seg_offs, seg_lens, fp, skip, cap, counts_out, hits_out, nwritten);
+}
+
+extern "C" int bzx_stage_find_lines(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nseg, const uint64_t *seg_offs,
+                                    const uint64_t *seg_lens, const uint8_t *pat, size_t m, int delim, uint64_t skip, uint32_t cap,
+                                    uint32_t *counts_out, uint32_t *dcounts_out, uint64_t *hits_out, uint64_t *lines_out,
+                                    uint32_t *nwritten)
+{
+    auto api_lock_ = ctx_lock(ctx);
+    BZX_REFUSE_WHILE_STREAMING(ctx);
+    BzxFindPat fp;
+    if (!ctx || !nwritten || (len && !buf) || (nseg && (!seg_offs || !seg_lens || !counts_out || !dcounts_out)) ||
+        (cap && (!hits_out || !lines_out)) || delim < 0 || delim > 255 || !bzx_find_pattern(pat, m, &fp))
+        return BZX_E_PARAM;
+    return stage_find(ctx, buf, len, nseg, seg_offs, seg_lens, fp, skip, cap, counts_out, hits_out, nwritten, delim, dcounts_out,
+                      lines_out);
 }

@@ -323,6 +323,10 @@ struct BzxFindOut {                          // what a pass leaves for the host 
     uint8_t head[BZX_FIND_MAX_PATTERN], tail[BZX_FIND_MAX_PATTERN];      // its first and last nedge verified bytes
     uint32_t hits[FIND_INLINE_HITS];         // its first hits, relative to the staging area
 };
+struct BzxFindLines {                        // (bzx_index_find_lines) ... and behind BzxFindOut, in front of the records
+    uint64_t dcount;                         // delimiters among the verified bytes of the pass
+    uint32_t lines[FIND_INLINE_HITS];        // delimiters of the pass in front of hits[i]
+};
 static inline size_t bzx_find_sections(uint64_t len) { return (size_t)((len + 15 + FIND_SEC_BYTES - 1) / FIND_SEC_BYTES) + 1; }
 uint32_t bzx_find_grid(uint64_t len, uint32_t n_cu);
 bool bzx_find_pattern(const uint8_t *pat, size_t m, BzxFindPat *out);
@@ -333,3 +337,12 @@ void bzx_launch_find_scan(const uint8_t *p, const uint64_t *len, uint32_t m, uin
 void bzx_launch_find_emit(const uint8_t *p, const uint64_t *len, const BzxFindPat &pat, const uint32_t *sec,
                           const uint64_t *before, const uint64_t *after, uint64_t skip, uint32_t cap, uint32_t *out,
                           uint32_t grid, hipStream_t stream);
+// The lines forms: dsec[] (bzx_find_sections() words, as sec[]) holds the delimiters per section of the whole run, then
+// their exclusive sum; *dafter = the run's delimiters; lines_out[k - skip] = the run's delimiters in front of hit k.
+void bzx_launch_find_count_lines(const uint8_t *p, const uint64_t *len, const BzxFindPat &pat, uint32_t delim, uint32_t *sec,
+                                 uint32_t *dsec, uint32_t grid, hipStream_t stream);
+void bzx_launch_find_scan_lines(const uint8_t *p, const uint64_t *len, uint32_t m, uint32_t *sec, uint32_t *dsec,
+                                const uint64_t *before, uint64_t *after, uint64_t *dafter, BzxFindOut *edges, hipStream_t stream);
+void bzx_launch_find_emit_lines(const uint8_t *p, const uint64_t *len, const BzxFindPat &pat, uint32_t delim, const uint32_t *sec,
+                                const uint32_t *dsec, const uint64_t *before, const uint64_t *after, uint64_t skip, uint32_t cap,
+                                uint32_t *out, uint32_t *lines_out, uint32_t grid, hipStream_t stream);

@@ -767,6 +767,58 @@ int bzx_stage_find(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nseg, 
                    const uint64_t *seg_lens, const uint8_t *pat, size_t m, uint64_t skip, uint32_t cap, uint32_t *counts_out,
                    uint64_t *hits_out, uint32_t *nwritten);
 /*
+ * Grep: "print the lines of this .bz2 that contain the string" -- the hits of find, the line number of every hit, counted
+ * on the device in the pass that finds it, and the record reader for the lines themselves.
+ * The rule.  D, N, delim as for the records above.  line(p) = the number of q < p with D[q] == delim: the record that
+ * holds byte p, rec_start(line(p)) <= p < rec_start(line(p) + 1); a byte that is itself a delimiter belongs to the record
+ * it ends.  For the list hits[0, nlisted) of bzx_index_get_hits, lines[i] = line(hits[i]): non-descending, and the borders
+ * of blocks, streams, passes, rounds and windows do not exist for it.  A pattern may contain delim; the line is that of
+ * the hit's first byte.  After BZX_E_DATA the list describes the hits of the verified prefix, as hits does.
+ *
+ * bzx_index_find_lines(ix, delim): after bzx_index_find and before the first bzx_index_feed, in any order with
+ * bzx_index_count_records (whose delimiter is its own: the two are independent).  BZX_E_STATE without find, after a feed
+ * and on an object from bzx_salvage_begin; BZX_E_PARAM for a delim outside 0..255.  Off is the default and off means off:
+ * a find without lines launches, copies, allocates and synchronises as it did.  On, the pass launches the lines forms of
+ * the three find kernels IN PLACE of the plain ones -- still three launches: they count the delimiters in the walk over
+ * the bytes they read anyway -- and the one copy grows by a record of 4,104 bytes (the pass's delimiter total and the
+ * line words of its inline_hits hits); a pass with at most inline_hits hits still gains no synchronisation; every
+ * further window is still one emit launch and one synchronisation, now with two copies (hits, lines).  This call
+ * allocates the sections' delimiter counts and the second window on the device and in page-locked memory.  The host
+ * keeps the 64-bit delimiter total of the passes so far; a device hit's line is that plus the 32-bit count the emit kernel
+ * left, a hit that straddles two passes gets its line on the host, from the carried bytes.
+ * bzx_index_get_hit_lines: the lines of the hits bzx_index_get_hits returns now, the same *nlisted; valid as long as that
+ * call's pointer; BZX_E_STATE when lines were not switched on.
+ *
+ * bzx_grep_buffer: ONE index pass over bz2 with find (max_hits), lines and bzx_index_count_records(delim) switched on;
+ * the distinct values of lines[], ascending, are recs[0, *nrecs); then ONE call of bzx_decompress_records_buffer over the
+ * index and record table of that same pass, one range {recs[i], 1} each, the whole input as one piece: record recs[i] --
+ * D[rec_start(recs[i]), rec_start(recs[i] + 1)), its terminating delimiter included, the unterminated last record without
+ * one -- lies at out[out_offs[i], + lens[i]), packed.  A record with several hits is listed once.
+ *   Refusals: BZX_E_PARAM for a pattern that contains delim (no record can hold it), a delim outside 0..255 and what
+ *   bzx_find_buffer refuses.  BZX_E_OUTBUF with *nrecs = the records needed when cap_recs is too small (recs, out_offs and
+ *   lens have room for cap_recs values), BZX_E_OUTBUF with *need = the bytes needed when cap is too small; after either
+ *   nothing has been written to out.
+ *   Truncation: *total_hits is exact; *truncated = 1 when it exceeds max_hits, and then the records are those of the
+ *   listed hits only.  The exact number of matching records beyond the list is deliberately not built.
+ *   Damage: the matching records of the verified prefix are delivered, the last one cut at the prefix's end, and the call
+ *   returns BZX_E_DATA with the pass's text.
+ *   Cost: every block that holds a matching record is decoded twice, by the pass and by the record read, and the record
+ *   read uploads those blocks again -- the trade of bzx_salvage_buffer and bzx_decompress_records_*.  Delivering the
+ *   lines from the pass itself is not built.
+ * bzx_stage_find_lines: bzx_stage_find over the lines forms.  dcounts_out[i] = the bytes of segment i equal to delim;
+ * lines_out[k] = the delimiters of the hit's OWN segment in front of the hit (a neighbouring segment's bytes never
+ * count), written for the same numbers as hits_out.
+ */
+int bzx_index_find_lines(bzx_index *ix, int delim);
+int bzx_index_get_hit_lines(const bzx_index *ix, const uint64_t **lines, uint64_t *nlisted);
+int bzx_grep_buffer(bzx_ctx *ctx, const uint8_t *bz2, size_t len, const uint8_t *pat, size_t m, int delim, uint64_t max_hits,
+                    uint64_t *recs, uint64_t cap_recs, uint64_t *nrecs, uint8_t *out, size_t cap, size_t *out_offs, size_t *lens,
+                    size_t *need, uint64_t *total_hits, int *truncated);
+int bzx_stage_find_lines(bzx_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nseg, const uint64_t *seg_offs,
+                         const uint64_t *seg_lens, const uint8_t *pat, size_t m, int delim, uint64_t skip, uint32_t cap,
+                         uint32_t *counts_out, uint32_t *dcounts_out, uint64_t *hits_out, uint64_t *lines_out,
+                         uint32_t *nwritten);
+/*
  * The inverse BWT alone, for the parity tests (host pointers): L[0, n) and orig_ptr < n -> the RLE1 image img_out[0, n)
  * and its expansion raw_out (at most raw_cap bytes are written; *raw_len is the whole expanded length).  wide = 0 runs
  * the one-lane walk of the one-shot, batch and stream decoders, wide = 1 the many-lane walk of the range reads; both

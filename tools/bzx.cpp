@@ -34,6 +34,12 @@
 // device); --count prints the total only; --max-hits N (default 1000000) bounds the list, and one line on standard error
 // says how many more hits there were.  With --index, and with --index --lines, the same pass writes .bzxi and .bzxr.  Exit
 // status as grep's: 0 a hit, 1 none, 2 an error or a damaged file (whose verified prefix is still searched and printed).
+// --grep STRING / --grep-hex HEX FILE.bz2 ... prints the lines (delimiter '\n') of what every FILE decodes to that contain the
+// byte string, FILE: in front with several files, N: in front with --line-number (N numbered from 0, the numbering of
+// --lines FIRST:COUNT): one index pass with bzx_index_find, bzx_index_find_lines and the line table, then one
+// bzx_decompress_records_buffer over the pieces of the file that hold a matching line.  --count prints the number of
+// matching lines among the listed hits; --max-hits as for --find; with --index --lines the same pass writes .bzxi and
+// .bzxr.  Exit status as grep's: 0 a line matched, 1 none, 2 an error or a damaged file.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -66,6 +72,7 @@ struct Opts {
     bool find = false, count = false;  // --find STRING or --find-hex HEX; --count
     std::string find_pat;
     uint64_t max_hits = 1000000;       // --max-hits N
+    bool grep = false, line_number = false;        // --grep STRING or --grep-hex HEX (the pattern is find_pat); --line-number
 };
 
 static void help()
@@ -87,6 +94,11 @@ static void help()
          "  --find-hex HEX    the same for the bytes HEX names (1 to 256 of them), e.g. 0d0a00ff\n"
          "                    --count: the total only; --max-hits N: list at most N (default 1000000); with --index (and\n"
          "                    --lines) the same pass writes the index; exit status 0: a hit, 1: none, 2: error or damage\n"
+         "  --grep STRING     print the lines of what every FILE (a .bz2) decodes to that contain STRING (--grep-hex HEX: bytes)\n"
+         "                    --line-number: N: in front, N numbered from 0 as for --lines FIRST:COUNT, so -dc --lines N:1 reads\n"
+         "                    that line; --count: the number of matching lines among the listed hits; --max-hits N as for\n"
+         "                    --find; with --index --lines the same pass writes both tables; exit status 0: a line matched,\n"
+         "                    1: none, 2: error or damage\n"
          "  --recover         write every intact block of a damaged FILE.bz2 to FILE.recovered (-c: standard output) and\n"
          "                    one line per gap to standard error; with --index also FILE.bz2.bzxi for --range;\n"
          "                    exit status 0: nothing lost, 2: data lost, 1: trouble\n"
@@ -317,6 +329,7 @@ struct FindReq {
     const std::string *pat;
     uint64_t max_hits;
     bool damaged = false;
+    int lines_delim = -1;              // (--grep) also bzx_index_find_lines
 };
 static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool salvage, bzx_index **out, int delim = -1,
                       FindReq *find = nullptr)
@@ -334,6 +347,7 @@ static int feed_index(const Opts &o, bzx_ctx *ctx, const std::string &f, bool sa
     if (!rc && delim >= 0 && (rc = bzx_index_count_records(ix, delim))) bzx_index_end(ix);
     if (!rc && find && (rc = bzx_index_find(ix, (const uint8_t *)find->pat->data(), find->pat->size(), find->max_hits)))
         bzx_index_end(ix);
+    if (!rc && find && find->lines_delim >= 0 && (rc = bzx_index_find_lines(ix, find->lines_delim))) bzx_index_end(ix);
     if (rc) {
         fclose(in);
         return fail(o, "cannot start", name, ctx, rc);
@@ -863,6 +877,99 @@ static int do_lines(const Opts &o, bzx_ctx *ctx, const std::string &f)
     return ret;
 }
 
+// --grep: the matching lines of FILE.bz2 to standard output.  One pass gives the hits' line numbers, the index and the
+// line table; the lines then come through bzx_decompress_records_buffer from the pieces of the file that
+// bzx_records_pieces names (blocks with a matching line are decoded a second time).  With --index --lines also what
+// do_index writes, from the same pass (not for a damaged file).  -> 0: a line matched, 1: none, 2: an error or damage.
+static int do_grep(const Opts &o, bzx_ctx *ctx, const std::string &f)
+{
+    const char *name = f.c_str();
+    const bool multi = o.files.size() > 1;
+    bzx_index *ix = nullptr;
+    FindReq req{&o.find_pat, o.max_hits};
+    req.lines_delim = LINE_DELIM;
+    if (feed_index(o, ctx, f, false, &ix, LINE_DELIM, &req)) return 2;
+    const bool damaged = req.damaged;
+    int rc, ret = 0;
+    uint64_t nmatch = 0;
+    try {
+        const uint64_t *hits = nullptr, *lines = nullptr, *rbp = nullptr;
+        uint64_t nlisted = 0, total = 0, nl = 0, nblk = 0;
+        const bzx_index_entry *ep = nullptr;
+        bzx_index_info info;
+        std::vector<bzx_index_entry> e;
+        std::vector<uint64_t> rb, recs;
+        if ((rc = bzx_index_get_hits(ix, &hits, &nlisted, &total)) || (rc = bzx_index_get_hit_lines(ix, &lines, &nl)) ||
+            (rc = bzx_index_get(ix, &ep, &info)) || (rc = bzx_index_get_records(ix, &rbp, &nblk)))
+            ret = fail(o, "grep failed", name, ctx, rc);
+        if (!ret) {
+            e.assign(ep, ep + nblk);
+            rb.assign(rbp, rbp + nblk + 1);
+            recs.assign(lines, lines + nl);                  // (non-descending)
+            recs.erase(std::unique(recs.begin(), recs.end()), recs.end());
+            nmatch = recs.size();
+            if (o.index && !damaged) {
+                ret = write_bzxi(o, f + ".bzxi", ep, info);
+                if (!ret && o.lines) ret = write_bzxr(o, f + ".bzxr", rbp, nblk);
+            }
+        }
+        bzx_index_end(ix);                                   // (the record read wants the context to itself)
+        ix = nullptr;
+        if (!ret && total > nlisted && !o.quiet)
+            fprintf(stderr, "bzx: %s: %llu more hits not listed (--max-hits %llu): their lines are missing\n", name,
+                    (unsigned long long)(total - nlisted), (unsigned long long)o.max_hits);
+        if (!ret && o.count) {
+            if (multi) printf("%s:", name);
+            printf("%llu\n", (unsigned long long)nmatch);
+        } else if (!ret && nmatch > 0x7FFFFFFFull) {
+            if (!o.quiet) fprintf(stderr, "bzx: %s: more than 2^31 - 1 matching lines: lower --max-hits\n", name);
+            ret = 1;
+        } else if (!ret && nmatch) {
+            const uint32_t count = (uint32_t)nmatch;
+            const std::vector<uint64_t> ones(count, 1);
+            std::vector<size_t> offs(count), gots(count);
+            std::vector<int> status(count);
+            uint32_t np = 0;
+            bzx_records_pieces(e.data(), nblk, rb.data(), count, recs.data(), ones.data(), nullptr, nullptr, 0, &np);
+            std::vector<uint64_t> bases(np), lens(np);
+            std::vector<std::vector<uint8_t>> held(np);
+            std::vector<bzx_piece> pieces(np);
+            if (np && (rc = bzx_records_pieces(e.data(), nblk, rb.data(), count, recs.data(), ones.data(), bases.data(), lens.data(), np, &np)))
+                ret = fail(o, "grep failed", name, nullptr, rc);
+            FILE *in = ret ? nullptr : fopen(name, "rb");
+            if (!ret && !in) ret = fail(o, strerror(errno), name, nullptr, BZX_OK);
+            for (uint32_t j = 0; !ret && j < np; j++) {      // (a piece may end up to 8 bytes behind the file)
+                held[j].resize((size_t)lens[j]);
+                if (fseeko(in, (off_t)bases[j], SEEK_SET) != 0) ret = fail(o, strerror(errno), name, nullptr, BZX_OK);
+                else if (fread(held[j].data(), 1, held[j].size(), in) != held[j].size() && ferror(in))
+                    ret = fail(o, strerror(errno), name, nullptr, BZX_OK);
+                pieces[j] = bzx_piece{held[j].data(), bases[j], lens[j]};
+            }
+            if (in) fclose(in);
+            std::vector<uint8_t> out;
+            size_t need = 0;
+            for (int turn = 0; !ret && turn < 2; turn++) {   // room is known behind the locate step: at most one repeat
+                out.resize(turn ? need : (size_t)std::min<uint64_t>(std::max<uint64_t>(info.out_bytes, 1), (uint64_t)64 << 20));
+                rc = bzx_decompress_records_buffer(ctx, pieces.data(), np, e.data(), nblk, rb.data(), LINE_DELIM, count, recs.data(),
+                                                   ones.data(), out.data(), out.size(), offs.data(), gots.data(), status.data(), &need);
+                if (rc != BZX_E_OUTBUF || turn) break;
+            }
+            if (!ret && rc) ret = fail(o, "line read failed", name, ctx, rc);
+            for (uint32_t i = 0; !ret && i < count; i++) {
+                if (multi) printf("%s:", name);
+                if (o.line_number) printf("%llu:", (unsigned long long)recs[i]);
+                fwrite(out.data() + offs[i], 1, gots[i], stdout);
+                if (!gots[i] || out[offs[i] + gots[i] - 1] != (uint8_t)LINE_DELIM) putchar(LINE_DELIM);     // (the unterminated last line)
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        ret = fail(o, "out of memory", name, nullptr, BZX_E_NOMEM);
+    }
+    if (ix) bzx_index_end(ix);
+    if (!ret && (fflush(stdout) != 0 || ferror(stdout))) ret = fail(o, strerror(errno), "standard output", nullptr, BZX_OK);
+    return ret || damaged ? 2 : nmatch ? 0 : 1;
+}
+
 // The end of one file's work: output flushed and closed (or removed after a failure), input removed unless -k.
 static int finish_file(const Opts &o, FILE *out, const std::string &oname, const std::string &f, int r)
 {
@@ -1016,7 +1123,9 @@ int main(int argc, char **argv)
     Opts o;
     int bad = 1;                                             // a usage error; 2, as grep's, when the command line asks for a find
     for (int i = 1; i < argc; i++)
-        if (!strncmp(argv[i], "--find", 6) || !strcmp(argv[i], "--count") || !strncmp(argv[i], "--max-hits", 10)) bad = 2;
+        if (!strncmp(argv[i], "--find", 6) || !strcmp(argv[i], "--count") || !strncmp(argv[i], "--max-hits", 10) ||
+            !strncmp(argv[i], "--grep", 6) || !strcmp(argv[i], "--line-number"))
+            bad = 2;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         if (a == "-" || a[0] != '-') {
@@ -1066,6 +1175,7 @@ int main(int argc, char **argv)
             }
             else if (a == "--find" || a.rfind("--find=", 0) == 0) {
                 if (a == "--find" && i + 1 >= argc) { fprintf(stderr, "bzx: --find takes a string\n"); return bad; }
+                if (o.grep) { fprintf(stderr, "bzx: --grep does not go with --find\n"); return 2; }
                 o.find = true;
                 o.find_pat = a == "--find" ? argv[++i] : a.substr(7);
             }
@@ -1079,6 +1189,24 @@ int main(int argc, char **argv)
                 o.find_pat.clear();
                 for (size_t k = 0; k < v.size(); k += 2) o.find_pat.push_back((char)strtoul(v.substr(k, 2).c_str(), nullptr, 16));
             }
+            else if (a == "--grep" || a.rfind("--grep=", 0) == 0) {
+                if (a == "--grep" && i + 1 >= argc) { fprintf(stderr, "bzx: --grep takes a string\n"); return bad; }
+                if (o.find) { fprintf(stderr, "bzx: --grep does not go with --find\n"); return 2; }
+                o.grep = true;
+                o.find_pat = a == "--grep" ? argv[++i] : a.substr(7);
+            }
+            else if (a == "--grep-hex" || a.rfind("--grep-hex=", 0) == 0) {
+                const std::string v = a == "--grep-hex" ? (i + 1 < argc ? argv[++i] : "") : a.substr(11);
+                if (v.empty() || v.size() % 2 || v.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos) {
+                    fprintf(stderr, "bzx: --grep-hex takes an even number of hex digits, e.g. 0d0a00ff (got \"%s\")\n", v.c_str());
+                    return 2;
+                }
+                if (o.find) { fprintf(stderr, "bzx: --grep does not go with --find\n"); return 2; }
+                o.grep = true;
+                o.find_pat.clear();
+                for (size_t k = 0; k < v.size(); k += 2) o.find_pat.push_back((char)strtoul(v.substr(k, 2).c_str(), nullptr, 16));
+            }
+            else if (a == "--line-number") o.line_number = true;
             else if (a == "--count") o.count = true;
             else if (a == "--max-hits" || a.rfind("--max-hits=", 0) == 0) {
                 const std::string v = a == "--max-hits" ? (i + 1 < argc ? argv[++i] : "") : a.substr(11);
@@ -1130,8 +1258,39 @@ int main(int argc, char **argv)
             }
         }
     }
+    if (o.grep || o.line_number) {                           // (exit status 2 for every error, as grep's)
+        const char *why = !o.grep ? "--line-number goes with --grep or --grep-hex"
+                          : o.find ? "--grep does not go with --find"
+                          : o.find_pat.empty() || o.find_pat.size() > BZX_FIND_MAX_PATTERN ? "--grep takes 1 to 256 bytes"
+                          : o.find_pat.find((char)LINE_DELIM) != std::string::npos ? "--grep takes a pattern without a newline (no line holds one)"
+                          : o.with_index || o.recover || o.range || !o.ranges.empty() || o.lines_range || o.mode_set || o.to_stdout
+                              ? "--grep goes with --line-number, --count, --max-hits, --index, --index --lines, -q and -v only (not with "
+                                "--find, --range, --ranges, --recover or --with-index)"
+                          : o.lines && !o.index ? "--lines goes with --index"
+                          : o.files.empty()     ? "--grep takes files"
+                                                : nullptr;
+        for (const std::string &f : o.files)
+            if (!why && f == "-") why = "--grep needs a file that can be read again, not standard input";
+        if (why) {
+            fprintf(stderr, "bzx: %s\n", why);
+            return 2;
+        }
+        bzx_ctx *ctx = nullptr;
+        const int rc = bzx_ctx_create(0, UNZIP_SLABS, &ctx);
+        if (rc) {
+            fprintf(stderr, "bzx: %s (the product has no CPU path)\n", bzx_strerror(rc));
+            return 2;
+        }
+        int worst = 1;
+        for (const std::string &f : o.files) {
+            const int r = do_grep(o, ctx, f);
+            worst = r == 2 || worst == 2 ? 2 : r == 0 ? 0 : worst;
+        }
+        bzx_ctx_destroy(ctx);
+        return worst;
+    }
     if (o.find || o.count) {                                 // (exit status 2 for every error, as grep's)
-        const char *why = !o.find ? "--count goes with --find or --find-hex"
+        const char *why = !o.find ? "--count goes with --find, --find-hex, --grep or --grep-hex"
                           : o.find_pat.empty() || o.find_pat.size() > BZX_FIND_MAX_PATTERN ? "--find takes 1 to 256 bytes"
                           : o.with_index || o.recover || o.range || !o.ranges.empty() || o.lines_range || o.mode_set || o.to_stdout
                               ? "--find goes with --index, --index --lines, --count, --max-hits, -q and -v only"
