@@ -5,8 +5,8 @@
 //
 // Design (MI355X: 160 KB LDS per CU, 256 CUs): an MSD partition followed by sorts that never leave LDS.
 //   split kernel  (one workgroup per block): bytes in use -> dense ids -> packed block P (bzx_pack.h); histogram of
-//                 the first 15 bits of every rotation in LDS; adjacent bins are merged into BUCKETS of at most BS_C
-//                 rotations (bins above BS_C/3 stay alone); one pass writes a 64-bit record per rotation
+//                 the first 15 bits of every rotation in LDS; adjacent bins are packed greedily into BUCKETS of at most
+//                 BS_C rotations (form_buckets); one pass writes a 64-bit record per rotation
 //                 [next 32 key bits | rotation:20 | preceding byte:8] into its bucket's range of ranks.  A bin that
 //                 alone exceeds BS_C is split again by its next 12 bits (records re-keyed from P), and so on.
 //   sort kernel   (work items = buckets, any workgroup takes any bucket of any block): the bucket's records are
@@ -118,12 +118,13 @@ __shared__ uint8_t b_seq[256];
 __shared__ uint32_t b_scratch[2 * BS_NW];
 __shared__ uint32_t b_lbase[8];              // first item of this block's buckets in each of the eight work lists
 __shared__ uint32_t b_bcast[12];             // [0] block, [2] item base, [3] oversized bins pushed so far, [4] ring overflow,
-                                             // [8..10] rotations in bins a smaller isolation limit would leave alone
+                                             // [8..10] rotations in bins a smaller isolation limit would leave alone (window rule)
 __shared__ uint32_t b_big[BS_MAX_BIG][3];    // oversized bins: {start | buffer << 31, cnt, depth bits}
 
 #define TAB(b) b_tab[(b) + ((b) >> 5)]
 
-// Bins [0, BINS) counted in TAB -> buckets.  With an isolation limit ISO, a new bucket starts at bin b when b or b-1 is
+// Bins [0, BINS) counted in TAB -> buckets.  The window rule (the regrouping pass; until the greedy packing below also
+// the split): with an isolation limit ISO, a new bucket starts at bin b when b or b-1 is
 // above ISO, or when the bin's first rank lies in another (BS_C - ISO)-window than its predecessor's: a merged bucket is
 // at most one window plus one bin <= BS_C.  The smaller ISO, the wider the window and the fuller the buckets, but bins
 // between ISO and BS_ISO then make small buckets of their own: the smallest of BS_C/8, /6, /4 that leaves fewer than
@@ -145,40 +146,135 @@ __device__ __forceinline__ void bucket_flags(const uint32_t (&c)[PER], uint32_t 
     }
 }
 
-template <int BINS, bool TAB16 = false>
+// The sort kernel's buckets (level 1 and the deeper splits) are packed greedily instead: every bucket costs the sort
+// kernel the same barriers, scans and set-up whatever it holds, so the fuller the better.  Bins are taken in order, a
+// bucket takes bins while its sum stays <= BS_C (at least one: a bin above BS_C is alone), and to keep the serial
+// walk short the rank axis is cut into nseg = clamp(total / (16 BS_C), 1, BS_NW) segments walked by one wave each:
+// segment k starts at the first bin whose first rank is >= ceil(k total / nseg) (segments that start at the same bin
+// are one), and a segment's last bucket ends where the next segment starts.  coarse[l]: ranks up to the end of lane
+// l's PER bins; a step of the walk finds the first bin whose inclusive prefix reaches a target -- 64 coarse words at
+// a time (stretches of empty bins make that repeat), then the PER counts of the chunk found.
+struct BzxBinHit {
+    uint32_t bin, incl, cnt;                // the bin, the ranks up to its end, its own count
+};
+
+// First bin at or after chunk l0's first whose inclusive prefix is >= target; bin = BS_NT * PER when there is none.
+// Called by whole waves, every argument wave-uniform.
+template <int PER>
+__device__ __forceinline__ BzxBinHit greedy_find(const uint32_t *coarse, uint32_t l0, uint32_t target)
+{
+    static_assert(PER >= 1 && PER <= 32, "one lane per bin of a chunk, one 32-bit flag word per chunk");
+    const uint32_t lane = bzx_lane();
+    for (; l0 < BS_NT; l0 += 64) {
+        const uint32_t l = l0 + lane;
+        const uint64_t m = __ballot(l < BS_NT && coarse[l] >= target);
+        if (m == 0) continue;
+        const uint32_t ch = l0 + (uint32_t)__ffsll((unsigned long long)m) - 1u;
+        const uint32_t before = ch ? coarse[ch - 1u] : 0u;
+        const uint32_t cv = lane < (uint32_t)PER ? TAB(ch * PER + lane) : 0u;
+        const uint32_t in = before + bzx_wave_incl_sum(cv);
+        const uint64_t h = __ballot(lane < (uint32_t)PER && in >= target);      // (not empty: coarse[ch] >= target)
+        const uint32_t hl = (uint32_t)__ffsll((unsigned long long)h) - 1u;
+        BzxBinHit r;
+        r.bin = ch * PER + hl;
+        r.incl = __shfl(in, (int)hl);
+        r.cnt = __shfl(cv, (int)hl);
+        return r;
+    }
+    BzxBinHit none;
+    none.bin = BS_NT * PER;
+    none.incl = none.cnt = 0;
+    return none;
+}
+
+// The walk of segment `seg` of `nseg`: a start bit (bit b % PER of flagw[b / PER]) for every bucket of the segment.
+template <int PER>
+__device__ __forceinline__ void greedy_walk(const uint32_t *coarse, uint32_t *flagw, uint32_t total, uint32_t nseg, uint32_t seg)
+{
+    constexpr uint32_t BINS = BS_NT * PER;
+    uint32_t s = 0, base = 0, end = BINS;           // first bin and first rank of the bucket being filled; the next segment's first bin
+    if (seg) {
+        const BzxBinHit h = greedy_find<PER>(coarse, 0, (seg * total + nseg - 1u) / nseg);
+        s = h.bin + 1u;                             // (the first bin with EXCLUSIVE prefix >= the target follows the hit)
+        base = h.incl;
+    }
+    if (seg + 1u < nseg) {
+        end = greedy_find<PER>(coarse, s ? (s - 1u) / PER : 0u, ((seg + 1u) * total + nseg - 1u) / nseg).bin + 1u;
+        end = end < BINS ? end : BINS;
+    }
+    while (s < end) {
+        if (bzx_lane() == 0) atomicOr(&flagw[s / PER], 1u << (s % PER));
+        const BzxBinHit h = greedy_find<PER>(coarse, s / PER, base + BS_C + 1u);      // the first bin that no longer fits
+        if (h.bin <= s) {                           // bin s alone is above BS_C
+            s++;
+            base = h.incl;
+        } else {
+            s = h.bin;
+            base = h.incl - h.cnt;
+        }
+    }
+}
+
+// WINDOWS: the window rule (the regrouping pass); otherwise the greedy packing.
+template <int BINS, bool TAB16 = false, bool WINDOWS = false>
 __device__ __forceinline__ uint32_t form_buckets(uint32_t total)
 {
     constexpr int PER = BINS / BS_NT;
     const uint32_t tid = threadIdx.x, bin0 = tid * PER;
-    uint32_t c[PER], sum = 0, e8 = 0, e6 = 0, e4 = 0;
+    uint32_t c[PER], sum = 0, excl, fl = 0, nf = 0;
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         c[k] = TAB(bin0 + k);
         sum += c[k];
-        const uint32_t m = c[k] <= BS_ISO ? c[k] : 0u;
-        e8 += m > BS_C / 8 ? m : 0u;
-        e6 += m > BS_C / 6 ? m : 0u;
-        e4 += m > BS_C / 4 ? m : 0u;
     }
-    const uint32_t prevc = tid ? TAB(bin0 - 1) : 0u;
-    if (__any(e8 != 0)) {
-        e8 = bzx_wave_incl_sum(e8);
-        e6 = bzx_wave_incl_sum(e6);
-        e4 = bzx_wave_incl_sum(e4);
-        if (bzx_lane() == 63) {
-            atomicAdd(&b_bcast[8], e8);
-            if (e6) atomicAdd(&b_bcast[9], e6);
-            if (e4) atomicAdd(&b_bcast[10], e4);
+    if constexpr (WINDOWS) {
+        uint32_t e8 = 0, e6 = 0, e4 = 0;
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const uint32_t m = c[k] <= BS_ISO ? c[k] : 0u;
+            e8 += m > BS_C / 8 ? m : 0u;
+            e6 += m > BS_C / 6 ? m : 0u;
+            e4 += m > BS_C / 4 ? m : 0u;
         }
+        const uint32_t prevc = tid ? TAB(bin0 - 1) : 0u;
+        if (__any(e8 != 0)) {
+            e8 = bzx_wave_incl_sum(e8);
+            e6 = bzx_wave_incl_sum(e6);
+            e4 = bzx_wave_incl_sum(e4);
+            if (bzx_lane() == 63) {
+                atomicAdd(&b_bcast[8], e8);
+                if (e6) atomicAdd(&b_bcast[9], e6);
+                if (e4) atomicAdd(&b_bcast[10], e4);
+            }
+        }
+        uint32_t tot;
+        excl = bzx_block_excl_sum<BS_NT>(sum, b_scratch, tot);      // (its first barrier publishes b_bcast[8..10])
+        const uint32_t allow = total >> BS_ISO_SHIFT;
+        if (b_bcast[8] <= allow) bucket_flags<BS_C / 8>(c, bin0, excl, prevc, fl, nf);
+        else if (b_bcast[9] <= allow) bucket_flags<BS_C / 6>(c, bin0, excl, prevc, fl, nf);
+        else if (b_bcast[10] <= allow) bucket_flags<BS_C / 4>(c, bin0, excl, prevc, fl, nf);
+        else bucket_flags<BS_ISO>(c, bin0, excl, prevc, fl, nf);
+    } else {
+        // b_start, b_first (and b_cur) are dead here: the coarse prefixes and the flag words live in them.  The counts
+        // stay in TAB until the walk is done (the bucket ids overwrite them behind the second scan's barriers).
+        uint32_t *coarse = b_start, *flagw = b_first;
+        const uint32_t incl = bzx_wave_incl_sum(sum);
+        if (bzx_lane() == 63) b_scratch[bzx_wave()] = incl;
+        __syncthreads();
+        uint32_t pre = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < BS_NW; i++) pre += i < bzx_wave() ? b_scratch[i] : 0u;
+        excl = pre + incl - sum;
+        coarse[tid] = pre + incl;
+        flagw[tid] = 0;
+        __syncthreads();
+        uint32_t nseg = total / (16u * BS_C);
+        nseg = nseg < 1u ? 1u : nseg > BS_NW ? BS_NW : nseg;
+        if (bzx_wave() < nseg) greedy_walk<PER>(coarse, flagw, total, nseg, bzx_wave());
+        __syncthreads();
+        fl = flagw[tid];
+        nf = (uint32_t)__popc(fl);
     }
-    uint32_t tot;
-    const uint32_t excl = bzx_block_excl_sum<BS_NT>(sum, b_scratch, tot);      // (its first barrier publishes b_bcast[8..10])
-    const uint32_t allow = total >> BS_ISO_SHIFT;
-    uint32_t fl = 0, nf = 0;
-    if (b_bcast[8] <= allow) bucket_flags<BS_C / 8>(c, bin0, excl, prevc, fl, nf);
-    else if (b_bcast[9] <= allow) bucket_flags<BS_C / 6>(c, bin0, excl, prevc, fl, nf);
-    else if (b_bcast[10] <= allow) bucket_flags<BS_C / 4>(c, bin0, excl, prevc, fl, nf);
-    else bucket_flags<BS_ISO>(c, bin0, excl, prevc, fl, nf);
     uint32_t nbk;
     const uint32_t fexcl = bzx_block_excl_sum<BS_NT>(nf, b_scratch, nbk);
     if (nbk > BS_MAX_BK) return 0;
@@ -388,7 +484,6 @@ __device__ bool deep_process(const BzxBatch &B, uint32_t b, uint32_t j_, uint32_
         constexpr uint32_t NB2 = 1u << BS_BIN2;
         for (uint32_t i = tid; i < NB2 + (NB2 >> 5); i += BS_NT) b_tab[i] = 0;
         if (tid == 0) b_bcast[1] = 0;
-        if (tid < 3) b_bcast[8 + tid] = 0;
         __syncthreads();
         for (uint32_t i = tid; i < cnt; i += BS_NT) atomicAdd(&TAB((uint32_t)(src[i] >> (64 - BS_BIN2))), 1u);
         __syncthreads();
@@ -441,7 +536,6 @@ __global__ __launch_bounds__(BS_NT) void bzx_bsplit_kernel(BzxBatch B)
             b_bcast[1] = 0;
             b_bcast[3] = 0;
             b_bcast[4] = 0;
-            b_bcast[8] = b_bcast[9] = b_bcast[10] = 0;
             B.blk[b].pack_word = 0;              // (until the stream is laid out: deeper splits spent on the block)
             B.blk[b].n_mtf = 0xFFFFFFFFu;        // (until the MTF stage: smallest depth, in symbols, at which a bucket gave up)
             B.blk[b].n_groups = 0;               // (until the Huffman stage: buckets that gave up and are still open)
@@ -2148,7 +2242,7 @@ __global__ __launch_bounds__(BS_NT) void bzx_brank_giant_kernel(BzxBatch B)
                 const uint32_t sh = span < NB ? 0u : 32u - (uint32_t)__builtin_clz(span) - BS_BIN2;      // (span >> sh) < NB
                 for (uint32_t i = tid; i < G; i += BS_NT) atomicAdd(&TAB(((uint32_t)(tmp[i] >> 32) - lo) >> sh), 1u);
                 __syncthreads();
-                nbk = form_buckets<(int)NB>(G);
+                nbk = form_buckets<(int)NB, false, true>(G);
                 if (nbk) {
                     // sub-buckets of one member join a neighbour; b_first[k] becomes the sub-bucket of bucket k, b_start is
                     // compacted in place; b_cur[k']: members dealt so far, later the item's place, ~0 (coarse) or ~1 (dealt again)
